@@ -16,10 +16,17 @@ DDIM updates, on synthetic inputs already resident in HBM
   --parallelism cfgxframes (BASELINE config 5 on 8 GPUs): the two CFG halves on two rank groups, frames sharded inside
       each group; per step the halves exchange their predictions pairwise for the CFG combine.  Strong scaling.
 Rank 0 prints ONE JSON line.
+
+A plain run only sets up, warms up, times the K steps and prints the line (plus the outputs with --dump-outputs).  --full adds
+what needs runs of its own after the timed region: the per-kernel-class pass and the roofline / attention blocks, the parity
+check of the timed launch mode against the eager one-stream step, the vendor-GEMM ceiling and the CPU baseline.
+--dump-outputs DIR: rank 0 writes the latents its last timed step returned (DIR/pano_latent.npy, DIR/pers_latent.npy, float32);
+inputs, weights and the RNG streams are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
 import os
+import random
 import socket
 import subprocess
 import sys
@@ -225,8 +232,13 @@ def main(argv=None):
     ap.add_argument("--parallelism", default="samples", choices=["samples", "frames", "cfgxframes"])
     ap.add_argument("--width-div", type=int, default=1, help="debug only: reduced-width model (INVALID as a benchmark)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the per-kernel-class pass (roofline / attention blocks), the parity check, "
+                         "the vendor-GEMM ceiling and the CPU baseline (off: the plain run times the steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the latents of the last timed step (rank 0) as DIR/<name>.npy, float32")
     ap.add_argument("--cpu-baseline", default="step", choices=["step", "sample", "none", "direct"],
-                    help="step: one full-width cfg1 oracle step on the host cores (~1 min) scaled to the workload by the FLOP ratio; "
+                    help="with --full: step: one full-width cfg1 oracle step on the host cores (~1 min) scaled to the workload by the FLOP ratio; "
                          "direct: one oracle step of the benchmarked workload (--workload) itself (~9 min at cfg2); sample: bounded block sample (~10 s)")
     ap.add_argument("--cpu-threads", default="probe", help="host threads of the CPU baseline: probe (fastest on a miniature of the step), all (os.cpu_count()), or a number")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -294,12 +306,15 @@ def main(argv=None):
     mv.warp_streams = bool(args.warp_streams)
     # samples: every rank its own sample (seed); frame modes: ONE sample, replicated conditioning, identical RNG streams
     seed = 1 + rank if mode == "samples" else 1
+    # the WarpAttn coins (Python's RNG) and the per-step IP-adapter noise (torch's generators, which start from a random seed
+    # otherwise): identical from run to run, like the inputs
+    random.seed(seed)
+    torch.manual_seed(seed)
     inp = synthetic.mv_inputs(frames=frames, pano_hw=w["pano_hw"], pers_hw=w["pers_hw"], seed=seed,
                               sam_frames=max(16, frames), dtype=dt, device=dev)
     cams = synthetic.icosahedron_cameras(90, w["pers_px"], device=dev)
     shard, pair = None, None
     if mode != "samples":
-        import random
         from imagine360_amd.dist import FrameShard, exchange_cfg_halves, shard_mv_inputs
         torch.manual_seed(1234)
         random.seed(1234)
@@ -402,10 +417,17 @@ def main(argv=None):
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed step receives: the updated latents of the last timed step (2 + 5 MB at cfg2)
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        last = (graphed.pano_lat, graphed.pers_lat) if graphed is not None else (pano_lat, pers_lat)
+        for name, t in zip(("pano_latent", "pers_latent"), last):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), t.float().cpu().numpy())
     # per-kernel-class durations: the same K steps once more, issued eagerly with HIP events around every launch
     # of our kernels (a graph replay has no per-launch host hook); kernel durations do not depend on how they were launched
     eager_elapsed = None
-    if rank == 0 and shard is None and not plumbing:
+    if args.full and rank == 0 and shard is None and not plumbing:
         if graphed is not None:
             pano_lat, pers_lat = graphed.pano_lat.clone(), graphed.pers_lat.clone()
 
@@ -425,8 +447,7 @@ def main(argv=None):
     # parity of the BENCHMARKED launch mode at the benchmarked size (outside the timed region, one step): from identical
     # latents, RNG states and timestep, the captured two-stream hipGraph against the same step issued eagerly on one stream
     parity_check = None
-    if rank == 0 and shard is None and graphed is not None:
-        import random
+    if args.full and rank == 0 and shard is None and graphed is not None:
         saved_counters = (kernels.STATS, kernels.SHAPES)          # (the profile pass's per-launch flop / byte counters: not these steps')
         kernels.STATS = kernels.SHAPES = None
         p0, q0 = graphed.pano_lat.clone(), graphed.pers_lat.clone()
@@ -613,7 +634,7 @@ def main(argv=None):
                 fl = sum(v[1][0] for v in mf)
                 out["attention"]["mfma_bound_kinds"] = {"tflops": fl / t / 1e12, "frac": fl / t / 1e12 / MFMA_PEAK_TFLOPS,
                                                         "note": "self + WarpAttn launches only (the kinds whose roofline is the matrix pipe); `frac` above stays the figure over ALL launches"}
-        if world == 1 and args.cpu_baseline != "none":
+        if args.full and world == 1 and args.cpu_baseline != "none":
             if args.cpu_baseline == "sample":
                 out["cpu_baseline"] = cpu_baseline_sample(args)
             else:

@@ -22,13 +22,13 @@ for mode in 1stream 2stream; do
     extra=""
     [ $mode = 1stream ] && extra="--dual-stream 0"
     cd /tmp
-    rocprofv3 --kernel-trace --stats -M --output-format csv -d $D -o bench -- python $R/bench.py --no-cpu-baseline $extra "$@" > $D/bench_stdout.log 2>&1
+    rocprofv3 --kernel-trace --stats -M --output-format csv -d $D -o bench -- python $R/bench.py --full --no-cpu-baseline $extra "$@" > $D/bench_stdout.log 2>&1
     cd $R
     stats=$(find $D -name "*kernel_stats.csv" | head -1)
     trace=$(find $D -name "*kernel_trace.csv" | head -1)
     tag=${ROUND:-r06}_${HASH}_bench_cfg2$([ $mode = 1stream ] && echo _1stream)
     if [ -n "$stats" ]; then
-        { echo "# rocprofv3 --kernel-trace --stats -M -- python bench.py --no-cpu-baseline $extra $*   (commit $HASH, libim360_kernels.so sha256 $LIBSHA)"; cat "$stats"; } > $OUT/${tag}_kernel_stats.csv
+        { echo "# rocprofv3 --kernel-trace --stats -M -- python bench.py --full --no-cpu-baseline $extra $*   (commit $HASH, libim360_kernels.so sha256 $LIBSHA)"; cat "$stats"; } > $OUT/${tag}_kernel_stats.csv
     fi
     grep '^{"metric"' $D/bench_stdout.log | tail -1 > $OUT/${tag}_profiled.json
     if [ $mode = 1stream ] && [ -n "$trace" ]; then

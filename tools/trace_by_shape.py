@@ -37,7 +37,7 @@ def main():
     ap.add_argument("--per-step", type=int, default=2)
     ap.add_argument("--top", type=int, default=70)
     ap.add_argument("--skip-steps", type=int, default=0,
-                    help="trailing steps to leave out (bench.py ends with its parity check: replayed graph, eager one-stream step, eager "
+                    help="trailing steps to leave out (bench.py --full ends with its parity check: replayed graph, eager one-stream step, eager "
                          "TWO-stream step -- `--skip-steps 1` tabulates the eager one-stream step, where every kernel has the chip alone)")
     args = ap.parse_args()
     rows = list(csv.DictReader(open(args.csv)))
