@@ -611,6 +611,57 @@ __global__ void cfg_ddim_kernel(const T* __restrict__ uncond, const T* __restric
     }
 }
 
+// ---- CFG combine + the full DDIMScheduler.step (diffusers/schedulers/scheduling_ddim.py:251-373), one elementwise pass:
+//      m = u + g (c - u);  x0 / e from the prediction type (mode bits 0-1: 0 epsilon, 1 v, 2 sample);  x0 clamped to [-1, 1]
+//      (bit 2);  e re-derived from the clamped x0 (bit 3);  out = sa_prev x0 + dir e + sigma z.  sa, sb = sqrt(a_t), sqrt(1 - a_t);
+//      dir = sqrt(1 - a_prev - sigma^2), sigma = eta sqrt(var) come from fp64 host math.  noise == nullptr: z = 0.
+template <typename T>
+__global__ void cfg_ddim_step_kernel(const T* __restrict__ uncond, const T* __restrict__ cond, const T* __restrict__ x,
+                                     const T* __restrict__ noise, T* __restrict__ out, long n8, float g, float sa, float sb,
+                                     float sap, float dir, float sigma, int mode, const float* __restrict__ coef) {
+    if (coef != nullptr) {          // (guidance, sa, sb, sa_prev, dir, sigma) read on the device: hipGraph replay
+        g = coef[0];
+        sa = coef[1];
+        sb = coef[2];
+        sap = coef[3];
+        dir = coef[4];
+        sigma = coef[5];
+    }
+    const int pred = mode & 3;
+    const bool clip = (mode & 4) != 0, clipped_out = (mode & 8) != 0;
+    const float isa = 1.0f / sa, isb = 1.0f / sb;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
+        float u[8], c[8], s[8], z[8];
+        unpack8<T>(((const uint4*)uncond)[i], u);
+        unpack8<T>(((const uint4*)cond)[i], c);
+        unpack8<T>(((const uint4*)x)[i], s);
+        if (noise != nullptr) unpack8<T>(((const uint4*)noise)[i], z);
+        else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) z[e] = 0.0f;
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float m = u[e] + g * (c[e] - u[e]);
+            float x0, eps;
+            if (pred == 0) {
+                x0 = (s[e] - sb * m) * isa;
+                eps = m;
+            } else if (pred == 1) {
+                x0 = sa * s[e] - sb * m;
+                eps = sa * m + sb * s[e];
+            } else {
+                x0 = m;
+                eps = m;                     // the reference's direction term multiplies the model output, i.e. x0 itself
+            }
+            if (clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+            if (clipped_out) eps = (s[e] - sa * x0) * isb;
+            s[e] = sap * x0 + dir * eps + sigma * z[e];
+        }
+        ((uint4*)out)[i] = pack8<T>(s);
+    }
+}
+
 static inline int pick_slabs(long N, long HW) {
     long s = (2048 + N - 1) / N;
     const long maxs = HW / 64 > 0 ? HW / 64 : 1;
@@ -949,6 +1000,36 @@ extern "C" __attribute__((visibility("default"))) int im360_cfg_ddim_update(cons
         im360_set_error("cfg_ddim_update: dtype %d unsupported", dtype);
         return IM360_ERR_UNSUPPORTED;
     }
+    IM360_CHECK_LAUNCH();
+    return IM360_OK;
+}
+
+// out = DDIMScheduler.step(uncond + g (cond - uncond), x, noise) for any prediction type / clip / eta, n elements (n % 8 == 0),
+// all same dtype; noise may be null (zero noise)
+extern "C" __attribute__((visibility("default"))) int im360_cfg_ddim_step(const void* uncond, const void* cond, const void* x, const void* noise,
+                                   void* out, int64_t n, float guidance, float sqrt_a, float sqrt_b, float sqrt_a_prev,
+                                   float dir, float sigma, int mode, int dtype, void* stream, const void* coef_dev) {
+    using namespace im360;
+    IM360_CHECK_ARG(uncond && cond && x && out, "cfg_ddim_step: null pointer");
+    IM360_CHECK_ARG(n > 0 && (n % 8) == 0, "cfg_ddim_step: n=%ld must be a positive multiple of 8", (long)n);
+    IM360_CHECK_ARG(((uintptr_t)uncond % 16) == 0 && ((uintptr_t)cond % 16) == 0 && ((uintptr_t)x % 16) == 0 &&
+                    ((uintptr_t)noise % 16) == 0 && ((uintptr_t)out % 16) == 0, "cfg_ddim_step: misaligned pointer");
+    IM360_CHECK_ARG(mode >= 0 && mode < 16 && (mode & 3) != 3, "cfg_ddim_step: mode %d unsupported", mode);
+    IM360_CHECK_ARG(noise || coef_dev || sigma == 0.0f, "cfg_ddim_step: sigma=%g needs a noise tensor", (double)sigma);
+    const long n8 = n / 8;
+    const unsigned blocks = (unsigned)((n8 + 255) / 256 > 4096 ? 4096 : (n8 + 255) / 256);
+    hipStream_t s = (hipStream_t)stream;
+#define IM360_DDIM_STEP(T)                                                                                              \
+    hipLaunchKernelGGL((cfg_ddim_step_kernel<T>), dim3(blocks), dim3(256), 0, s, (const T*)uncond, (const T*)cond,      \
+                       (const T*)x, (const T*)noise, (T*)out, n8, guidance, sqrt_a, sqrt_b, sqrt_a_prev, dir, sigma, mode, \
+                       (const float*)coef_dev)
+    if (dtype == 0) IM360_DDIM_STEP(__bf16);
+    else if (dtype == 1) IM360_DDIM_STEP(_Float16);
+    else {
+        im360_set_error("cfg_ddim_step: dtype %d unsupported", dtype);
+        return IM360_ERR_UNSUPPORTED;
+    }
+#undef IM360_DDIM_STEP
     IM360_CHECK_LAUNCH();
     return IM360_OK;
 }

@@ -4,7 +4,10 @@ A cfg2 step is ~3000 kernel launches; issued from Python that is 0.4-0.6 s of ho
 launch-bound on a slow host.  Everything in the step is static-shaped and sync-free, so it is captured once and
 replayed: per step the host only refreshes four tiny device buffers (timestep, (guidance, cx, cv), the 7 WarpAttn
 coins drawn from Python's RNG in the reference's order) and calls replay().  The per-step IP-adapter noise is drawn
-inside the graph from torch's device generator (graph-safe philox state), like the reference's GPU path.
+inside the graph from torch's device generator (graph-safe philox state), like the reference's GPU path.  Stochastic
+sampling (eta > 0) draws the two variance noises inside the graph as well, right before each branch's update, from the
+caller's generator (registered with the graph) or the default one; the coefficients are then (guidance, sqrt a_t,
+sqrt b_t, sqrt a_prev, dir, sigma) for ``cfg_ddim_step``.
 """
 import random
 
@@ -34,22 +37,28 @@ class _PinnedUploads:
 
 
 class GraphedDenoiseStep:
-    def __init__(self, mv, scheduler, inputs, cameras, pano_latent, pers_latent, guidance, use_fps=True, warmup=2, cfg_pair=None):
+    def __init__(self, mv, scheduler, inputs, cameras, pano_latent, pers_latent, guidance, use_fps=True, warmup=2, cfg_pair=None,
+                 eta=0.0, generator=None, use_clipped_model_output=False, frame_shard=None):
         """``inputs``: the keyword tensors of MultiViewBaseModel.forward (CFG-batched, resident on the GPU);
         ``pano_latent`` [1,4,F,H,W] / ``pers_latent`` [1,m,4,F,h,w]: initial noisy latents.
         Frame-sharded models (``mv.set_frame_shard``) capture their all-to-alls with the step: the exchange buffers are
         pre-sized and cached (dist.FrameShard), RCCL collectives are stream operations.  ``cfg_pair``: process group of the
         two ranks holding the two CFG halves of the same frames (dist.cfg_frame_layout) -- their predictions are exchanged
-        inside the captured step before the CFG combine."""
+        inside the captured step before the CFG combine.
+        ``eta`` / ``generator`` / ``use_clipped_model_output``: DDIMScheduler.step's keywords (defaults: the eta = 0 update).
+        ``frame_shard`` (dist.FrameShard): with eta > 0 the variance noise is drawn for the whole clip and cut to the local
+        frames, like the initial noise."""
         self.mv, self.sch, self.inp, self.cams, self.g = mv, scheduler, inputs, cameras, float(guidance)
         self.cfg_pair = cfg_pair
+        self.eta, self.gen, self.clipped, self.shard = float(eta), generator, bool(use_clipped_model_output), frame_shard
+        self.step_kernel = scheduler.uses_step_kernel(self.eta, self.clipped)
         dev = pano_latent.device
         # private copies: the caller's tensors may alias the model-input buffers the body writes into
         init_pano, init_pers = pano_latent.clone(), pers_latent.clone()
         self.pano_lat = init_pano.clone()
         self.pers_lat = init_pers.clone()
         self.timestep = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.coef = torch.zeros(3, dtype=torch.float32, device=dev)
+        self.coef = torch.zeros(6 if self.step_kernel else 3, dtype=torch.float32, device=dev)
         self.use_fps = use_fps
         self.graph = None
         self._up_t, self._up_c = _PinnedUploads(self.timestep), _PinnedUploads(self.coef)
@@ -57,6 +66,7 @@ class GraphedDenoiseStep:
         # noise) and allocating the coin buffer used to take 7 Python draws, which shifted the streams of the default
         # (graphed) pipeline relative to the eager one and to the reference for the same seeds.
         py_state, cuda_state = random.getstate(), torch.cuda.get_rng_state(dev)
+        gen_state = generator.get_state() if generator is not None else None
         mv.draw_coins(dev)                       # allocates the device coin buffer
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
@@ -74,6 +84,8 @@ class GraphedDenoiseStep:
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
+        if generator is not None:
+            self.graph.register_generator_state(generator)      # each replay advances it like the eager draws would
         mv.coins_preloaded = True
         try:
             # thread-local capture mode: a RCCL watchdog / other host thread touching the runtime must not abort the capture
@@ -87,6 +99,8 @@ class GraphedDenoiseStep:
         random.setstate(py_state)
         torch.cuda.synchronize()
         torch.cuda.set_rng_state(cuda_state, dev)
+        if generator is not None:
+            generator.set_state(gen_state)
 
     def _body(self):
         inp = self.inp
@@ -109,17 +123,30 @@ class GraphedDenoiseStep:
             from .dist import exchange_cfg_halves
             pred_pano, pred_pers = exchange_cfg_halves(pred_pano, self.cfg_pair), exchange_cfg_halves(pred_pers, self.cfg_pair)
         self.pred_pano, self.pred_pers = pred_pano, pred_pers          # static graph-pool tensors (inspection / tests)
-        ldt = self.pano_lat.dtype            # latents may be kept in another 16-bit type than the model (the reference promotes)
+        ldt, mdt = self.pano_lat.dtype, pred_pano.dtype    # latents may be kept in another 16-bit type than the model (the reference promotes)
         pred_pano, pred_pers = pred_pano.to(ldt), pred_pers.to(ldt)
-        new_pano = self.sch.fused_cfg_step(pred_pano[0:1], pred_pano[1:2], self.g, None, self.pano_lat, coef_dev=self.coef)
-        new_pers = self.sch.fused_cfg_step(pred_pers[0:1], pred_pers[1:2], self.g, None, self.pers_lat, coef_dev=self.coef)
+        kw = dict(eta=self.eta, use_clipped_model_output=self.clipped)
+        new_pano = self.sch.fused_cfg_step(pred_pano[0:1], pred_pano[1:2], self.g, None, self.pano_lat, coef_dev=self.coef,
+                                           noise=self._noise(self.pano_lat, mdt, 2), **kw)
+        new_pers = self.sch.fused_cfg_step(pred_pers[0:1], pred_pers[1:2], self.g, None, self.pers_lat, coef_dev=self.coef,
+                                           noise=self._noise(self.pers_lat, mdt, 3), **kw)
         self.pano_lat.copy_(new_pano)
         self.pers_lat.copy_(new_pers)
 
+    def _noise(self, latent, model_dtype, frame_dim):
+        """Variance noise of one branch (eta > 0 only), drawn where the reference's ``step`` draws it."""
+        if self.eta <= 0:
+            return None
+        from .pipeline import variance_noise
+        return variance_noise(self.sch, latent, model_dtype, self.gen, "device", self.shard, frame_dim, self.clipped)
+
     def _upload(self, t_host, draw=True):
-        cx, cv = self.sch.coefficients(t_host)
         self._up_t.upload(self.timestep, [int(t_host)])
-        self._up_c.upload(self.coef, [self.g, cx, cv])
+        if self.step_kernel:
+            self._up_c.upload(self.coef, list(self.sch.step_coefficients(t_host, self.eta, self.g)))
+        else:
+            cx, cv = self.sch.coefficients(t_host)
+            self._up_c.upload(self.coef, [self.g, cx, cv])
         if draw:
             self.mv.draw_coins(self.timestep.device)
 

@@ -50,6 +50,7 @@ _SIGNATURES = {
     "im360_circular_pad_w": (_INT, [_PTR] * 2 + [_I64] * 4 + [_INT, _PTR]),
     "im360_circular_pad_hw": (_INT, [_PTR] * 2 + [_I64] * 8 + [_PTR]),
     "im360_cfg_ddim_update": (_INT, [_PTR] * 4 + [_I64] + [_F32] * 3 + [_INT, _PTR, _PTR]),
+    "im360_cfg_ddim_step": (_INT, [_PTR] * 5 + [_I64] + [_F32] * 6 + [_INT, _INT, _PTR, _PTR]),
     "im360_layernorm": (_INT, [_PTR] * 6 + [_I64] * 5 + [_F32, _INT, _PTR]),
     "im360_geglu": (_INT, [_PTR] * 2 + [_I64] * 2 + [_INT, _PTR]),
     "im360_linear_geglu": (_INT, [_PTR] * 4 + [_I64] * 3 + [_INT, _PTR]),
@@ -837,6 +838,31 @@ def cfg_ddim_update(uncond, cond, sample, guidance, cx, cv, coef_dev=None):
     rc = lib().im360_cfg_ddim_update(_p(uncond), _p(cond), _p(sample), _p(out), sample.numel(),
                                      float(guidance), float(cx), float(cv), _dt(sample), _stream(), _p(coef_dev))
     _check(rc, "im360_cfg_ddim_update")
+    return out
+
+
+DDIM_PRED_MODE = {"epsilon": 0, "v_prediction": 1, "sample": 2}
+DDIM_CLIP_SAMPLE, DDIM_CLIPPED_OUTPUT = 4, 8
+
+
+def cfg_ddim_step(uncond, cond, sample, noise, mode, coefs, coef_dev=None):
+    """DDIMScheduler.step(uncond + g (cond - uncond), t, sample) for any prediction type / clip / eta in one pass.
+    ``mode``: DDIM_PRED_MODE | DDIM_CLIP_SAMPLE | DDIM_CLIPPED_OUTPUT; ``coefs`` = (guidance, sqrt_a, sqrt_b, sqrt_a_prev,
+    dir, sigma) (DDIMScheduler.step_coefficients); ``noise``: variance noise like ``sample`` or None (zero noise, refused
+    with sigma > 0); ``coef_dev`` = device float32[6] holding ``coefs``, read by the kernel instead (graph replay)."""
+    _dev(uncond, cond, sample, noise)
+    assert uncond.is_contiguous() and cond.is_contiguous() and sample.is_contiguous()
+    assert uncond.shape == cond.shape == sample.shape and uncond.dtype == cond.dtype == sample.dtype
+    if noise is not None:
+        assert noise.is_contiguous() and noise.shape == sample.shape and noise.dtype == sample.dtype
+    elif coef_dev is None and coefs[5] != 0.0:
+        raise ValueError("cfg_ddim_step: sigma > 0 needs a noise tensor")
+    if coef_dev is not None:
+        assert coef_dev.dtype == torch.float32 and coef_dev.numel() == 6 and coef_dev.is_cuda
+    out = torch.empty_like(sample)
+    rc = lib().im360_cfg_ddim_step(_p(uncond), _p(cond), _p(sample), _p(noise), _p(out), sample.numel(),
+                                   *(float(v) for v in coefs), int(mode), _dt(sample), _stream(), _p(coef_dev))
+    _check(rc, "im360_cfg_ddim_step")
     return out
 
 

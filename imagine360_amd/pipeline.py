@@ -8,7 +8,9 @@ surface, rebuilt for the MI355X:
     latents, the nearest-E2P index maps of init_noise, the pad-4 latent for the decode;
   * RNG: ``rng="host"`` draws every Gaussian (init noise, VAE posterior samples, per-step IP noise) from
     the CPU generator in the reference's order, so results are comparable to the reference's CPU path
-    on the same seeds; ``rng="device"`` (default) draws on the GPU like the reference's GPU path.
+    on the same seeds; ``rng="device"`` (default) draws on the GPU like the reference's GPU path;
+  * stochastic DDIM (``eta > 0``): per step, after the model's IP-adapter noise, the panorama then the perspective variance
+    noise is drawn (from ``generator`` when given), exactly where the reference's ``scheduler.step`` draws it.
 
 CLIP text encoding and SAM feature extraction are outside the hot path: the
 pipeline uses ``text_encoder``/``tokenizer``/``image_encoder`` when given, and also accepts precomputed
@@ -24,6 +26,25 @@ from . import kernels
 from . import pano_geometry as G
 
 VAE_SCALE = 0.18215        # hard-coded in the reference pipeline (:303, :440, :465)
+
+
+def variance_noise(scheduler, latent, model_dtype, generator, rng, shard=None, frame_dim=2, use_clipped_model_output=False):
+    """The variance noise DDIMScheduler.step draws for ``latent`` (scheduling_ddim.py:354-366), in the latent's dtype.
+    ``rng="device"``: torch.randn on the latent's device from ``generator`` (None: the global device generator) in the dtype
+    the reference draws in; ``"host"``: float32 from the CPU ``generator`` (or the global CPU generator), then moved.
+    ``shard`` (dist.FrameShard): drawn for the whole clip along ``frame_dim`` and cut to the local frames."""
+    shape = list(latent.shape)
+    if shard is not None:
+        shape[frame_dim] = shard.total
+    if rng == "host":
+        gen = generator if generator is not None and generator.device.type == "cpu" else None
+        z = torch.randn(shape, generator=gen, dtype=torch.float32)
+    else:
+        dt = scheduler.noise_dtype(model_dtype, latent.dtype, use_clipped_model_output)
+        z = torch.randn(shape, generator=generator, device=latent.device, dtype=dt)
+    if shard is not None:
+        z = shard.take(z, frame_dim)
+    return z.to(device=latent.device, dtype=latent.dtype).contiguous()
 
 
 @dataclass
@@ -260,8 +281,9 @@ class AnimationPipeline:
                 inputs = dict(latents=in_pers, pano_latent=in_pano, prompt_embd=text_pers, pano_prompt_embd=text_pano,
                               fps_tensor_pano=fps_pano, fps_tensor_pers=fps_pers, reference_images_clip_feat_pano=feat_pano,
                               reference_images_clip_feat_pers=feat_pers, relative_position_tensor=rel, pitchs_tensor=pitch)
+                stoch = dict(eta=eta, generator=generator, frame_shard=sh) if eta > 0 else {}
                 graphed = GraphedDenoiseStep(self.mv_base_model, self.scheduler, inputs, cameras, pano_latent, pers_latent,
-                                             guidance_scale_text, use_fps=use_fps_condition, warmup=1)       # one eager step fills every cache
+                                             guidance_scale_text, use_fps=use_fps_condition, warmup=1, **stoch)       # one eager step fills every cache
             for i, t in enumerate(self.progress_bar(steps_host)):
                 if graphed is not None:
                     pano_latent, pers_latent = graphed.step(t)
@@ -274,8 +296,8 @@ class AnimationPipeline:
                     use_ip_plus_cross_attention=use_ip_plus_cross_attention, fps_tensor_pano=fps_pano, fps_tensor_pers=fps_pers,
                     reference_images_clip_feat_pano=feat_pano, reference_images_clip_feat_pers=feat_pers,
                     relative_position_tensor=rel, pitchs_tensor=pitch)
-                pano_latent = self._cfg_step(pred_pano, guidance_scale_text, t, pano_latent)
-                pers_latent = self._cfg_step(pred_pers, guidance_scale_text, t, pers_latent)
+                pano_latent = self._cfg_step(pred_pano, guidance_scale_text, t, pano_latent, eta, generator, sh, 2)
+                pers_latent = self._cfg_step(pred_pers, guidance_scale_text, t, pers_latent, eta, generator, sh, 3)
                 if trace is not None:
                     trace.append(pano_latent.clone())
                 if callback is not None and i % callback_steps == 0:
@@ -296,6 +318,9 @@ class AnimationPipeline:
             if sh is not None:
                 self.mv_base_model.set_frame_shard(None)      # also when the loop raises: the model must not stay sharded
 
-    def _cfg_step(self, pred, g, t, latent):
+    def _cfg_step(self, pred, g, t, latent, eta=0.0, generator=None, shard=None, frame_dim=2):
         u, c = pred.to(latent.dtype).chunk(2)          # latents_dtype may differ from the model dtype (the reference promotes)
+        if eta > 0:
+            z = variance_noise(self.scheduler, latent, pred.dtype, generator, self.rng, shard, frame_dim)
+            return self.scheduler.fused_cfg_step(u, c, g, t, latent, eta=eta, noise=z)
         return self.scheduler.fused_cfg_step(u, c, g, t, latent)

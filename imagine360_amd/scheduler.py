@@ -3,8 +3,11 @@
 
 Coefficients are tabulated on the host in fp32 exactly like the reference (so ``alphas_cumprod`` matches
 bit for bit) and combined in fp64 python floats; on the GPU the whole CFG + update chain of the
-pipeline is one elementwise HIP kernel (``fused_cfg_step``).
+pipeline is one elementwise HIP kernel (``fused_cfg_step``): the eta = 0 v / epsilon update of the dual pipeline on
+``cfg_ddim_update``, everything else ``step`` supports (eta > 0, clip_sample, prediction_type="sample",
+use_clipped_model_output) on ``cfg_ddim_step``.
 """
+import math
 from dataclasses import dataclass
 
 import numpy as np
@@ -21,6 +24,23 @@ class DDIMSchedulerOutput:
 
 class _Cfg(dict):
     __getattr__ = dict.get
+
+
+def betas_for_alpha_bar(num_diffusion_timesteps, max_beta=0.999):
+    """scheduling_ddim.py:49-79: the Glide cosine schedule ("squaredcos_cap_v2")."""
+    def alpha_bar(time_step):
+        return math.cos((time_step + 0.008) / 1.008 * math.pi / 2) ** 2
+
+    betas = []
+    for i in range(num_diffusion_timesteps):
+        t1, t2 = i / num_diffusion_timesteps, (i + 1) / num_diffusion_timesteps
+        betas.append(min(1 - alpha_bar(t2) / alpha_bar(t1), max_beta))
+    return torch.tensor(betas)
+
+
+def _sqrt(v):
+    """``v ** 0.5`` of a host float with torch.sqrt's answer (NaN) for a negative radicand instead of a complex number."""
+    return math.sqrt(v) if v >= 0 else float("nan")
 
 
 def rescale_zero_terminal_snr(betas):
@@ -45,6 +65,8 @@ class DDIMScheduler:
             self.betas = torch.linspace(beta_start, beta_end, num_train_timesteps, dtype=torch.float32)
         elif beta_schedule == "scaled_linear":
             self.betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
+        elif beta_schedule == "squaredcos_cap_v2":
+            self.betas = betas_for_alpha_bar(num_train_timesteps)
         else:
             raise NotImplementedError(f"{beta_schedule} is not implemented for {self.__class__}")
         if rescale_betas_zero_snr:
@@ -91,17 +113,90 @@ class DDIMScheduler:
             raise ValueError(f"prediction_type {self.config.prediction_type} unsupported")
         return cx, cv
 
+    def uses_step_kernel(self, eta=0.0, use_clipped_model_output=False):
+        """True when an update needs ``cfg_ddim_step``: anything but the eta = 0, unclipped v / epsilon update that
+        ``coefficients`` / ``cfg_ddim_update`` compute."""
+        return (eta != 0.0 or bool(self.config.clip_sample) or bool(use_clipped_model_output)
+                or self.config.prediction_type not in ("v_prediction", "epsilon"))
+
+    def kernel_mode(self, use_clipped_model_output=False):
+        """Mode bits of ``cfg_ddim_step``: prediction type | clip_sample | use_clipped_model_output."""
+        pt = self.config.prediction_type
+        if pt not in kernels.DDIM_PRED_MODE:
+            raise ValueError(f"prediction_type given as {pt} must be one of `epsilon`, `sample`, or `v_prediction`")
+        return (kernels.DDIM_PRED_MODE[pt] | (kernels.DDIM_CLIP_SAMPLE if self.config.clip_sample else 0)
+                | (kernels.DDIM_CLIPPED_OUTPUT if use_clipped_model_output else 0))
+
+    def step_coefficients(self, timestep, eta=0.0, guidance=1.0):
+        """Coefficient vector of ``cfg_ddim_step``: (guidance, sqrt(a_t), sqrt(1 - a_t), sqrt(a_prev), dir, sigma) with
+        sigma = eta sqrt(var), var = (b_prev / b_t)(1 - a_t / a_prev), dir = sqrt(1 - a_prev - sigma^2), in fp64 from the
+        fp32 ``alphas_cumprod`` (scheduling_ddim.py:300-368).  A negative radicand gives NaN like the reference; the noise
+        term is only added for eta > 0 (a negative eta still enters ``dir``, as in the reference)."""
+        a_t, a_prev = self._alphas(timestep)
+        b_t, b_prev = 1.0 - a_t, 1.0 - a_prev
+        var = (b_prev / b_t) * (1.0 - a_t / a_prev)
+        sigma = eta * _sqrt(var)
+        return (float(guidance), _sqrt(a_t), _sqrt(b_t), _sqrt(a_prev), _sqrt(1.0 - a_prev - sigma ** 2),
+                sigma if eta > 0 else 0.0)
+
+    def noise_dtype(self, model_dtype, sample_dtype, use_clipped_model_output=False):
+        """dtype the reference's ``step`` draws its variance noise in: that of ``model_output`` after the v_prediction /
+        clipped-output rewrites, which combine it with the sample."""
+        if self.config.prediction_type == "v_prediction" or use_clipped_model_output:
+            return torch.promote_types(model_dtype, sample_dtype)
+        return model_dtype
+
     def step(self, model_output, timestep, sample, eta=0.0, use_clipped_model_output=False, generator=None,
              variance_noise=None, return_dict=True):
-        if eta != 0.0 or self.config.clip_sample:
-            raise NotImplementedError("the dual pipeline runs eta = 0, clip_sample = False (prompt-dual.yaml:48-56)")
-        cx, cv = self.coefficients(timestep)
-        prev = cx * sample + cv * model_output
-        return DDIMSchedulerOutput(prev_sample=prev.to(sample.dtype)) if return_dict else (prev,)
+        """scheduling_ddim.py:251-373, formula for formula, in torch ops on the tensors' device."""
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        a_t, a_prev = self._alphas(timestep)
+        b_t = 1.0 - a_t
+        pt = self.config.prediction_type
+        if pt == "epsilon":
+            x0 = (sample - b_t ** 0.5 * model_output) / a_t ** 0.5
+        elif pt == "sample":
+            x0 = model_output
+        elif pt == "v_prediction":
+            x0 = a_t ** 0.5 * sample - b_t ** 0.5 * model_output
+        else:
+            raise ValueError(f"prediction_type given as {pt} must be one of `epsilon`, `sample`, or `v_prediction`")
+        if not self.uses_step_kernel(eta, use_clipped_model_output):
+            # the dual pipeline's update (eta = 0, no clipping): x_prev = cx x_t + cv model_output
+            cx, cv = self.coefficients(timestep)
+            prev = (cx * sample + cv * model_output).to(sample.dtype)
+            return DDIMSchedulerOutput(prev_sample=prev, pred_original_sample=x0) if return_dict else (prev,)
+        if pt == "v_prediction":
+            model_output = a_t ** 0.5 * model_output + b_t ** 0.5 * sample
+        if self.config.clip_sample:
+            x0 = torch.clamp(x0, -1, 1)
+        _, _, _, sa_prev, direction, sigma = self.step_coefficients(timestep, eta)
+        if use_clipped_model_output:
+            model_output = (sample - a_t ** 0.5 * x0) / b_t ** 0.5
+        prev = sa_prev * x0 + direction * model_output
+        if eta > 0:
+            if variance_noise is not None and generator is not None:
+                raise ValueError("Cannot pass both generator and variance_noise. Please make sure that either `generator` or"
+                                 " `variance_noise` stays `None`.")
+            if variance_noise is None:
+                variance_noise = torch.randn(model_output.shape, generator=generator, device=model_output.device,
+                                             dtype=model_output.dtype)
+            prev = prev + sigma * variance_noise
+        return DDIMSchedulerOutput(prev_sample=prev, pred_original_sample=x0) if return_dict else (prev,)
 
-    def fused_cfg_step(self, pred_uncond, pred_text, guidance_scale, timestep, sample, coef_dev=None):
-        """CFG combine + update in one HIP kernel (pipeline_animation_inference_dual.py:791-800).  ``coef_dev``:
-        device float32[3] (guidance, cx, cv) read by the kernel instead of host scalars (graph replay)."""
-        cx, cv = (0.0, 0.0) if coef_dev is not None else self.coefficients(timestep)
-        return kernels.cfg_ddim_update(pred_uncond.contiguous(), pred_text.contiguous(), sample.contiguous(),
-                                       guidance_scale, cx, cv, coef_dev=coef_dev)
+    def fused_cfg_step(self, pred_uncond, pred_text, guidance_scale, timestep, sample, coef_dev=None, *, eta=0.0, noise=None,
+                       use_clipped_model_output=False):
+        """CFG combine + update in one HIP kernel (pipeline_animation_inference_dual.py:791-800).  ``coef_dev``: device
+        float32 coefficients read by the kernel instead of host scalars (graph replay): [3] = (guidance, cx, cv) for the
+        eta = 0 v / epsilon update, [6] = ``step_coefficients`` otherwise.  ``noise``: the variance noise (like ``sample``),
+        used when eta > 0."""
+        u, c, x = pred_uncond.contiguous(), pred_text.contiguous(), sample.contiguous()
+        if not self.uses_step_kernel(eta, use_clipped_model_output):
+            cx, cv = (0.0, 0.0) if coef_dev is not None else self.coefficients(timestep)
+            return kernels.cfg_ddim_update(u, c, x, guidance_scale, cx, cv, coef_dev=coef_dev)
+        if eta > 0 and noise is None:
+            raise ValueError("fused_cfg_step: eta > 0 needs the variance noise")
+        coefs = (0.0,) * 6 if coef_dev is not None else self.step_coefficients(timestep, eta, guidance_scale)
+        return kernels.cfg_ddim_step(u, c, x, noise.to(x.dtype).contiguous() if eta > 0 else None,
+                                     self.kernel_mode(use_clipped_model_output), coefs, coef_dev=coef_dev)

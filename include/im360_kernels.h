@@ -231,6 +231,19 @@ int im360_circular_pad_hw(const void* x, void* y, int64_t N, int64_t H, int64_t 
 int im360_cfg_ddim_update(const void* uncond, const void* cond, const void* x, void* out, int64_t n,
                           float guidance, float cx, float cv, int dtype, void* stream, const void* coef_dev);
 
+/* The full DDIMScheduler.step on the CFG combination m = uncond + guidance * (cond - uncond), per element in fp32:
+ *   mode bits 0-1: prediction type (0 epsilon: x0 = (x - sqrt_b m) / sqrt_a, e = m;  1 v_prediction: x0 = sqrt_a x - sqrt_b m,
+ *   e = sqrt_a m + sqrt_b x;  2 sample: x0 = e = m);  bit 2: clip_sample (x0 clamped to [-1, 1]);  bit 3:
+ *   use_clipped_model_output (e = (x - sqrt_a x0) / sqrt_b);
+ *   out = sqrt_a_prev * x0 + dir * e + sigma * noise, dir = sqrt(1 - a_prev - sigma^2), sigma = eta * sqrt(variance).
+ * noise (optional, same shape and dtype): null means zero noise, refused with sigma > 0 unless coef_dev is given.
+ * coef_dev (optional): device float[6] = (guidance, sqrt_a, sqrt_b, sqrt_a_prev, dir, sigma) overriding the scalars (hipGraph replay).
+ * Replaces: the CFG combine + DDIMScheduler.step with eta > 0, clip_sample or use_clipped_model_output,
+ *   pipeline_animation_inference_dual.py:791-800; diffusers/schedulers/scheduling_ddim.py:251-373. */
+int im360_cfg_ddim_step(const void* uncond, const void* cond, const void* x, const void* noise, void* out, int64_t n,
+                        float guidance, float sqrt_a, float sqrt_b, float sqrt_a_prev, float dir, float sigma, int mode,
+                        int dtype, void* stream, const void* coef_dev);
+
 /* y[r] = LayerNorm(x[r] + pre[r % pre_period]) * gamma + beta + post[(r / post_div) % post_mod] on token rows
  * [rows, C]; pre / post are optional [*, C] tables (the WarpAttn spherical PE added before norm1, the motion
  * module's frame PE added after the norm).

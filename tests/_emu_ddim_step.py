@@ -1,0 +1,44 @@
+"""Torch stand-in of ``kernels.cfg_ddim_step`` (csrc/groupnorm.hip cfg_ddim_step_kernel) for the CPU tier: the same
+per-element formulas in fp32, one rounding to the sample's dtype at the end.  Used together with
+_emu_kernels.patched_kernels(), which covers the other kernels."""
+import contextlib
+
+import torch
+
+
+def cfg_ddim_step(uncond, cond, sample, noise, mode, coefs, coef_dev=None):
+    if coef_dev is not None:
+        coefs = [float(v) for v in coef_dev]
+    g, sa, sb, sap, direction, sigma = coefs
+    if noise is None and coef_dev is None and sigma != 0.0:
+        raise ValueError("cfg_ddim_step: sigma > 0 needs a noise tensor")
+    u, c, x = uncond.float(), cond.float(), sample.float()
+    m = u + g * (c - u)
+    pred = mode & 3
+    if pred == 0:
+        x0, eps = (x - sb * m) / sa, m
+    elif pred == 1:
+        x0, eps = sa * x - sb * m, sa * m + sb * x
+    elif pred == 2:
+        x0, eps = m, m
+    else:
+        raise ValueError(f"cfg_ddim_step: mode {mode} unsupported")
+    if mode & 4:
+        x0 = x0.clamp(-1.0, 1.0)
+    if mode & 8:
+        eps = (x - sa * x0) / sb
+    out = sap * x0 + direction * eps
+    if noise is not None:
+        out = out + sigma * noise.float()
+    return out.to(sample.dtype)
+
+
+@contextlib.contextmanager
+def patched_step_kernel():
+    from imagine360_amd import kernels
+    saved = kernels.cfg_ddim_step
+    kernels.cfg_ddim_step = cfg_ddim_step
+    try:
+        yield
+    finally:
+        kernels.cfg_ddim_step = saved
