@@ -615,10 +615,16 @@ __global__ void cfg_ddim_kernel(const T* __restrict__ uncond, const T* __restric
 //      m = u + g (c - u);  x0 / e from the prediction type (mode bits 0-1: 0 epsilon, 1 v, 2 sample);  x0 clamped to [-1, 1]
 //      (bit 2);  e re-derived from the clamped x0 (bit 3);  out = sa_prev x0 + dir e + sigma z.  sa, sb = sqrt(a_t), sqrt(1 - a_t);
 //      dir = sqrt(1 - a_prev - sigma^2), sigma = eta sqrt(var) come from fp64 host math.  noise == nullptr: z = 0.
-template <typename T>
-__global__ void cfg_ddim_step_kernel(const T* __restrict__ uncond, const T* __restrict__ cond, const T* __restrict__ x,
-                                     const T* __restrict__ noise, T* __restrict__ out, long n8, float g, float sa, float sb,
-                                     float sap, float dir, float sigma, int mode, const float* __restrict__ coef) {
+// The step arithmetic of one element, shared by cfg_ddim_step_kernel and cfg_ddim_step_windows_kernel: m is the guided model output,
+// s the sample, z the variance noise (0 without one); isa = 1 / sa, isb = 1 / sb.
+struct DdimCoefs {
+    float g, sa, sb, sap, dir, sigma, isa, isb;
+    int pred;
+    bool clip, clipped_out;
+};
+
+__device__ __forceinline__ DdimCoefs ddim_coefs(float g, float sa, float sb, float sap, float dir, float sigma, int mode,
+                                                const float* __restrict__ coef) {
     if (coef != nullptr) {          // (guidance, sa, sb, sa_prev, dir, sigma) read on the device: hipGraph replay
         g = coef[0];
         sa = coef[1];
@@ -627,9 +633,38 @@ __global__ void cfg_ddim_step_kernel(const T* __restrict__ uncond, const T* __re
         dir = coef[4];
         sigma = coef[5];
     }
-    const int pred = mode & 3;
-    const bool clip = (mode & 4) != 0, clipped_out = (mode & 8) != 0;
-    const float isa = 1.0f / sa, isb = 1.0f / sb;
+    DdimCoefs k;
+    k.g = g, k.sa = sa, k.sb = sb, k.sap = sap, k.dir = dir, k.sigma = sigma;
+    k.isa = 1.0f / sa, k.isb = 1.0f / sb;
+    k.pred = mode & 3;
+    k.clip = (mode & 4) != 0, k.clipped_out = (mode & 8) != 0;
+    return k;
+}
+
+__device__ __forceinline__ float cfg_combine(float u, float c, float g) { return u + g * (c - u); }
+
+__device__ __forceinline__ float ddim_step_elem(float m, float s, float z, const DdimCoefs& k) {
+    float x0, eps;
+    if (k.pred == 0) {
+        x0 = (s - k.sb * m) * k.isa;
+        eps = m;
+    } else if (k.pred == 1) {
+        x0 = k.sa * s - k.sb * m;
+        eps = k.sa * m + k.sb * s;
+    } else {
+        x0 = m;
+        eps = m;                     // the reference's direction term multiplies the model output, i.e. x0 itself
+    }
+    if (k.clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    if (k.clipped_out) eps = (s - k.sa * x0) * k.isb;
+    return k.sap * x0 + k.dir * eps + k.sigma * z;
+}
+
+template <typename T>
+__global__ void cfg_ddim_step_kernel(const T* __restrict__ uncond, const T* __restrict__ cond, const T* __restrict__ x,
+                                     const T* __restrict__ noise, T* __restrict__ out, long n8, float g, float sa, float sb,
+                                     float sap, float dir, float sigma, int mode, const float* __restrict__ coef) {
+    const DdimCoefs k = ddim_coefs(g, sa, sb, sap, dir, sigma, mode, coef);
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
         float u[8], c[8], s[8], z[8];
         unpack8<T>(((const uint4*)uncond)[i], u);
@@ -641,24 +676,72 @@ __global__ void cfg_ddim_step_kernel(const T* __restrict__ uncond, const T* __re
             for (int e = 0; e < 8; ++e) z[e] = 0.0f;
         }
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float m = u[e] + g * (c[e] - u[e]);
-            float x0, eps;
-            if (pred == 0) {
-                x0 = (s[e] - sb * m) * isa;
-                eps = m;
-            } else if (pred == 1) {
-                x0 = sa * s[e] - sb * m;
-                eps = sa * m + sb * s[e];
-            } else {
-                x0 = m;
-                eps = m;                     // the reference's direction term multiplies the model output, i.e. x0 itself
-            }
-            if (clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-            if (clipped_out) eps = (s[e] - sa * x0) * isb;
-            s[e] = sap * x0 + dir * eps + sigma * z[e];
-        }
+        for (int e = 0; e < 8; ++e) s[e] = ddim_step_elem(cfg_combine(u[e], c[e], k.g), s[e], z[e], k);
         ((uint4*)out)[i] = pack8<T>(s);
+    }
+}
+
+// ---- the same step on the per-frame blend of sliding temporal context windows.  x / noise / out are [outer, F, inner]; the
+//      predictions of all windows sit in one buffer pred[nW, 2, outer, L, inner] (window, CFG half, the model's own layout);
+//      start[nW] ascending window start frames, weight[L] the blend weight of each position inside a window.  Per element at frame f:
+//          m = (sum_k w[f - s_k] (u_k + g (c_k - u_k))) / (sum_k w[f - s_k])   over the windows with s_k <= f < s_k + L, k ascending
+//      (a fixed summation order: deterministic), then ddim_step_elem; one rounding, at the store.  V = 8: 16-byte lanes (inner % 8
+//      == 0, so a lane never straddles a frame); V = 1: the scalar path for any inner.  The first covering window initialises the
+//      sums, so one window with weight 1 gives m = 1 * m_0 / 1 = m_0 exactly: bit-identical to cfg_ddim_step_kernel.
+template <typename T, int V>
+__global__ void cfg_ddim_step_windows_kernel(const T* __restrict__ pred, const T* __restrict__ x, const T* __restrict__ noise,
+                                             T* __restrict__ out, const int* __restrict__ start, const float* __restrict__ weight,
+                                             int nW, long outer, int F, int L, long inner, float g, float sa, float sb, float sap,
+                                             float dir, float sigma, int mode, const float* __restrict__ coef) {
+    const DdimCoefs k = ddim_coefs(g, sa, sb, sap, dir, sigma, mode, coef);
+    const long nv = outer * F * inner / V;
+    const long half = outer * L * inner;              // one CFG half of one window
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
+        const long e0 = i * V;
+        const long r = e0 % inner, of = e0 / inner;
+        const int f = (int)(of % F);
+        const long o = of / F;
+        float acc[V], s[V], z[V];
+#pragma unroll
+        for (int e = 0; e < V; ++e) acc[e] = 0.0f;
+        float wsum = 0.0f;
+        bool first = true;
+        for (int w = 0; w < nW; ++w) {
+            const int j = f - start[w];
+            if (j < 0 || j >= L) continue;
+            const float wt = weight[j];
+            const long at = (long)w * 2 * half + (o * L + j) * inner + r;
+            float u[V], c[V];
+            if (V == 8) {
+                unpack8<T>(*(const uint4*)(pred + at), u);
+                unpack8<T>(*(const uint4*)(pred + at + half), c);
+            } else {
+                u[0] = to_f32<T>(pred[at]);
+                c[0] = to_f32<T>(pred[at + half]);
+            }
+#pragma unroll
+            for (int e = 0; e < V; ++e) {
+                const float m = wt * cfg_combine(u[e], c[e], k.g);
+                acc[e] = first ? m : acc[e] + m;
+            }
+            wsum = first ? wt : wsum + wt;
+            first = false;
+        }
+        if (V == 8) {
+            unpack8<T>(((const uint4*)x)[i], s);
+            if (noise != nullptr) unpack8<T>(((const uint4*)noise)[i], z);
+        } else {
+            s[0] = to_f32<T>(x[i]);
+            if (noise != nullptr) z[0] = to_f32<T>(noise[i]);
+        }
+        if (noise == nullptr) {
+#pragma unroll
+            for (int e = 0; e < V; ++e) z[e] = 0.0f;
+        }
+#pragma unroll
+        for (int e = 0; e < V; ++e) s[e] = ddim_step_elem(acc[e] / wsum, s[e], z[e], k);
+        if (V == 8) ((uint4*)out)[i] = pack8<T>(s);
+        else out[i] = from_f32<T>(s[0]);
     }
 }
 
@@ -1030,6 +1113,42 @@ extern "C" __attribute__((visibility("default"))) int im360_cfg_ddim_step(const 
         return IM360_ERR_UNSUPPORTED;
     }
 #undef IM360_DDIM_STEP
+    IM360_CHECK_LAUNCH();
+    return IM360_OK;
+}
+
+// The step of im360_cfg_ddim_step on the per-frame weighted blend of nW sliding-window predictions (see the kernel's comment):
+// x / noise / out [outer, F, inner], pred [nW, 2, outer, L, inner], start int32[nW] and weight float[L] on the device.  The host
+// cannot see the tables: the caller guarantees 0 <= start[k] <= F - L and that every frame is covered (imagine360_amd/context.py).
+extern "C" __attribute__((visibility("default"))) int im360_cfg_ddim_step_windows(const void* pred, const void* x, const void* noise, void* out,
+                                   const void* start, const void* weight, int nW, int64_t outer, int64_t F, int64_t L,
+                                   int64_t inner, float guidance, float sqrt_a, float sqrt_b, float sqrt_a_prev, float dir,
+                                   float sigma, int mode, int dtype, void* stream, const void* coef_dev) {
+    using namespace im360;
+    IM360_CHECK_ARG(pred && x && out && start && weight, "cfg_ddim_step_windows: null pointer");
+    IM360_CHECK_ARG(nW > 0 && outer > 0 && inner > 0 && L > 0 && L <= F && F < (1 << 30),
+                    "cfg_ddim_step_windows: nW=%d outer=%ld F=%ld L=%ld inner=%ld out of range", nW, (long)outer, (long)F, (long)L, (long)inner);
+    IM360_CHECK_ARG(mode >= 0 && mode < 16 && (mode & 3) != 3, "cfg_ddim_step_windows: mode %d unsupported", mode);
+    IM360_CHECK_ARG(noise || coef_dev || sigma == 0.0f, "cfg_ddim_step_windows: sigma=%g needs a noise tensor", (double)sigma);
+    IM360_CHECK_ARG(((uintptr_t)start % 4) == 0 && ((uintptr_t)weight % 4) == 0, "cfg_ddim_step_windows: misaligned table");
+    const bool vec = (inner % 8) == 0 && ((uintptr_t)pred % 16) == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)noise % 16) == 0 &&
+                     ((uintptr_t)out % 16) == 0;
+    const long nv = (long)(outer * F * inner) / (vec ? 8 : 1);
+    const unsigned blocks = (unsigned)((nv + 255) / 256 > 4096 ? 4096 : (nv + 255) / 256);
+    hipStream_t s = (hipStream_t)stream;
+#define IM360_DDIM_WIN(T, V)                                                                                              \
+    hipLaunchKernelGGL((cfg_ddim_step_windows_kernel<T, V>), dim3(blocks), dim3(256), 0, s, (const T*)pred, (const T*)x,     \
+                       (const T*)noise, (T*)out, (const int*)start, (const float*)weight, nW, (long)outer, (int)F, (int)L,   \
+                       (long)inner, guidance, sqrt_a, sqrt_b, sqrt_a_prev, dir, sigma, mode, (const float*)coef_dev)
+    if (dtype == 0 && vec) IM360_DDIM_WIN(__bf16, 8);
+    else if (dtype == 0) IM360_DDIM_WIN(__bf16, 1);
+    else if (dtype == 1 && vec) IM360_DDIM_WIN(_Float16, 8);
+    else if (dtype == 1) IM360_DDIM_WIN(_Float16, 1);
+    else {
+        im360_set_error("cfg_ddim_step_windows: dtype %d unsupported", dtype);
+        return IM360_ERR_UNSUPPORTED;
+    }
+#undef IM360_DDIM_WIN
     IM360_CHECK_LAUNCH();
     return IM360_OK;
 }

@@ -37,6 +37,8 @@ class _PinnedUploads:
 
 
 class GraphedDenoiseStep:
+    always_step_kernel = False      # (GraphedWindowedStep) the six-coefficient step kernel for eta = 0 as well
+
     def __init__(self, mv, scheduler, inputs, cameras, pano_latent, pers_latent, guidance, use_fps=True, warmup=2, cfg_pair=None,
                  eta=0.0, generator=None, use_clipped_model_output=False, frame_shard=None):
         """``inputs``: the keyword tensors of MultiViewBaseModel.forward (CFG-batched, resident on the GPU);
@@ -51,7 +53,7 @@ class GraphedDenoiseStep:
         self.mv, self.sch, self.inp, self.cams, self.g = mv, scheduler, inputs, cameras, float(guidance)
         self.cfg_pair = cfg_pair
         self.eta, self.gen, self.clipped, self.shard = float(eta), generator, bool(use_clipped_model_output), frame_shard
-        self.step_kernel = scheduler.uses_step_kernel(self.eta, self.clipped)
+        self.step_kernel = self.always_step_kernel or scheduler.uses_step_kernel(self.eta, self.clipped)
         dev = pano_latent.device
         # private copies: the caller's tensors may alias the model-input buffers the body writes into
         init_pano, init_pers = pano_latent.clone(), pers_latent.clone()
@@ -155,3 +157,48 @@ class GraphedDenoiseStep:
         self._upload(t_host)
         self.graph.replay()
         return self.pano_lat, self.pers_lat
+
+
+class GraphedWindowedStep(GraphedDenoiseStep):
+    """One denoising step over sliding temporal context windows (imagine360_amd.context) in ONE hipGraph: the forwards of all
+    windows in ascending order, each reading its frames of the full-length model-input buffers and its own cached conditioning
+    and writing its prediction into slot k of the [nW, 2, ...] buffers, then the blend + CFG + DDIM kernel of each branch.
+    Captured: the nW forwards with their IP-adapter noise draws, (eta > 0) the two whole-clip variance noises, both updates.
+    Not captured, per step on the host: three small pinned uploads -- the timestep, the six coefficients, the [nW, 8] table of
+    WarpAttn coins drawn from Python's RNG in window order -- and replay(); no synchronisation.  Building it consumes no
+    randomness (GraphedDenoiseStep.__init__).  The caller keeps ``context.ip_cache_slots(mv, len(plan))`` open while this is
+    built, so that every window's IP tokens exist before the capture."""
+    always_step_kernel = True
+
+    def __init__(self, mv, scheduler, inputs, cameras, pano_latent, pers_latent, guidance, plan, use_fps=True, warmup=1, eta=0.0,
+                 generator=None, use_clipped_model_output=False):
+        dev = pano_latent.device
+        self.plan = plan
+        self.static = plan.static_inputs(inputs)
+        self.preds_pers, self.preds_pano = plan.pred_buffers(pano_latent, pers_latent)
+        self.coins = torch.zeros(len(plan), 8, dtype=torch.int32, device=dev)
+        self._up_k = _PinnedUploads(self.coins)
+        super().__init__(mv, scheduler, inputs, cameras, pano_latent, pers_latent, guidance, use_fps=use_fps, warmup=warmup, eta=eta,
+                         generator=generator, use_clipped_model_output=use_clipped_model_output)
+
+    def _body(self):
+        inp = self.inp
+        inp["pano_latent"][:, :4] = self.pano_lat
+        inp["latents"][:, :, :4] = self.pers_lat
+        self.plan.forward(self.mv, inp, self.static, self.cams, self.timestep, self.use_fps, self.preds_pers, self.preds_pano,
+                          coins=self.coins)
+        mdt = self.mv.unet.dtype
+        kw = dict(coef_dev=self.coef, eta=self.eta, use_clipped_model_output=self.clipped)
+        new_pano = self.sch.fused_cfg_step_windows(self.preds_pano, self.plan.starts_dev, self.plan.weights, self.g, None,
+                                                   self.pano_lat, noise=self._noise(self.pano_lat, mdt, 2), **kw)
+        new_pers = self.sch.fused_cfg_step_windows(self.preds_pers, self.plan.starts_dev, self.plan.weights, self.g, None,
+                                                   self.pers_lat, noise=self._noise(self.pers_lat, mdt, 3), **kw)
+        self.pano_lat.copy_(new_pano)
+        self.pers_lat.copy_(new_pers)
+
+    def _upload(self, t_host, draw=True):
+        self._up_t.upload(self.timestep, [int(t_host)])
+        self._up_c.upload(self.coef, list(self.sch.step_coefficients(t_host, self.eta, self.g)))
+        if draw:
+            # the coins of nW successive forwards: 7 per window in execution order (MultiViewBaseModel.draw_coins)
+            self._up_k.upload(self.coins, [[1 if random.random() < 0.4 else 0 for _ in range(7)] + [0] for _ in range(len(self.plan))])

@@ -5,6 +5,7 @@ There is NO fallback: a missing library or a non-GPU tensor raises.  Model code 
 through the module (``kernels.attention(...)``).
 """
 import ctypes
+import math
 import os
 
 import torch
@@ -51,6 +52,7 @@ _SIGNATURES = {
     "im360_circular_pad_hw": (_INT, [_PTR] * 2 + [_I64] * 8 + [_PTR]),
     "im360_cfg_ddim_update": (_INT, [_PTR] * 4 + [_I64] + [_F32] * 3 + [_INT, _PTR, _PTR]),
     "im360_cfg_ddim_step": (_INT, [_PTR] * 5 + [_I64] + [_F32] * 6 + [_INT, _INT, _PTR, _PTR]),
+    "im360_cfg_ddim_step_windows": (_INT, [_PTR] * 6 + [_INT] + [_I64] * 4 + [_F32] * 6 + [_INT, _INT, _PTR, _PTR]),
     "im360_layernorm": (_INT, [_PTR] * 6 + [_I64] * 5 + [_F32, _INT, _PTR]),
     "im360_geglu": (_INT, [_PTR] * 2 + [_I64] * 2 + [_INT, _PTR]),
     "im360_linear_geglu": (_INT, [_PTR] * 4 + [_I64] * 3 + [_INT, _PTR]),
@@ -863,6 +865,34 @@ def cfg_ddim_step(uncond, cond, sample, noise, mode, coefs, coef_dev=None):
     rc = lib().im360_cfg_ddim_step(_p(uncond), _p(cond), _p(sample), _p(noise), _p(out), sample.numel(),
                                    *(float(v) for v in coefs), int(mode), _dt(sample), _stream(), _p(coef_dev))
     _check(rc, "im360_cfg_ddim_step")
+    return out
+
+
+def cfg_ddim_step_windows(preds, sample, noise, starts, weights, mode, coefs, coef_dev=None):
+    """``cfg_ddim_step`` on the per-frame weighted blend of sliding-window predictions, one pass.  ``sample`` (and ``noise`` /
+    the result): a panorama latent [1, 4, F, H, W] or a perspective latent [1, m, 4, F, h, w];  ``preds`` [nW, 2, *sample.shape
+    with F -> L]: window k's CFG-batched prediction in slot k;  ``starts`` device int32 [nW] ascending window start frames
+    (context.context_windows);  ``weights`` device float32 [L] (context.context_weights).  ``mode`` / ``coefs`` / ``coef_dev`` as in
+    ``cfg_ddim_step``."""
+    _dev(preds, sample, noise, starts, weights)
+    assert preds.is_contiguous() and sample.is_contiguous() and preds.dtype == sample.dtype
+    assert sample.dim() in (5, 6) and sample.shape[0] == 1, "sample must be [1, 4, F, H, W] or [1, m, 4, F, h, w]"
+    fd = sample.dim() - 3
+    outer, F, inner = math.prod(sample.shape[:fd]), sample.shape[fd], math.prod(sample.shape[fd + 1:])
+    nW, L = preds.shape[0], preds.shape[fd + 1]
+    assert tuple(preds.shape) == (nW, 2, *sample.shape[1:fd], L, *sample.shape[fd + 1:]), (tuple(preds.shape), tuple(sample.shape))
+    assert starts.dtype == torch.int32 and starts.is_contiguous() and starts.numel() == nW
+    assert weights.dtype == torch.float32 and weights.is_contiguous() and weights.numel() == L and 1 <= L <= F
+    if noise is not None:
+        assert noise.is_contiguous() and noise.shape == sample.shape and noise.dtype == sample.dtype
+    elif coef_dev is None and coefs[5] != 0.0:
+        raise ValueError("cfg_ddim_step_windows: sigma > 0 needs a noise tensor")
+    if coef_dev is not None:
+        assert coef_dev.dtype == torch.float32 and coef_dev.numel() == 6 and coef_dev.is_cuda
+    out = torch.empty_like(sample)
+    rc = lib().im360_cfg_ddim_step_windows(_p(preds), _p(sample), _p(noise), _p(out), _p(starts), _p(weights), nW, outer, F, L,
+                                           inner, *(float(v) for v in coefs), int(mode), _dt(sample), _stream(), _p(coef_dev))
+    _check(rc, "im360_cfg_ddim_step_windows")
     return out
 
 

@@ -10,7 +10,9 @@ surface, rebuilt for the MI355X:
     the CPU generator in the reference's order, so results are comparable to the reference's CPU path
     on the same seeds; ``rng="device"`` (default) draws on the GPU like the reference's GPU path;
   * stochastic DDIM (``eta > 0``): per step, after the model's IP-adapter noise, the panorama then the perspective variance
-    noise is drawn (from ``generator`` when given), exactly where the reference's ``scheduler.step`` draws it.
+    noise is drawn (from ``generator`` when given), exactly where the reference's ``scheduler.step`` draws it;
+  * long clips (``context_frames=L``): sliding temporal context windows -- one forward of the unmodified model per window
+    of L frames, the windows' predictions blended per frame inside the CFG + DDIM kernel (imagine360_amd/context.py).
 
 CLIP text encoding and SAM feature extraction are outside the hot path: the
 pipeline uses ``text_encoder``/``tokenizer``/``image_encoder`` when given, and also accepts precomputed
@@ -214,13 +216,24 @@ class AnimationPipeline:
                  output_type="tensor", return_dict=True, callback=None, callback_steps=1, latents_dtype=torch.float16,
                  video_batch=None, use_outpaint=False, use_ip_plus_cross_attention=False, use_fps_condition=False,
                  ip_plus_condition="image", prompt_embeds=None, sam_features=None, trace=None, frame_shard=None,
-                 **kwargs):
+                 context_frames=None, context_overlap=4, context_weights="pyramid", **kwargs):
         """``frame_shard`` (imagine360_amd.dist.FrameShard): this rank denoises a contiguous chunk of the frames (BASELINE
         configs 4 / 5); all ranks must be called with the same seeds and inputs.  Noise is drawn for the whole clip and
         cut, the VAE encodes / the loop runs / the VAE decodes only the local frames, the motion modules exchange tokens
-        with one all-to-all each way, and the decoded frames are all-gathered at the end (the only other collective)."""
+        with one all-to-all each way, and the decoded frames are all-gathered at the end (the only other collective).
+        ``context_frames`` (None: off): sliding temporal context windows (imagine360_amd.context) -- per step the model runs on
+        overlapping windows of ``context_frames`` frames (the motion modules' trained length; frame positions 0 .. L-1 inside
+        every window, which lifts the temporal_position_encoding_max_len ceiling), ``context_overlap`` frames shared between
+        neighbours, and the windows' predictions are blended per frame with ``context_weights`` ("pyramid" / "uniform") inside
+        the CFG + DDIM kernel.  ``context_frames >= video_length`` is the call without it."""
         device = self.device
         vb = video_batch
+        plan = None
+        if context_frames is not None and int(context_frames) < vb["video_length"]:
+            if frame_shard is not None:
+                raise ValueError("context_frames cannot be combined with frame_shard (windows under frame sharding are not implemented)")
+            from .context import WindowPlan
+            plan = WindowPlan(vb["video_length"], context_frames, context_overlap, context_weights, device)
         assert use_outpaint and use_ip_plus_cross_attention, "the dual pipeline runs with use_outpaint and the IP adapter"
         cfg = guidance_scale_text > 1.0
         assert cfg, "the reference only binds its model inputs under classifier-free guidance (:744-751)"
@@ -273,10 +286,18 @@ class AnimationPipeline:
             in_pano = torch.cat([torch.cat((pano_latent, pano_mask_l.to(dt), pano_ml.to(dt)), dim=1)] * 2)
             in_pers = torch.cat([torch.cat((pers_latent, pers_mask_l.to(dt), pers_ml.to(dt)), dim=2)] * 2)
 
+            if plan is not None:
+                inputs = dict(latents=in_pers, pano_latent=in_pano, prompt_embd=text_pers, pano_prompt_embd=text_pano,
+                              fps_tensor_pano=fps_pano, fps_tensor_pers=fps_pers, reference_images_clip_feat_pano=feat_pano,
+                              reference_images_clip_feat_pers=feat_pers, relative_position_tensor=rel, pitchs_tensor=pitch)
+                pano_latent, pers_latent = self._windowed_loop(plan, inputs, cameras, pano_latent, pers_latent, steps_host, ts_dev,
+                                                               guidance_scale_text, use_fps_condition, eta, generator, trace,
+                                                               callback, callback_steps)
             graphed = None
             import torch.distributed as tdist
             capturable = sh is None or (tdist.is_initialized() and tdist.get_backend(sh.group) == "nccl")     # RCCL all-to-alls are stream ops
-            if self.use_graph and self.rng == "device" and pano_latent.is_cuda and trace is None and callback is None and capturable:
+            if (plan is None and self.use_graph and self.rng == "device" and pano_latent.is_cuda and trace is None and callback is None
+                    and capturable):
                 from .graph_step import GraphedDenoiseStep
                 inputs = dict(latents=in_pers, pano_latent=in_pano, prompt_embd=text_pers, pano_prompt_embd=text_pano,
                               fps_tensor_pano=fps_pano, fps_tensor_pers=fps_pers, reference_images_clip_feat_pano=feat_pano,
@@ -284,7 +305,7 @@ class AnimationPipeline:
                 stoch = dict(eta=eta, generator=generator, frame_shard=sh) if eta > 0 else {}
                 graphed = GraphedDenoiseStep(self.mv_base_model, self.scheduler, inputs, cameras, pano_latent, pers_latent,
                                              guidance_scale_text, use_fps=use_fps_condition, warmup=1, **stoch)       # one eager step fills every cache
-            for i, t in enumerate(self.progress_bar(steps_host)):
+            for i, t in enumerate(self.progress_bar(steps_host) if plan is None else ()):
                 if graphed is not None:
                     pano_latent, pers_latent = graphed.step(t)
                     continue
@@ -324,3 +345,37 @@ class AnimationPipeline:
             z = variance_noise(self.scheduler, latent, pred.dtype, generator, self.rng, shard, frame_dim)
             return self.scheduler.fused_cfg_step(u, c, g, t, latent, eta=eta, noise=z)
         return self.scheduler.fused_cfg_step(u, c, g, t, latent)
+
+    def _windowed_loop(self, plan, inputs, cameras, pano_latent, pers_latent, steps_host, ts_dev, g, use_fps, eta, generator,
+                       trace, callback, callback_steps):
+        """The denoising loop over sliding temporal context windows: per step one forward per window (ascending), then ONE
+        blend + CFG + DDIM kernel per branch, panorama first.  RNG: as len(plan) successive calls of the model, then (eta > 0)
+        the whole clip's panorama and perspective variance noise.  Captured in one hipGraph under the conditions of the
+        one-block loop (graph_step.GraphedWindowedStep), issued eagerly otherwise."""
+        from .context import ip_cache_slots
+        mv, sch = self.mv_base_model, self.scheduler
+        with ip_cache_slots(mv, len(plan)):
+            if self.use_graph and self.rng == "device" and pano_latent.is_cuda and trace is None and callback is None:
+                from .graph_step import GraphedWindowedStep
+                graphed = GraphedWindowedStep(mv, sch, inputs, cameras, pano_latent, pers_latent, g, plan, use_fps=use_fps, warmup=1,
+                                              eta=eta, generator=generator)
+                for t in self.progress_bar(steps_host):
+                    pano_latent, pers_latent = graphed.step(t)
+                return pano_latent, pers_latent
+            static = plan.static_inputs(inputs)
+            preds_pers, preds_pano = plan.pred_buffers(pano_latent, pers_latent)
+            for i, t in enumerate(self.progress_bar(steps_host)):
+                inputs["pano_latent"][:, :4] = pano_latent
+                inputs["latents"][:, :, :4] = pers_latent
+                plan.forward(mv, inputs, static, cameras, ts_dev[i], use_fps, preds_pers, preds_pano)
+                mdt = mv.unet.dtype
+                kw = dict(eta=eta)
+                z = variance_noise(sch, pano_latent, mdt, generator, self.rng) if eta > 0 else None
+                pano_latent = sch.fused_cfg_step_windows(preds_pano, plan.starts_dev, plan.weights, g, t, pano_latent, noise=z, **kw)
+                z = variance_noise(sch, pers_latent, mdt, generator, self.rng, frame_dim=3) if eta > 0 else None
+                pers_latent = sch.fused_cfg_step_windows(preds_pers, plan.starts_dev, plan.weights, g, t, pers_latent, noise=z, **kw)
+                if trace is not None:
+                    trace.append(pano_latent.clone())
+                if callback is not None and i % callback_steps == 0:
+                    callback(i, t, pano_latent)
+        return pano_latent, pers_latent

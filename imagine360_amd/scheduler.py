@@ -200,3 +200,17 @@ class DDIMScheduler:
         coefs = (0.0,) * 6 if coef_dev is not None else self.step_coefficients(timestep, eta, guidance_scale)
         return kernels.cfg_ddim_step(u, c, x, noise.to(x.dtype).contiguous() if eta > 0 else None,
                                      self.kernel_mode(use_clipped_model_output), coefs, coef_dev=coef_dev)
+
+    def fused_cfg_step_windows(self, preds, starts, weights, guidance_scale, timestep, sample, coef_dev=None, *, eta=0.0,
+                               noise=None, use_clipped_model_output=False):
+        """``fused_cfg_step`` over sliding temporal context windows: the per-frame weighted blend of the windows' CFG-combined
+        predictions + the update, one HIP kernel (``kernels.cfg_ddim_step_windows``).  ``preds`` [nW, 2, ...]: window k's
+        CFG-batched prediction in slot k, in ``sample``'s layout with L frames;  ``starts`` device int32 [nW], ``weights`` device
+        float32 [L] (imagine360_amd.context).  The step kernel serves eta = 0 as well, so ``coef_dev`` is always float32[6] =
+        ``step_coefficients``."""
+        if eta > 0 and noise is None:
+            raise ValueError("fused_cfg_step_windows: eta > 0 needs the variance noise")
+        x = sample.contiguous()
+        coefs = (0.0,) * 6 if coef_dev is not None else self.step_coefficients(timestep, eta, guidance_scale)
+        return kernels.cfg_ddim_step_windows(preds.contiguous(), x, noise.to(x.dtype).contiguous() if eta > 0 else None, starts,
+                                             weights, self.kernel_mode(use_clipped_model_output), coefs, coef_dev=coef_dev)

@@ -244,6 +244,23 @@ int im360_cfg_ddim_step(const void* uncond, const void* cond, const void* x, con
                         float guidance, float sqrt_a, float sqrt_b, float sqrt_a_prev, float dir, float sigma, int mode,
                         int dtype, void* stream, const void* coef_dev);
 
+/* im360_cfg_ddim_step on the per-frame blend of sliding temporal context windows (imagine360_amd/context.py).  x / noise / out
+ * are viewed as [outer, F, inner] (panorama latent [1,4,F,H,W]: outer 4, inner H*W; perspective latent [1,m,4,F,h,w]: outer 4m,
+ * inner h*w).  pred holds the predictions of all nW windows in one buffer [nW, 2, outer, L, inner] (window, CFG half: uncond then
+ * cond, then the model's own layout), same 16-bit dtype.  start: device int32[nW], ascending window start frames, 0 <= start[k]
+ * <= F - L, every frame covered;  weight: device float[L], positive.  Per element at frame f, in fp32,
+ *   m = (sum_k weight[f - start[k]] * (u_k + guidance * (c_k - u_k))) / (sum_k weight[f - start[k]])
+ * over the windows with start[k] <= f < start[k] + L, k ascending (fixed order: deterministic), then the step of
+ * im360_cfg_ddim_step on m (same mode word, same six coefficients, same optional coef_dev[6]); one rounding, at the store.
+ * 16-byte lanes when inner % 8 == 0 and the tensors are 16-byte aligned, a scalar path otherwise.  nW = 1, start = {0}, weight
+ * all 1, L = F gives im360_cfg_ddim_step's result bit for bit.
+ * Replaces: nothing in the reference (it has no temporal windows); composes the CFG combine + DDIMScheduler.step of
+ *   pipeline_animation_inference_dual.py:771-800 over several forwards. */
+int im360_cfg_ddim_step_windows(const void* pred, const void* x, const void* noise, void* out, const void* start,
+                                const void* weight, int nW, int64_t outer, int64_t F, int64_t L, int64_t inner, float guidance,
+                                float sqrt_a, float sqrt_b, float sqrt_a_prev, float dir, float sigma, int mode, int dtype,
+                                void* stream, const void* coef_dev);
+
 /* y[r] = LayerNorm(x[r] + pre[r % pre_period]) * gamma + beta + post[(r / post_div) % post_mod] on token rows
  * [rows, C]; pre / post are optional [*, C] tables (the WarpAttn spherical PE added before norm1, the motion
  * module's frame PE added after the norm).

@@ -1,0 +1,126 @@
+#!/usr/bin/env python
+"""Sliding temporal context windows at BASELINE cfg4 size (48 frames, full width, CFG batch 2): one windowed denoising step
+(L = 16, overlap 4 -> 4 windows, one captured hipGraph: graph_step.GraphedWindowedStep) next to the 48-frame full-attention step
+(graph_step.GraphedDenoiseStep), replays alternated round by round, timed with a host clock around work that ends in a device
+synchronise; and the blend + CFG + DDIM kernel alone next to cfg_ddim_step_kernel on the same perspective latent, timed with
+device events, with the bytes each has to move computed from the shapes.  Prints one line of JSON (and writes it to --out).
+    python tools/bench_context.py [--steps 3] [--rounds 3] [--kernel-iters 200] [--out profiles/context_windows.json]
+    python tools/bench_context.py --kernel-only       # skip the two whole steps"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from imagine360_amd import configs, kernels, synthetic  # noqa: E402
+from imagine360_amd.context import WindowPlan, coverage, ip_cache_slots  # noqa: E402
+from imagine360_amd.scheduler import DDIMScheduler  # noqa: E402
+
+FRAMES, LENGTH, OVERLAP = 48, 16, 4
+PANO_HW, PERS_HW, PERS_PX = (64, 128), (32, 32), 256
+
+
+def kernel_bytes(sample, plan):
+    """Bytes the two kernels have to move for ``sample`` (no variance noise): the windowed one reads both CFG halves of every
+    window once (2 x sum of coverage) + the sample and writes one latent; the plain one reads uncond, cond, sample and writes one."""
+    per_frame = sample.numel() // plan.frames * sample.element_size()
+    cov = sum(coverage(plan.frames, plan.length, plan.starts))
+    return dict(windows=(2 * cov + 2 * plan.frames) * per_frame, plain=4 * plan.frames * per_frame)
+
+
+def time_kernels(sch, plan, sample, iters, rounds=5):
+    """Device-event time of the two kernels on ``sample`` (alternated round by round, ``iters`` back-to-back launches each)."""
+    t = sch._timesteps_host[8]
+    coefs = sch.step_coefficients(t, 0.0, 7.5)
+    mode = sch.kernel_mode()
+    fd = sample.dim() - 3
+    shape = list(sample.shape)
+    shape[fd] = plan.length
+    preds = torch.randn(len(plan), 2, *shape[1:], device=sample.device).to(sample.dtype)
+    u, c = (torch.randn(sample.shape, device=sample.device).to(sample.dtype) for _ in range(2))
+    fns = dict(windows=lambda: kernels.cfg_ddim_step_windows(preds, sample, None, plan.starts_dev, plan.weights, mode, coefs),
+               plain=lambda: kernels.cfg_ddim_step(u, c, sample, None, mode, coefs))
+    times = {k: [] for k in fns}
+    for r in range(rounds + 1):
+        for name, fn in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            a.record()
+            for _ in range(iters):
+                fn()
+            b.record()
+            torch.cuda.synchronize()
+            if r:                                   # round 0 warms both up
+                times[name].append(a.elapsed_time(b) / iters * 1e3)
+    return {k: dict(us_min=min(v), us_median=statistics.median(v)) for k, v in times.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--kernel-iters", type=int, default=200)
+    ap.add_argument("--kernel-only", action="store_true")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "bench_context.py measures on the MI355X; there is nothing to time without one"
+    torch.set_grad_enabled(False)
+    kernels.lib()
+    dev, dt = torch.device("cuda", 0), torch.bfloat16
+    sch = DDIMScheduler(**configs.NOISE_SCHEDULER_KWARGS)
+    sch.set_timesteps(25)
+    ts_host = [int(t) for t in sch._timesteps_host]
+    plan = WindowPlan(FRAMES, LENGTH, OVERLAP, "pyramid", dev)
+    res = dict(tool="bench_context", frames=FRAMES, context_frames=LENGTH, context_overlap=OVERLAP, windows=plan.starts,
+               pano_hw=PANO_HW, pers_hw=PERS_HW, dtype="bfloat16", device=torch.cuda.get_device_name(0))
+
+    pers = torch.randn(1, 20, 4, FRAMES, *PERS_HW, device=dev).to(dt)
+    nbytes = kernel_bytes(pers, plan)
+    kt = time_kernels(sch, plan, pers, args.kernel_iters)
+    res["blend_kernel"] = {k: dict(**kt[k], bytes=nbytes[k], gb_per_s=nbytes[k] / (kt[k]["us_min"] * 1e-6) / 1e9) for k in kt}
+    res["blend_kernel"]["tensor"] = list(pers.shape)
+    res["blend_kernel"]["note"] = "event time over back-to-back launches; the working set fits the 256 MB Infinity Cache, so GB/s is an effective rate"
+
+    if not args.kernel_only:
+        mv = configs.build_mv_model(1, device=dev, dtype=dt, xformers=True)
+        mv.dual_stream, mv.warp_streams = True, True
+        inp = synthetic.mv_inputs(frames=FRAMES, pano_hw=PANO_HW, pers_hw=PERS_HW, seed=1, dtype=dt, device=dev)
+        inp.pop("timestep")
+        cams = synthetic.icosahedron_cameras(90, PERS_PX, device=dev)
+        pano_lat, pers_lat = inp["pano_latent"][:1, :4].contiguous(), inp["latents"][:1, :, :4].contiguous()
+        from imagine360_amd.graph_step import GraphedDenoiseStep, GraphedWindowedStep
+        with ip_cache_slots(mv, len(plan)):
+            windowed = GraphedWindowedStep(mv, sch, inp, cams, pano_lat, pers_lat, 7.5, plan, warmup=1)
+        torch.cuda.synchronize()
+        print("captured: windowed step", file=sys.stderr, flush=True)
+        full = GraphedDenoiseStep(mv, sch, inp, cams, pano_lat, pers_lat, 7.5, warmup=1)
+        torch.cuda.synchronize()
+        print("captured: 48-frame full-attention step", file=sys.stderr, flush=True)
+        graphs = dict(windowed_step=windowed, full_attention_step=full)
+        times = {k: [] for k in graphs}
+        for r in range(args.rounds + 1):
+            for name, gs in graphs.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for i in range(args.steps):
+                    gs.step(ts_host[i % len(ts_host)])
+                torch.cuda.synchronize()
+                if r:                               # round 0 warms every graph up
+                    times[name].append((time.perf_counter() - t0) / args.steps * 1e3)
+        for name, v in times.items():
+            res[name] = dict(ms_min=min(v), ms_median=statistics.median(v), rounds=len(v), steps_per_round=args.steps)
+        res["finite"] = bool(torch.isfinite(windowed.pano_lat.float()).all() and torch.isfinite(windowed.pers_lat.float()).all())
+    line = json.dumps(res)
+    print(line, flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            fh.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
