@@ -1731,7 +1731,8 @@ static int launch_conv_t(ConvParams p, hipStream_t stream) {
         return IM360_ERR_UNSUPPORTED;
     }
     if (cm) {
-        if constexpr (has_cm)
+        // (the 256 x 320 tile returned above with its per-residual-mode kernels: no RESM 0 instantiation of it for nothing to launch)
+        if constexpr (has_cm && !(WM == 4 && WN == 2 && TM == 2 && TN == 5 && EPI == 0))
             hipLaunchKernelGGL((conv_igemm_kernel<T, 64, WM, WN, TM, TN, EPI, true>), dim3((unsigned)p.nblocks), dim3(NT), 0, stream, p);
     } else if ((p.Cin % 64 == 0 && bk_env != 32 && !(WM == 2 && TN >= 4 && TM == 2) && !(WM == 4 && WN == 1 && knob(KNOB_CONV_SMALL) == 0)) || !has_bk32) {      // (the 128 x 320 / 128 x 256 tiles exist for two workgroups per CU: 32-channel stages)
         hipLaunchKernelGGL((conv_igemm_kernel<T, 64, WM, WN, TM, TN, EPI>), dim3(grid_cm), dim3(NT), 0, stream, p);

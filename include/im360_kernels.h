@@ -348,8 +348,15 @@ int im360_max_rect(const uint8_t* mask, int64_t H, int64_t W, int64_t* rect);
  * workgroup on four (batch, head) pairs over the same query rows, measured slower, default 0; 16 tiles of
  * convolutions with Cout % 128 in (0, 64] on small grids: 2 (default) 128 x 128, 0 / 1 256 x 64 with 32- / 64-channel K steps; 17 d = 64 attention without a bias on four-wave grids: 1 (default)
  * one query block per wave at three waves per SIMD, 0 the round-2 rule (two blocks per wave on large grids)).  Defaults are the measured best; the IM360_* environment variables seed them at load time.  Knobs 7 and 8
- * change the fp32 summation order, 11 (0 against 1 - 3: the scale is folded into K instead of Q) and 12 the 16-bit rounding points, 6 and 14
- * break results on purpose, the others do not change results. */
+ * change the fp32 summation order, and so do 2 (= 32) and 16 (= 0 / 1) for 3x3 convolutions that the default runs taps-innermost: the 32-channel and
+ * the 256 x 64 kernels are tap-major, i.e. they give the bits of knob 8 = 0.  11 (0 against 1 - 3: the scale is folded into K instead of Q) and 12 move
+ * the 16-bit rounding points; 0 and 17 (= 0, on large grids) switch between one and two query blocks per wave, which rescale the running sums at
+ * different points; 9 reduces a row over other lane groups (last bits); 24 (register-staged four-wave GEMM tiles: bit 0 / 2 GEGLU projection on
+ * the 256 x 256 / 256 x 128 tile, bit 1 / 3 the same with LayerNorm folded in; also knob 4 = 12 / 13) is bit-identical for the plain GEGLU epilogue
+ * and differs in last bits for the LayerNorm-folded one (same summation order; hipcc contracts the fp32 `(acc - mu c1) rstd + c2` differently in the
+ * two kernels).  6 and 14 break results on purpose.  The others -- 1, 2 / 16 where the K order is kept, 10, 13, 17 on small grids, 22 (temporal
+ * attention load / store forms), 23 (non-temporal epilogue stores), 25 (GroupNorm apply workgroups) -- do not change a bit
+ * (tests/test_kernel_variants_gpu.py). */
 int im360_tuning_set(int knob, int value);
 
 /* ---- diagnostics: the ONLY process-global state behind this ABI (boundary nit).  A production binding needs neither
