@@ -234,3 +234,21 @@ extern "C" __attribute__((visibility("hidden"))) void im360_set_error(const char
             return IM360_ERR_LAUNCH;                                  \
         }                                                             \
     } while (0)
+
+// ---- value -> template argument (host-side launchers): a run-time dtype / flag / small integer picks an instantiation
+namespace im360 {
+template <typename T> struct TypeTag { typedef T type; };
+// f(TypeTag<__bf16>{}) for dtype 0, f(TypeTag<_Float16>{}) for dtype 1 (f returns the status code); anything else is the
+// caller's "<who>: dtype %d unsupported"
+template <typename F> static inline int with_dtype(int dtype, const char* who, F&& f) {
+    if (dtype == 0) return f(TypeTag<__bf16>{});
+    if (dtype == 1) return f(TypeTag<_Float16>{});
+    im360_set_error("%s: dtype %d unsupported", who, dtype);
+    return IM360_ERR_UNSUPPORTED;
+}
+// f(std::integral_constant<int, V>{}) for the one V of Vs... that equals v; false: none does, no call
+template <int... Vs, typename F> static inline bool with_const(int v, F&& f) {
+    return ((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...);
+}
+template <typename F> static inline void with_bool(bool b, F&& f) { b ? f(std::true_type{}) : f(std::false_type{}); }
+}  // namespace im360

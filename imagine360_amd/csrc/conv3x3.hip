@@ -79,7 +79,6 @@ static inline ConvParams conv_params_zero() {
     return p;
 }
 
-
 // 16 bytes of zeros that out-of-image taps are pointed at (LDS-DMA loads cannot zero-fill by themselves)
 __device__ uint4 g_zero_chunk[1];
 
@@ -1656,72 +1655,138 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void c
     }
 }
 
+// ==== host side: which kernel a launch runs ===================================================================================
+
+// ---- the tiles of conv_igemm_kernel: WM x WN waves of TM x TN 32 x 32 MFMA blocks.  What a tile can do beyond the plain BK = 64 loop:
+//   has_cm = a taps-innermost form for 3 x 3 convolutions without wrap / upsample addressing (see the kernel; EPI 0 only); has_bk32 = a BK = 32 form (its stage rows
+//   divide over the workgroup's lanes); two_per_cu = exists for two workgroups per CU: 32-channel stages come first; big = the 256 x 320 convolution tile: K-split,
+//   GroupNorm statistics from the epilogue, kernels per residual mode (EPI 0 only)
+template <int WM_, int WN_, int TM_, int TN_>
+struct TileShape {
+    static constexpr int WM = WM_, WN = WN_, TM = TM_, TN = TN_;
+    static constexpr int BM = WM * TM * 32, BN = WN * TN * 32, NT = WM * WN * 64;
+    static constexpr bool has_cm = false, has_bk32 = false, two_per_cu = false, big = false;
+};
+struct Tile256x320 : TileShape<4, 2, 2, 5> { static constexpr bool has_cm = true, big = true; };
+struct Tile128x128 : TileShape<2, 2, 2, 2> { static constexpr bool has_cm = true, has_bk32 = true; };
+struct Tile256x64 : TileShape<4, 1, 2, 2> { static constexpr bool has_bk32 = true; };
+struct TileGeglu256x256 : TileShape<4, 2, 2, 4> {};                       // EPI 1; the 8-wave GEGLU tile is BK = 64 only
+// make ablate only
+struct Tile128x320 : TileShape<2, 2, 2, 5> { static constexpr bool has_bk32 = true, two_per_cu = true; };
+struct Tile192x320 : TileShape<2, 2, 3, 5> { static constexpr bool has_cm = true, has_bk32 = true; };      // four waves
+struct Tile128x256 : TileShape<2, 2, 2, 4> { static constexpr bool has_bk32 = true, two_per_cu = true; };  // EPI 1
+
+// 256 x 320 tiles of an [M, Cout] output; the tile is chosen once they fill the chip at least twice (256 CUs, one workgroup each).  BIG_TILE_MIN is also im360_linear_geglu's least count of 256 x 256 tiles for the ring kernel
+static inline long big_tile_count(long M, long Cout) { return ((M + 255) / 256) * (Cout / 320); }
+constexpr long BIG_TILE_MIN = 512;
+// K-split workspace of one part of one 256 x 320 tile: its fp32 accumulators, 160 per lane
+constexpr long KSPLIT_PART_BYTES = 160 * 512 * 4;
+
+// ---- knob conv_ring: the K loop of a persistent-kernel launch (launch_ring_t's `variant`) and who goes there
+//   1 = default: token-major GEMMs on the staggered 64-channel-stage loop (MODE 3, round 4), convolutions sent here on the interleaved
+//       ring (MODE 2); 8 = MODE 2 for the GEMMs too (round 2 / 3's default), 6 = MODE 3 for everything;
+//   make ablate: 2 = builtin LDS-DMA, plain ring; 3 = asm LDS-DMA, plain ring; 4 = staggered wave groups on the ring; 9 = 3 x 3
+//       convolution, taps innermost, in the persistent shell (knob conv_persist, never a knob value); 10 = two activation stages in
+//       flight (gemm_a3_kernel); 11 = the same with a chunk-major weight operand
+//   knob values only: 0 = no ring kernel where conv_igemm_kernel can serve; 5 = 1 and 7 = 6 with the convolutions on the ring too (any value
+//       >= 5 sends them); 12 / 13 = 1 with the GEGLU GEMMs on the four-wave tiles (knob g4's bits, for the A/B tools)
+enum RingLoop { RING_DEFAULT = 1, RING_DMA_BUILTIN = 2, RING_DMA_ASM = 3, RING_STAG_RING = 4, RING_STAG_ALL = 6, RING_INTERLEAVED = 8,
+                RING_CONV_CM = 9, RING_A3 = 10, RING_A3_BCM = 11 };
+struct RingKnob {
+    int raw;
+    bool on() const { return raw != 0; }
+    bool convs_too() const { return raw >= 5; }
+    int loop() const { return raw == 5 ? RING_DEFAULT : (raw == 7 ? RING_STAG_ALL : raw); }
+    int conv_loop() const { return raw == 7 ? RING_STAG_ALL : RING_DEFAULT; }
+    // the row-statistics and LayerNorm-folded epilogues exist on these loops only
+    int ln_loop() const { return (raw == RING_INTERLEAVED || raw == RING_A3 || raw == RING_A3_BCM) ? raw : RING_DEFAULT; }
+    bool g4_alias(bool narrow) const { return raw == (narrow ? 13 : 12); }
+};
+static inline RingKnob ring_knob() { return RingKnob{knob(KNOB_CONV_RING)}; }
+
+// ---- knob g4: which GEGLU GEMMs take the four-wave register-staged tiles (conv3x3_g4.hip)
+enum G4Bit { G4_GEGLU = 1, G4_GEGLU_LN = 2, G4_GEGLU_NARROW = 4, G4_GEGLU_LN_NARROW = 8 };
+// wide: 256 x 256 tiles, one workgroup per CU; narrow: the same loop on 256 x 128 tiles, two workgroups per CU
+static bool g4_fits(int bit, long M, long K, long Cout, bool narrow) {
+    if (!((knob(KNOB_G4) & bit) || ring_knob().g4_alias(narrow))) return false;
+    if ((K % 64) != 0 || K < 128 || (M % 256) != 0) return false;
+    return narrow ? (M / 256) * (Cout / 128) >= 512 : (Cout % 256) == 0 && (M / 256) * (Cout / 256) >= 256;
+}
+
+// ---- persistent launches: one workgroup per CU (`per_cu` = 2: two), grid a multiple of 8 (XCDs)
+static unsigned persistent_grid(long nblocks, int per_cu = 1) {
+    static const int ncu = [] {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 256;
+        return n >= 8 ? n / 8 * 8 : 8;
+    }();
+    const long want = (nblocks + 7) / 8 * 8, most = (long)per_cu * ncu;
+    return (unsigned)(want < most ? want : most);
+}
+// cout groups of the persistent tile walk (see conv_ring_kernel): the fewest of 1 / 2 / 4 / 8 that divide tiles_n and bring one group's
+// weights under ~3.4 MB of the XCD's 4 MB L2 (knob ring_groups: 0 = this rule, else forced when it divides tiles_n)
+static int ring_groups(long wbytes, int tiles_n, unsigned grid) {
+    int ng = 1;
+    const int force = knob(KNOB_RING_GROUPS);
+    if (force > 0) {
+        if ((force == 2 || force == 4 || force == 8) && tiles_n % force == 0) ng = force;
+    } else {
+        while (ng < 8 && wbytes / ng > 3400000L && tiles_n % (2 * ng) == 0) ng *= 2;
+        if (wbytes / ng > 3400000L) ng = 1;          // no split brings a group under the budget: keep the plain walk
+    }
+    return grid >= 8u * ng ? ng : 1;
+}
+
+// residual mode of tile_epilogue (RESM) as f's argument: the GEGLU epilogues have no residual (0), the LayerNorm-folded plain one
+// never carries one (2); for the others present (1) / absent (2) are different code
+template <int EPI, typename F>
+static void with_resm(const ConvParams& p, F&& f) {
+    if constexpr (EPI == 1 || EPI == 4) f(std::integral_constant<int, 0>{});
+    else if constexpr (EPI == 3) f(std::integral_constant<int, 2>{});
+    else with_const<1, 2>(p.res ? 1 : 2, f);
+}
+
+template <typename T, typename Tile, int EPI = 0> static int launch_conv_t(ConvParams p, hipStream_t stream);
+template <typename T, int TN, int EPI, bool LINEAR> static int launch_ring_t(ConvParams p, hipStream_t stream, int variant);
+
 // ---- the four-wave, register-staged tile for the token-major GEMMs (round 6)
 #include "conv3x3_g4.hip"
 
-// ---- ablation-only kernels (`make ablate`, -DIM360_ABLATE): gemm_a3_kernel (two activation stages in flight, knob conv_ring 10) and
-//      conv_halo_kernel (halo-patch 3 x 3 convolution, knob conv_halo) with its launcher -- measured, slower, not shipped; they live
-//      in conv3x3_ablate.hip and see this file's ConvParams / tile_epilogue / helpers
-#ifdef IM360_ABLATE
+// ---- ablation-only kernels and launch rules (`make ablate`, -DIM360_ABLATE): gemm_a3_kernel (two activation stages in flight, knob conv_ring 10),
+//      conv_halo_kernel (halo-patch 3 x 3 convolution, knob conv_halo) and the rejected A/B variants of the kernels above -- measured, slower, not
+//      shipped; they live in conv3x3_ablate.hip and see this file's ConvParams / tile_epilogue / helpers.  Every launcher below first asks that
+//      file's ablate_*() whether a variant takes the launch: constant false in the default build
 #define IM360_CONV3X3_INCLUDES_ABLATE 1
 #include "conv3x3_ablate.hip"
-#endif
 
-template <typename T, int WM, int WN, int TM, int TN, int EPI = 0>
+template <typename T, typename Tile, int EPI>
 static int launch_conv_t(ConvParams p, hipStream_t stream) {
-    constexpr int BM = WM * TM * 32, BN = WN * TN * 32, NT = WM * WN * 64;
-    p.tiles_n = (p.Cout + BN - 1) / BN;
-    p.nblocks = ((p.M + BM - 1) / BM) * p.tiles_n;
+    constexpr int WM = Tile::WM, WN = Tile::WN, TM = Tile::TM, TN = Tile::TN, NT = Tile::NT;
+    p.tiles_n = (p.Cout + Tile::BN - 1) / Tile::BN;
+    p.nblocks = ((p.M + Tile::BM - 1) / Tile::BM) * p.tiles_n;
     if (p.nblocks > 0x7fffffffL) {
         im360_set_error("conv_fwd: problem too large");
         return IM360_ERR_ARG;
     }
     const int bk_env = knob(KNOB_CONV_BK);       // tuning override
-    constexpr bool has_bk32 = (BN * 4) % NT == 0 && (BM * 4) % NT == 0 && (EPI != 1 || NT == 256);      // the 8-wave GEGLU tile is BK = 64 only
-    // 3x3 convolutions without wrap / upsample addressing: taps innermost (see the kernel); the 256 x 320 and 128 x 128 tiles
-    constexpr bool has_cm = EPI == 0 && ((WM == 4 && WN == 2 && TN == 5) || (WM == 2 && WN == 2 && TN == 2) || (WM == 2 && WN == 2 && TM == 3 && TN == 5));
+    constexpr bool has_cm = Tile::has_cm && EPI == 0, big = Tile::big && EPI == 0;
+    static_assert(!Tile::has_bk32 || ((Tile::BN * 4) % NT == 0 && (Tile::BM * 4) % NT == 0), "a BK = 32 stage's rows must divide over the workgroup's lanes");
+    // 3x3 convolutions without wrap / upsample addressing: taps innermost (see the kernel)
     const bool cm = has_cm && knob(KNOB_CONV_CM) && p.ntaps == 9 && !p.wrap && !p.up && p.Cin % 64 == 0 && bk_env != 32;
-    if (!(WM == 4 && WN == 2 && TM == 2 && TN == 5 && EPI == 0) || p.ntaps != 9 || p.up || p.Cin % 64 != 0 || bk_env == 32) p.ksplit = 0;       // K-split: the 256 x 320 tile's 3 x 3 kernels only
-    const unsigned grid_cm = (unsigned)(p.nblocks * (p.ksplit > 1 ? p.ksplit : 1));
+    if (!big || p.ntaps != 9 || p.up || p.Cin % 64 != 0 || bk_env == 32) p.ksplit = 0;       // K-split: the 256 x 320 tile's 3 x 3 kernels only
+    const unsigned grid = (unsigned)p.nblocks, grid_ks = (unsigned)(p.nblocks * (p.ksplit > 1 ? p.ksplit : 1));
     p.dbg = knob(KNOB_CONV_DBG);
-#ifdef IM360_ABLATE
-    if constexpr (((WM == 4 && WN == 2) || (WM == 2 && WN == 2 && TM == 3)) && TN == 5 && EPI == 0) {
-        if (p.dbg && p.Cin % 64 == 0) {         // ablation build of the 256 x 320 conv tile (results are garbage)
-            if (cm) hipLaunchKernelGGL((conv_igemm_kernel<T, 64, WM, WN, TM, TN, EPI, true, true>), dim3((unsigned)p.nblocks), dim3(NT), 0, stream, p);
-            else hipLaunchKernelGGL((conv_igemm_kernel<T, 64, WM, WN, TM, TN, EPI, false, true>), dim3((unsigned)p.nblocks), dim3(NT), 0, stream, p);
+    if (int rc; ablate_conv_t<T, Tile, EPI>(p, stream, cm, rc)) return rc;
+    if constexpr (big) {
+        if (cm) {       // per residual mode of the epilogue (no RESM 0 instantiation of this form: nothing would launch it), with or without GroupNorm statistics
+            with_bool(p.gn_out != nullptr, [&](auto gns) { with_const<1, 2>(p.res ? 1 : 2, [&](auto resm) {
+                hipLaunchKernelGGL((conv_igemm_kernel<T, 64, WM, WN, TM, TN, EPI, true, false, false, decltype(gns)::value, false, decltype(resm)::value>), dim3(grid_ks), dim3(NT), 0, stream, p);
+            }); });
             IM360_CHECK_LAUNCH();
             return IM360_OK;
         }
-    }
-#endif
-    if constexpr (WM == 4 && WN == 2 && TM == 2 && TN == 5 && EPI == 0) {
-#ifdef IM360_ABLATE
-        // staggered wave groups on this kernel's producer (round 4; knob conv_stag): identical bits, 0.97 - 1.05 x the plain loop's
-        // speed on the nine cfg2 convolution shapes (profiles/r04_conv_stag_ab.log) -- with two stage buffers a step's operands have
-        // one step to arrive either way, and that latency, not the fragment reads the stagger hides, is what the loop waits for
-        if (knob(KNOB_CONV_STAG) && p.Cin % 64 == 0 && bk_env != 32) {
-            if (p.gn_out) {
-                if (cm) hipLaunchKernelGGL((conv_igemm_kernel<T, 64, WM, WN, TM, TN, EPI, true, false, false, true, true>), dim3((unsigned)p.nblocks), dim3(NT), 0, stream, p);
-                else hipLaunchKernelGGL((conv_igemm_kernel<T, 64, WM, WN, TM, TN, EPI, false, false, false, true, true>), dim3((unsigned)p.nblocks), dim3(NT), 0, stream, p);
-            } else {
-                if (cm) hipLaunchKernelGGL((conv_igemm_kernel<T, 64, WM, WN, TM, TN, EPI, true, false, false, false, true>), dim3((unsigned)p.nblocks), dim3(NT), 0, stream, p);
-                else hipLaunchKernelGGL((conv_igemm_kernel<T, 64, WM, WN, TM, TN, EPI, false, false, false, false, true>), dim3((unsigned)p.nblocks), dim3(NT), 0, stream, p);
-            }
-            IM360_CHECK_LAUNCH();
-            return IM360_OK;
-        }
-#endif
-        if (p.gn_out) {            // the 256 x 320 tile with GroupNorm statistics from its epilogue (per residual mode of the epilogue)
-            if (cm) {
-                if (p.res) hipLaunchKernelGGL((conv_igemm_kernel<T, 64, WM, WN, TM, TN, EPI, true, false, false, true, false, 1>), dim3(grid_cm), dim3(NT), 0, stream, p);
-                else hipLaunchKernelGGL((conv_igemm_kernel<T, 64, WM, WN, TM, TN, EPI, true, false, false, true, false, 2>), dim3(grid_cm), dim3(NT), 0, stream, p);
-            } else hipLaunchKernelGGL((conv_igemm_kernel<T, 64, WM, WN, TM, TN, EPI, false, false, false, true>), dim3(grid_cm), dim3(NT), 0, stream, p);
-            IM360_CHECK_LAUNCH();
-            return IM360_OK;
-        }
-        if (cm) {
-            if (p.res) hipLaunchKernelGGL((conv_igemm_kernel<T, 64, WM, WN, TM, TN, EPI, true, false, false, false, false, 1>), dim3(grid_cm), dim3(NT), 0, stream, p);
-            else hipLaunchKernelGGL((conv_igemm_kernel<T, 64, WM, WN, TM, TN, EPI, true, false, false, false, false, 2>), dim3(grid_cm), dim3(NT), 0, stream, p);
+        if (p.gn_out) {
+            hipLaunchKernelGGL((conv_igemm_kernel<T, 64, WM, WN, TM, TN, EPI, false, false, false, true>), dim3(grid_ks), dim3(NT), 0, stream, p);
             IM360_CHECK_LAUNCH();
             return IM360_OK;
         }
@@ -1730,20 +1795,20 @@ static int launch_conv_t(ConvParams p, hipStream_t stream) {
         im360_set_error("conv_fwd: GroupNorm statistics are produced by the 256 x 320 tile only (ask im360_conv_gn_slabs first)");
         return IM360_ERR_UNSUPPORTED;
     }
+    // (the two-workgroups-per-CU tiles, and the 256 x 64 tile under knob conv_small 0, run 32-channel stages)
+    const bool bk64 = p.Cin % 64 == 0 && bk_env != 32 && !Tile::two_per_cu && !(std::is_same<Tile, Tile256x64>::value && knob(KNOB_CONV_SMALL) == 0);
     if (cm) {
-        // (the 256 x 320 tile returned above with its per-residual-mode kernels: no RESM 0 instantiation of it for nothing to launch)
-        if constexpr (has_cm && !(WM == 4 && WN == 2 && TM == 2 && TN == 5 && EPI == 0))
-            hipLaunchKernelGGL((conv_igemm_kernel<T, 64, WM, WN, TM, TN, EPI, true>), dim3((unsigned)p.nblocks), dim3(NT), 0, stream, p);
-    } else if ((p.Cin % 64 == 0 && bk_env != 32 && !(WM == 2 && TN >= 4 && TM == 2) && !(WM == 4 && WN == 1 && knob(KNOB_CONV_SMALL) == 0)) || !has_bk32) {      // (the 128 x 320 / 128 x 256 tiles exist for two workgroups per CU: 32-channel stages)
-        hipLaunchKernelGGL((conv_igemm_kernel<T, 64, WM, WN, TM, TN, EPI>), dim3(grid_cm), dim3(NT), 0, stream, p);
-    } else if constexpr (has_bk32) {
-        hipLaunchKernelGGL((conv_igemm_kernel<T, 32, WM, WN, TM, TN, EPI>), dim3((unsigned)p.nblocks), dim3(NT), 0, stream, p);
+        if constexpr (has_cm && !big) hipLaunchKernelGGL((conv_igemm_kernel<T, 64, WM, WN, TM, TN, EPI, true>), dim3(grid), dim3(NT), 0, stream, p);
+    } else if (bk64 || !Tile::has_bk32) {
+        hipLaunchKernelGGL((conv_igemm_kernel<T, 64, WM, WN, TM, TN, EPI>), dim3(grid_ks), dim3(NT), 0, stream, p);
+    } else if constexpr (Tile::has_bk32) {
+        hipLaunchKernelGGL((conv_igemm_kernel<T, 32, WM, WN, TM, TN, EPI>), dim3(grid), dim3(NT), 0, stream, p);
     }
     IM360_CHECK_LAUNCH();
     return IM360_OK;
 }
 
-// persistent ring kernel: one workgroup per CU (its LDS footprint allows no second one), grid a multiple of 8 (XCDs)
+// persistent ring kernel: one workgroup per CU (its LDS footprint allows no second one)
 template <typename T, int TN, int EPI, bool LINEAR>
 static int launch_ring_t(ConvParams p, hipStream_t stream, int variant) {
     constexpr int BM = 256, BN = 2 * TN * 32;
@@ -1753,130 +1818,27 @@ static int launch_ring_t(ConvParams p, hipStream_t stream, int variant) {
         im360_set_error("linear_fwd / conv_fwd: problem too large");
         return IM360_ERR_ARG;
     }
-    static const int ncu = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 256;
-        return n >= 8 ? n / 8 * 8 : 8;
-    }();
     p.dbg = knob(KNOB_CONV_DBG);
-    const long want = (p.nblocks + 7) / 8 * 8;
-    const unsigned grid = (unsigned)(want < ncu ? want : ncu);
-    // cout groups of the tile walk (see the kernel): the fewest of 1 / 2 / 4 / 8 that divide tiles_n and bring one group's
-    // weights under ~3.4 MB of the XCD's 4 MB L2 (knob ring_groups: 0 = this rule, else forced when it divides tiles_n)
-    {
-        const long wbytes = (long)p.tiles_n * BN * p.ntaps * p.Cin * 2;
-        int ng = 1;
-        const int force = knob(KNOB_RING_GROUPS);
-        if (force > 0) {
-            if ((force == 2 || force == 4 || force == 8) && p.tiles_n % force == 0) ng = force;
-        } else {
-            while (ng < 8 && wbytes / ng > 3400000L && p.tiles_n % (2 * ng) == 0) ng *= 2;
-            if (wbytes / ng > 3400000L) ng = 1;          // no split brings a group under the budget: keep the plain walk
-        }
-        p.ngroups = grid >= 8u * ng ? ng : 1;
-    }
-    // variant (knob conv_ring): 1 = default: token-major GEMMs on the staggered 64-channel-stage loop (MODE 3, round 4), convolutions
-    // sent here by knob value 5 on the interleaved ring (MODE 2); 8 = MODE 2 for the GEMMs too (round 2 / 3's default), 6 = MODE 3
-    // for everything; make ablate: 2 = builtin LDS-DMA, plain ring; 3 = asm LDS-DMA, plain ring; 4 = staggered wave groups on the ring
-    const bool stag = p.Cin % 64 == 0 && (variant == 6 || (LINEAR && variant != 8 && (variant < 2 || variant > 4)));
-    // the default loop's kernels exist per residual mode of the epilogue (tile_epilogue, RESM): present / absent are different code
-    auto launch_stag = [&](auto gns_c) {
-        constexpr bool G = decltype(gns_c)::value;
-#ifdef IM360_ABLATE
-        // measured and not shipped (profiles/r04_gemm_a3_ab.log): identical bits on every shape and epilogue at the first run, but
-        // 0.85 - 0.97 x the staggered loop's speed (only the level-0 GEGLU ties): with the weight tile in 64-byte row segments the
-        // L2 -> LDS path carries 2170 clk of transfers per stage instead of 1385, and that path's throughput -- not only the latency
-        // of the activation rows -- is what the K loop runs against
-        if constexpr (LINEAR && EPI != 3) {             // (EPI 3's two sets of c1 | c2 do not fit next to the A3 kernel's 156 KB)
-            if (variant == 10) {                        // two activation stages in flight (gemm_a3_kernel)
-                if constexpr (EPI == 1 || EPI == 4) {
-                    hipLaunchKernelGGL((gemm_a3_kernel<T, TN, EPI, G, 0>), dim3(grid), dim3(512), 0, stream, p);
-                } else {
-                    if (p.res) hipLaunchKernelGGL((gemm_a3_kernel<T, TN, EPI, G, 1>), dim3(grid), dim3(512), 0, stream, p);
-                    else hipLaunchKernelGGL((gemm_a3_kernel<T, TN, EPI, G, 2>), dim3(grid), dim3(512), 0, stream, p);
-                }
-                return;
-            }
-            if (variant == 11) {                        // the same with a CHUNK-MAJOR weight operand (the caller repacked it: kernels.chunk_major)
-                if constexpr (EPI == 1 || EPI == 4) {
-                    hipLaunchKernelGGL((gemm_a3_kernel<T, TN, EPI, G, 0, true>), dim3(grid), dim3(512), 0, stream, p);
-                } else {
-                    if (p.res) hipLaunchKernelGGL((gemm_a3_kernel<T, TN, EPI, G, 1, true>), dim3(grid), dim3(512), 0, stream, p);
-                    else hipLaunchKernelGGL((gemm_a3_kernel<T, TN, EPI, G, 2, true>), dim3(grid), dim3(512), 0, stream, p);
-                }
-                return;
-            }
-        }
-#endif
-        if constexpr (EPI == 1 || EPI == 4) {
-            hipLaunchKernelGGL((conv_ring_kernel<T, TN, EPI, LINEAR, true, 3, G, 0>), dim3(grid), dim3(512), 0, stream, p);
-        } else if constexpr (EPI == 3) {
-            hipLaunchKernelGGL((conv_ring_kernel<T, TN, EPI, LINEAR, true, 3, G, 2>), dim3(grid), dim3(512), 0, stream, p);
-        } else {
-            if (p.res) hipLaunchKernelGGL((conv_ring_kernel<T, TN, EPI, LINEAR, true, 3, G, 1>), dim3(grid), dim3(512), 0, stream, p);
-            else hipLaunchKernelGGL((conv_ring_kernel<T, TN, EPI, LINEAR, true, 3, G, 2>), dim3(grid), dim3(512), 0, stream, p);
-        }
-    };
-#ifdef IM360_ABLATE
-    if constexpr (!LINEAR && TN == 5 && EPI == 0) {
-        if (variant == 9) {                     // 3 x 3 convolution, taps innermost, on the plain 64-channel loop in the persistent shell (the caller checked that the order applies)
-            if (p.gn_out) {
-                if (p.res) hipLaunchKernelGGL((conv_ring_kernel<T, TN, EPI, LINEAR, true, 4 + 128, true, 1>), dim3(grid), dim3(512), 0, stream, p);
-                else hipLaunchKernelGGL((conv_ring_kernel<T, TN, EPI, LINEAR, true, 4 + 128, true, 2>), dim3(grid), dim3(512), 0, stream, p);
-            } else {
-                if (p.res) hipLaunchKernelGGL((conv_ring_kernel<T, TN, EPI, LINEAR, true, 4 + 128, false, 1>), dim3(grid), dim3(512), 0, stream, p);
-                else hipLaunchKernelGGL((conv_ring_kernel<T, TN, EPI, LINEAR, true, 4 + 128, false, 2>), dim3(grid), dim3(512), 0, stream, p);
-            }
-            IM360_CHECK_LAUNCH();
-            return IM360_OK;
-        }
-    }
-#endif
-    if constexpr (LINEAR && TN == 5 && (EPI == 2 || EPI == 5)) {
-        if (p.gn_out) {                         // GroupNorm partial sums from the epilogue (see ConvParams::gn_out)
-            if (stag) launch_stag(std::true_type{});
-            else hipLaunchKernelGGL((conv_ring_kernel<T, TN, EPI, LINEAR, true, 2, true>), dim3(grid), dim3(512), 0, stream, p);
-            IM360_CHECK_LAUNCH();
-            return IM360_OK;
-        }
-    }
-    if (p.gn_out) {
+    const unsigned grid = persistent_grid(p.nblocks);
+    p.ngroups = ring_groups((long)p.tiles_n * BN * p.ntaps * p.Cin * 2, p.tiles_n, grid);
+    // the staggered loop: everything on RING_STAG_ALL, the token-major GEMMs on every loop that is not one of the ring's own
+    const bool stag = p.Cin % 64 == 0 && (variant == RING_STAG_ALL || (LINEAR && variant != RING_INTERLEAVED && variant != RING_DMA_BUILTIN && variant != RING_DMA_ASM && variant != RING_STAG_RING));
+    constexpr bool has_gns = LINEAR && TN == 5 && (EPI == 2 || EPI == 5);       // GroupNorm partial sums from the epilogue (see ConvParams::gn_out)
+    if (int rc; ablate_ring_t<T, TN, EPI, LINEAR>(p, stream, variant, grid, stag, rc)) return rc;
+    if (p.gn_out && !has_gns) {
         im360_set_error("linear_fwd: GroupNorm statistics are produced by the plain / row-statistics epilogues only");
         return IM360_ERR_UNSUPPORTED;
     }
-#ifdef IM360_ABLATE
-    if constexpr (LINEAR && TN == 5 && EPI == 2) {
-        if (stag && p.dbg) {                    // ablation builds of the staggered loop (tools/ab_stag.py --ablate)
-            switch (p.dbg & 7) {
-#define IM360_ABL_CASE(a) case a: hipLaunchKernelGGL((conv_ring_kernel<T, TN, EPI, LINEAR, true, 3 + 16 * a>), dim3(grid), dim3(512), 0, stream, p); break;
-                IM360_ABL_CASE(1) IM360_ABL_CASE(2) IM360_ABL_CASE(3) IM360_ABL_CASE(4) IM360_ABL_CASE(5) IM360_ABL_CASE(6) IM360_ABL_CASE(7)
-#undef IM360_ABL_CASE
+    // (3x3 convolutions on the staggered loop: 27 spilled registers, 0.90 - 1.13 PF/s against the two-stage kernel's 1.05 - 1.16: make ablate only)
+    with_bool(has_gns && p.gn_out, [&](auto gns) {
+        constexpr bool G = has_gns && decltype(gns)::value;
+        if constexpr (LINEAR) {
+            if (stag) {
+                return with_resm<EPI>(p, [&](auto resm) { hipLaunchKernelGGL((conv_ring_kernel<T, TN, EPI, LINEAR, true, 3, G, decltype(resm)::value>), dim3(grid), dim3(512), 0, stream, p); });
             }
-            IM360_CHECK_LAUNCH();
-            return IM360_OK;
         }
-    }
-    if constexpr (EPI < 3) {
-        if (variant == 2) hipLaunchKernelGGL((conv_ring_kernel<T, TN, EPI, LINEAR, false, 0>), dim3(grid), dim3(512), 0, stream, p);
-        else if (variant == 3) hipLaunchKernelGGL((conv_ring_kernel<T, TN, EPI, LINEAR, true, 0>), dim3(grid), dim3(512), 0, stream, p);
-        else if (variant == 4) hipLaunchKernelGGL((conv_ring_kernel<T, TN, EPI, LINEAR, true, 1>), dim3(grid), dim3(512), 0, stream, p);
-        if (variant >= 2 && variant <= 4) {
-            IM360_CHECK_LAUNCH();
-            return IM360_OK;
-        }
-    }
-#endif
-    if constexpr (LINEAR) {
-        if (stag) launch_stag(std::false_type{});
-        else hipLaunchKernelGGL((conv_ring_kernel<T, TN, EPI, LINEAR, true, 2>), dim3(grid), dim3(512), 0, stream, p);
-    } else {
-        // (3x3 convolutions on the staggered loop: 27 spilled registers, 0.90 - 1.13 PF/s against the two-stage kernel's 1.05 - 1.16: make ablate only)
-#ifdef IM360_ABLATE
-        if (stag) hipLaunchKernelGGL((conv_ring_kernel<T, TN, EPI, LINEAR, true, 3>), dim3(grid), dim3(512), 0, stream, p);
-        else
-#endif
-        hipLaunchKernelGGL((conv_ring_kernel<T, TN, EPI, LINEAR, true, 2>), dim3(grid), dim3(512), 0, stream, p);
-    }
+        hipLaunchKernelGGL((conv_ring_kernel<T, TN, EPI, LINEAR, true, 2, G>), dim3(grid), dim3(512), 0, stream, p);
+    });
     IM360_CHECK_LAUNCH();
     return IM360_OK;
 }
@@ -1887,13 +1849,13 @@ static int launch_ring_t(ConvParams p, hipStream_t stream, int variant) {
 // three quarters of the large tile's rate.  Knob conv_ksplit: 0 = off, 1 = this rule, 2 .. 4 = that many parts wherever eligible.
 static int ksplit_plan(long M, int Cin, int Cout, int ntaps, int up, int wrap, bool gn_stats) {
     const int kn = knob(KNOB_CONV_KSPLIT);
-    if (kn <= 0 || !knob(KNOB_CONV_BIG) || !knob(KNOB_CONV_CM) || knob(KNOB_CONV_BK) == 32 || knob(KNOB_CONV_RING) >= 5) return 1;
+    if (kn <= 0 || !knob(KNOB_CONV_BIG) || !knob(KNOB_CONV_CM) || knob(KNOB_CONV_BK) == 32 || ring_knob().convs_too()) return 1;
     if (ntaps != 9 || up || Cout % 320 != 0 || Cin % 64 != 0 || M > 0x7fffffffL) return 1;
     if (wrap && kn == 1) return 1;              // (the panorama's wrap-addressed, tap-major launches split correctly but gain nothing inside the step -- they run beside the
                                                 //  perspective branch: 290.2 vs 289.9 ms, profiles/r06_conv_ksplit_ab.log -- so the rule leaves them alone; knob 9 = the rule for them too)
-    const long T = ((M + 255) / 256) * (Cout / 320);
+    const long T = big_tile_count(M, Cout);
     const int nch = Cin / 64;
-    if (T < 64 || (gn_stats && T < 512)) return 1;
+    if (T < 64 || (gn_stats && T < BIG_TILE_MIN)) return 1;
     // Liveness of the waiting owners (conv_igemm_kernel): block ids are part-major and every XCD dispatches its share of them in order, so an XCD
     // starts a launch's owners only after ALL of that launch's parts it was dealt -- one launch alone can never block itself.  Two launches side
     // by side (the two branches' streams) could only block each other if some XCD's 32 CUs were ALL held by waiting owners of ONE launch (those of
@@ -1904,10 +1866,10 @@ static int ksplit_plan(long M, int Cin, int Cout, int ntaps, int up, int wrap, b
     // measured inside the step (profiles/r06_conv_ksplit_ab.log): launches below two rounds of the chip -- which otherwise take the 128 x 128 tile --
     // gain (- 3 ... - 4.7 ms per cfg2 step), the 640-tile launches (2.5 rounds -> five half rounds) LOSE 2 ms to the partial sums' round trip:
     // the rule is for the former only (knob 5: for every tile count, the A/B; 7 / 8: two / four parts for the former)
-    if (kn == 9) { if (T >= 512) return 1; }
-    else if (T >= 512 && kn != 5) return 1;
-    if (T < 512 && (kn == 7 || kn == 8)) return (kn == 7 ? 2 : 4) <= nch ? (kn == 7 ? 2 : 4) : 1;
-    double best = T >= 512 ? (double)((T + 255) / 256) : 1.35 * (double)T / 256.0 + 0.15;
+    if (kn == 9) { if (T >= BIG_TILE_MIN) return 1; }
+    else if (T >= BIG_TILE_MIN && kn != 5) return 1;
+    if (T < BIG_TILE_MIN && (kn == 7 || kn == 8)) return (kn == 7 ? 2 : 4) <= nch ? (kn == 7 ? 2 : 4) : 1;
+    double best = T >= BIG_TILE_MIN ? (double)((T + 255) / 256) : 1.35 * (double)T / 256.0 + 0.15;
     int bs = 1;
     for (int S = 2; S <= 4 && S <= nch; ++S) {
         const double c = (double)((T * S + 255) / 256) / S * (1.0 + 0.04 * (S - 1));
@@ -1923,38 +1885,19 @@ template <typename T>
 static int launch_conv(const ConvParams& p_in, hipStream_t stream) {
     ConvParams p = p_in;
     const int big_env = knob(KNOB_CONV_BIG);           // tuning overrides
-    const int ring_env = knob(KNOB_CONV_RING);
+    const RingKnob ring = ring_knob();
     if (!(p.ks_ws && p.ks_cnt && p.ksplit > 1)) p.ksplit = 0;       // (the entry point checked the plan and the buffers)
     // 256 x 320 tiles once they fill the chip at least twice (one workgroup per CU) -- or in K parts (ksplit_plan)
-    if (big_env && p.Cout % 320 == 0 && p.Cin % 64 == 0 && (((p.M + 255) / 256) * (p.Cout / 320) >= 512 || p.ksplit > 1)) {
+    if (big_env && p.Cout % 320 == 0 && p.Cin % 64 == 0 && (big_tile_count(p.M, p.Cout) >= BIG_TILE_MIN || p.ksplit > 1)) {
         const bool linear = p.ntaps == 1 && p.Hin == 1 && p.Win == 1 && !p.temb;       // EPI 2 has no temb add
-#ifdef IM360_ABLATE
-        if (knob(KNOB_CONV_HALO)) {
-            ConvParams ph = p;
-            if (halo_geometry(ph)) return launch_halo<T>(ph, stream);
-        }
-        if (big_env == 2) return linear ? launch_conv_t<T, 2, 2, 2, 5, 2>(p, stream) : launch_conv_t<T, 2, 2, 2, 5>(p, stream);   // A/B: 128 x 320, 2 workgroups per CU
-        // A/B: the same 256 x 320 tile on FOUR waves (128 x 160 each, 320 accumulators in the unified 512-register file, one
-        // wave per SIMD): 144 instead of 224 KB of fragment reads per K step
-        if (big_env == 4 && !linear) return launch_conv_t<T, 2, 2, 3, 5>(p, stream);
-#endif
+        if (int rc; ablate_conv<T>(p, stream, linear, big_env, rc)) return rc;
         // measured (tools/ab_ring.py, profiles/README.md): the persistent ring kernel wins 3-8 % on the token-major GEMMs
-        // (short K, epilogue-heavy) and loses 1-8 % on the deep-K convolutions; knob value 5 forces it for both
-#ifdef IM360_ABLATE
-        // round 4, measured and not shipped: 3 x 3 convolutions with the taps innermost on the PERSISTENT kernel (next tile's first
-        // stage requested under the epilogue, no workgroup turnover between tiles; knob conv_persist).  Identical bits on nine
-        // shapes incl. stride 2 and the statistics epilogue.  First form 0.93 - 1.04 x conv_igemm_kernel's speed: hipcc kept the 64-bit
-        // tap / chunk offsets in VGPR pairs, spilled one and reloaded it inside the K loop -- a scratch reload is a VMEM load whose
-        // wait also waits for the stage requested in front of it.  With the offsets 32-bit and pinned to SGPRs the loop is clean and
-        // the kernel TIES: 0.96 - 1.05 x (profiles/r04_conv_persist_ab.log) -- workgroup turnover is not what the convolutions lose.
-        if (knob(KNOB_CONV_PERSIST) && !linear && knob(KNOB_CONV_CM) && p.ntaps == 9 && !p.wrap && !p.up && !p.x2 && p.Cin % 64 == 0 && knob(KNOB_CONV_BK) != 32 && p.M <= 0x7fffffffL)
-            return launch_ring_t<T, 5, 0, false>(p, stream, 9);
-#endif
-        if (p.gn_out && !linear) return launch_conv_t<T, 4, 2, 2, 5>(p, stream);
-        if (ring_env && linear) return launch_ring_t<T, 5, 2, true>(p, stream, ring_env == 5 ? 1 : (ring_env == 7 ? 6 : ring_env));
-        if (ring_env >= 5) return launch_ring_t<T, 5, 0, false>(p, stream, ring_env == 7 ? 6 : 1);
-        if (linear) return launch_conv_t<T, 4, 2, 2, 5, 2>(p, stream);
-        return launch_conv_t<T, 4, 2, 2, 5>(p, stream);
+        // (short K, epilogue-heavy) and loses 1-8 % on the deep-K convolutions; knob values >= 5 force it for both
+        if (p.gn_out && !linear) return launch_conv_t<T, Tile256x320>(p, stream);
+        if (ring.on() && linear) return launch_ring_t<T, 5, 2, true>(p, stream, ring.loop());
+        if (ring.convs_too()) return launch_ring_t<T, 5, 0, false>(p, stream, ring.conv_loop());
+        if (linear) return launch_conv_t<T, Tile256x320, 2>(p, stream);
+        return launch_conv_t<T, Tile256x320>(p, stream);
     }
     // Cout % 128 in (0, 64] (the UNet's 320 on grids too small for the 256 x 320 tile, i.e. every cfg1-sized launch): rounds 1 - 2
     // used 256 x 64 tiles so that no cout tile is half empty.  Since round 3 the 64-channel instantiation of that tile spills 688
@@ -1964,9 +1907,18 @@ static int launch_conv(const ConvParams& p_in, hipStream_t stream) {
     // 0.228 ms (taps innermost, 17 % of the MFMA work wasted on the half-empty tile all the same).  Knob conv_small: 2 = 128 x 128
     // (default), 0 = 256 x 64 / 32 channels, 1 = 256 x 64 / 64 channels.
     const int rem = p.Cout % 128;
-    const int small = knob(KNOB_CONV_SMALL);
-    if (rem != 0 && rem <= 64 && p.Cout > 64 && small != 2) return launch_conv_t<T, 4, 1, 2, 2>(p, stream);
-    return launch_conv_t<T, 2, 2, 2, 2>(p, stream);
+    if (rem != 0 && rem <= 64 && p.Cout > 64 && knob(KNOB_CONV_SMALL) != 2) return launch_conv_t<T, Tile256x64>(p, stream);
+    return launch_conv_t<T, Tile128x128>(p, stream);
+}
+
+// ConvParams of a token-major Linear y[M, N] = x[M, K] w^T: a 1 x 1 convolution over an [M, 1, 1, K] view
+static ConvParams linear_params(const void* x, const void* w_packed, void* y, int64_t M, int64_t K, int64_t N) {
+    ConvParams p = conv_params_zero();
+    p.x = x; p.w = w_packed; p.y = y;
+    p.N = (int)M; p.Hin = 1; p.Win = 1; p.Cin = (int)K; p.Hout = 1; p.Wout = 1; p.Cout = (int)N; p.ntaps = 1;
+    p.stride = 1; p.imgs_per_temb = 1;
+    p.M = M;
+    return p;
 }
 
 // weights [Cout, Cin, kh, kw] (PyTorch) -> [CoutPad128][kh*kw][CinPad] zero padded, K contiguous
@@ -1995,7 +1947,7 @@ extern "C" __attribute__((visibility("default"))) int64_t im360_conv_gn_slabs(in
     using namespace im360;
     const int64_t hw = Hout * Wout, M = N * hw;
     if (N <= 0 || hw <= 0 || (hw % 256) != 0 || (Cout % 320) != 0 || (Cin % 64) != 0 || (ntaps != 1 && ntaps != 9)) return 0;
-    if (!knob(KNOB_CONV_BIG) || (M / 256) * (Cout / 320) < 512) return 0;
+    if (!knob(KNOB_CONV_BIG) || big_tile_count(M, Cout) < BIG_TILE_MIN) return 0;
     return hw / 256;
 }
 
@@ -2029,23 +1981,19 @@ static int conv_fwd_impl(const void* x, const void* w_packed, const void* bias, 
     p.gn_out = (float*)gn_partial;
     if (ks_ws || ks_cnt) {
         const int S = ksplit_plan(p.M, p.Cin, p.Cout, p.ntaps, p.up, p.wrap, gn_partial != nullptr);
-        const int64_t tiles = Cout % 320 == 0 ? ((p.M + 255) / 256) * (Cout / 320) : 0;
+        const int64_t tiles = Cout % 320 == 0 ? big_tile_count(p.M, Cout) : 0;
         IM360_CHECK_ARG(S > 1, "conv_fwd_ksplit: im360_conv_ksplit_plan gives no K-split for this launch");
         IM360_CHECK_ARG(ks_ws && ks_cnt && ((uintptr_t)ks_ws % 16) == 0 && ((uintptr_t)ks_cnt % 4) == 0 && ks_cnt_n >= tiles &&
-                        ks_ws_bytes >= tiles * (S - 1) * (int64_t)(160 * 512 * 4),
+                        ks_ws_bytes >= tiles * (S - 1) * KSPLIT_PART_BYTES,
                         "conv_fwd_ksplit: %ld tiles x %d parts need %ld workspace bytes and %ld zeroed counters", (long)tiles, S,
-                        (long)(tiles * (S - 1) * (int64_t)(160 * 512 * 4)), (long)tiles);
+                        (long)(tiles * (S - 1) * KSPLIT_PART_BYTES), (long)tiles);
         p.ksplit = S;
         p.ks_ws = (float*)ks_ws;
         p.ks_cnt = (int*)ks_cnt;
     }
-    hipStream_t s = (hipStream_t)stream;
     // token-major linears routed through the kernel (1x1 taps on a [M, 1, 1, K] view) are accounted separately
     ProfScope prof(ntaps == 1 && Hin == 1 && Win == 1 ? PROF_GEMM : PROF_CONV, stream);
-    if (dtype == 0) return launch_conv<__bf16>(p, s);
-    if (dtype == 1) return launch_conv<_Float16>(p, s);
-    im360_set_error("conv_fwd: dtype %d unsupported", dtype);
-    return IM360_ERR_UNSUPPORTED;
+    return with_dtype(dtype, "conv_fwd", [&](auto t) { return launch_conv<typename decltype(t)::type>(p, (hipStream_t)stream); });
 }
 
 extern "C" __attribute__((visibility("default"))) int im360_conv_fwd(const void* x, const void* w_packed, const void* bias, const void* temb,
@@ -2096,37 +2044,34 @@ extern "C" __attribute__((visibility("default"))) int im360_conv_up2_fwd(const v
                     "conv_up2_fwd: misaligned pointer");
     IM360_CHECK_ARG(dtype == 0 || dtype == 1, "conv_up2_fwd: dtype %d unsupported", dtype);
     ConvParams p = conv_params_zero();
-    p.x = x; p.bias = bias; p.temb = nullptr; p.res = nullptr; p.y = y;
+    p.x = x; p.bias = bias; p.y = y;
     p.N = (int)N; p.Hin = (int)Hin; p.Win = (int)Win; p.Cin = (int)Cin;
     p.Hout = (int)Hin; p.Wout = (int)Win; p.Cout = (int)Cout; p.ntaps = 4;          // the tile walks the LOW-resolution grid
-    p.stride = 1; p.up = 0; p.wrap = wrap ? 1 : 0; p.x_off = 0; p.y_off = 0; p.imgs_per_temb = 1;
+    p.stride = 1; p.wrap = wrap ? 1 : 0; p.imgs_per_temb = 1;
     p.M = N * Hin * Win;
-    p.dbg = 0;
-    hipStream_t s = (hipStream_t)stream;
     ProfScope prof(PROF_CONV, stream);
     const long cout_pad = (Cout + 127) / 128 * 128;
     const size_t esize = 2;
-    const bool big = Cout % 320 == 0 && ((p.M + 255) / 256) * (Cout / 320) >= 512;
-    for (int parity = 0; parity < 4; ++parity) {
-        p.w = (const char*)w4 + (size_t)parity * cout_pad * 4 * Cin * esize;
-        p.up2_py = parity >> 1;
-        p.up2_px = parity & 1;
-        if (big) {
-            constexpr int BM = 256, BN = 320;
-            p.tiles_n = (p.Cout + BN - 1) / BN;
-            p.nblocks = ((p.M + BM - 1) / BM) * p.tiles_n;
-            if (dtype == 0) hipLaunchKernelGGL((conv_igemm_kernel<__bf16, 64, 4, 2, 2, 5, 0, false, false, true>), dim3((unsigned)p.nblocks), dim3(512), 0, s, p);
-            else hipLaunchKernelGGL((conv_igemm_kernel<_Float16, 64, 4, 2, 2, 5, 0, false, false, true>), dim3((unsigned)p.nblocks), dim3(512), 0, s, p);
-        } else {
-            constexpr int BM = 128, BN = 128;
-            p.tiles_n = (p.Cout + BN - 1) / BN;
-            p.nblocks = ((p.M + BM - 1) / BM) * p.tiles_n;
-            if (dtype == 0) hipLaunchKernelGGL((conv_igemm_kernel<__bf16, 64, 2, 2, 2, 2, 0, false, false, true>), dim3((unsigned)p.nblocks), dim3(256), 0, s, p);
-            else hipLaunchKernelGGL((conv_igemm_kernel<_Float16, 64, 2, 2, 2, 2, 0, false, false, true>), dim3((unsigned)p.nblocks), dim3(256), 0, s, p);
+    const bool big = Cout % 320 == 0 && big_tile_count(p.M, Cout) >= BIG_TILE_MIN;
+    // the UP2 kernels of the two convolution tiles, launched directly: no knob applies to them
+    auto launch = [&](auto t, auto tile) {
+        using Tile = decltype(tile);
+        p.tiles_n = (p.Cout + Tile::BN - 1) / Tile::BN;
+        p.nblocks = ((p.M + Tile::BM - 1) / Tile::BM) * p.tiles_n;
+        hipLaunchKernelGGL((conv_igemm_kernel<typename decltype(t)::type, 64, Tile::WM, Tile::WN, Tile::TM, Tile::TN, 0, false, false, true>),
+                           dim3((unsigned)p.nblocks), dim3(Tile::NT), 0, (hipStream_t)stream, p);
+    };
+    return with_dtype(dtype, "conv_up2_fwd", [&](auto t) {
+        for (int parity = 0; parity < 4; ++parity) {
+            p.w = (const char*)w4 + (size_t)parity * cout_pad * 4 * Cin * esize;
+            p.up2_py = parity >> 1;
+            p.up2_px = parity & 1;
+            if (big) launch(t, Tile256x320{});
+            else launch(t, Tile128x128{});
+            IM360_CHECK_LAUNCH();
         }
-        IM360_CHECK_LAUNCH();
-    }
-    return IM360_OK;
+        return IM360_OK;
+    });
 }
 
 extern "C" __attribute__((visibility("default"))) int im360_linear_geglu(const void* x, const void* w_packed, const void* bias_packed, void* y,
@@ -2137,34 +2082,20 @@ extern "C" __attribute__((visibility("default"))) int im360_linear_geglu(const v
     IM360_CHECK_ARG(I > 0 && (I % 128) == 0, "linear_geglu: I=%ld must be a positive multiple of 128", (long)I);
     IM360_CHECK_ARG(((uintptr_t)x % 16) == 0 && ((uintptr_t)w_packed % 16) == 0 && ((uintptr_t)y % 16) == 0 &&
                     ((uintptr_t)bias_packed % 8) == 0, "linear_geglu: misaligned pointer");
-    ConvParams p = conv_params_zero();
-    p.x = x; p.w = w_packed; p.bias = bias_packed; p.temb = nullptr; p.res = nullptr; p.y = y;
-    p.N = (int)M; p.Hin = 1; p.Win = 1; p.Cin = (int)K; p.Hout = 1; p.Wout = 1; p.Cout = (int)(2 * I); p.ntaps = 1;
-    p.stride = 1; p.up = 0; p.wrap = 0; p.x_off = 0; p.y_off = 0; p.imgs_per_temb = 1;
-    p.M = M;
+    ConvParams p = linear_params(x, w_packed, y, M, K, 2 * I);
+    p.bias = bias_packed;
     IM360_CHECK_ARG(M <= 0x7fffffffL, "linear_geglu: M too large");
-    hipStream_t s = (hipStream_t)stream;
     ProfScope prof(PROF_GEMM, stream);
-#ifdef IM360_ABLATE
-    if (knob(KNOB_CONV_BIG) == 3) {            // A/B: 128 x 256 tiles, two 4-wave workgroups per CU (one's GELU epilogue under the other's K loop)
-        if (dtype == 0) return launch_conv_t<__bf16, 2, 2, 2, 4, 1>(p, s);
-        if (dtype == 1) return launch_conv_t<_Float16, 2, 2, 2, 4, 1>(p, s);
-    }
-#endif
-    // the four-wave register-staged tile: knob g4 bit 0 (or, A/B tools, conv_ring 12)
-    if (((knob(KNOB_G4) & 1) || knob(KNOB_CONV_RING) == 12) && (K % 64) == 0 && K >= 128 && (M % 256) == 0 && ((2 * I) % 256) == 0 && (M / 256) * (2 * I / 256) >= 256)
-        return dtype == 0 ? launch_g4_t<__bf16, 1>(p, s) : launch_g4_t<_Float16, 1>(p, s);
-    if (((knob(KNOB_G4) & 4) || knob(KNOB_CONV_RING) == 13) && (K % 64) == 0 && K >= 128 && (M % 256) == 0 && (M / 256) * (2 * I / 128) >= 512)       // the same loop, two workgroups per CU (256 x 128 tiles): knob g4 bit 2
-        return dtype == 0 ? launch_g4b_t<__bf16, 1>(p, s) : launch_g4b_t<_Float16, 1>(p, s);
-    if (knob(KNOB_CONV_RING) && ((M + 255) / 256) * (2 * I / 256) >= 512) {
-        const int v = knob(KNOB_CONV_RING) == 5 ? 1 : (knob(KNOB_CONV_RING) == 7 ? 6 : knob(KNOB_CONV_RING));      // (5 / 7: the ring kernel for the convolutions too)
-        if (dtype == 0) return launch_ring_t<__bf16, 4, 1, true>(p, s, v);
-        if (dtype == 1) return launch_ring_t<_Float16, 4, 1, true>(p, s, v);
-    }
-    if (dtype == 0) return launch_conv_t<__bf16, 4, 2, 2, 4, 1>(p, s);
-    if (dtype == 1) return launch_conv_t<_Float16, 4, 2, 2, 4, 1>(p, s);
-    im360_set_error("linear_geglu: dtype %d unsupported", dtype);
-    return IM360_ERR_UNSUPPORTED;
+    return with_dtype(dtype, "linear_geglu", [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipStream_t s = (hipStream_t)stream;
+        if (int rc; ablate_geglu<T>(p, s, rc)) return rc;
+        if (g4_fits(G4_GEGLU, M, K, 2 * I, false)) return launch_g4_t<T, 1>(p, s);
+        if (g4_fits(G4_GEGLU_NARROW, M, K, 2 * I, true)) return launch_g4b_t<T, 1>(p, s);
+        const RingKnob ring = ring_knob();
+        if (ring.on() && ((M + 255) / 256) * (2 * I / 256) >= BIG_TILE_MIN) return launch_ring_t<T, 4, 1, true>(p, s, ring.loop());
+        return launch_conv_t<T, TileGeglu256x256, 1>(p, s);
+    });
 }
 
 // 1x1 convolution of the channel concatenation [xa | xb] that is never materialised (the skip connections of the decoder:
@@ -2188,7 +2119,7 @@ extern "C" __attribute__((visibility("default"))) int im360_conv1x1_cat_fwd(cons
     p.stride = 1; p.imgs_per_temb = 1;
     p.M = N * H * W;
     ProfScope prof(PROF_CONV, stream);
-    return dtype == 0 ? launch_conv<__bf16>(p, (hipStream_t)stream) : launch_conv<_Float16>(p, (hipStream_t)stream);
+    return with_dtype(dtype, "conv1x1_cat_fwd", [&](auto t) { return launch_conv<typename decltype(t)::type>(p, (hipStream_t)stream); });
 }
 
 // Token-major Linear y[M, N] = x[M, K] w^T + bias (+ res) on the persistent ring kernel (N % 320 == 0, K % 32 == 0), with
@@ -2205,19 +2136,16 @@ extern "C" __attribute__((visibility("default"))) int im360_linear_fwd(const voi
     IM360_CHECK_ARG(((uintptr_t)x % 16) == 0 && ((uintptr_t)w_packed % 16) == 0 && ((uintptr_t)y % 16) == 0 &&
                     ((uintptr_t)res % 16) == 0 && ((uintptr_t)bias % 8) == 0 && ((uintptr_t)rowstats % 8) == 0, "linear_fwd: misaligned pointer");
     IM360_CHECK_ARG(dtype == 0 || dtype == 1, "linear_fwd: dtype %d unsupported", dtype);
-    ConvParams p = conv_params_zero();
-    p.x = x; p.w = w_packed; p.bias = bias; p.res = res; p.y = y; p.rs_out = (float*)rowstats;
-    p.N = (int)M; p.Hin = 1; p.Win = 1; p.Cin = (int)K; p.Hout = 1; p.Wout = 1; p.Cout = (int)N; p.ntaps = 1;
-    p.stride = 1; p.imgs_per_temb = 1;
-    p.M = M;
+    ConvParams p = linear_params(x, w_packed, y, M, K, N);
+    p.bias = bias; p.res = res; p.rs_out = (float*)rowstats;
     IM360_CHECK_ARG(!gn_partial || ((M % 256) == 0 && (K % 64) == 0), "linear_fwd: GroupNorm statistics need M %% 256 == 0 and K %% 64 == 0");
     p.gn_out = (float*)gn_partial;          // (per 256-row tile: the caller's images are whole numbers of tiles)
-    hipStream_t s = (hipStream_t)stream;
     ProfScope prof(PROF_GEMM, stream);
-    const int kr = knob(KNOB_CONV_RING);
-    const int v = kr == 5 ? 1 : (kr == 7 ? 6 : kr);
-    if (rowstats) return dtype == 0 ? launch_ring_t<__bf16, 5, 5, true>(p, s, (v == 8 || v == 10 || v == 11) ? v : 1) : launch_ring_t<_Float16, 5, 5, true>(p, s, (v == 8 || v == 10 || v == 11) ? v : 1);
-    return dtype == 0 ? launch_ring_t<__bf16, 5, 2, true>(p, s, v) : launch_ring_t<_Float16, 5, 2, true>(p, s, v);
+    return with_dtype(dtype, "linear_fwd", [&](auto t) {
+        using T = typename decltype(t)::type;
+        if (rowstats) return launch_ring_t<T, 5, 5, true>(p, (hipStream_t)stream, ring_knob().ln_loop());
+        return launch_ring_t<T, 5, 2, true>(p, (hipStream_t)stream, ring_knob().loop());
+    });
 }
 
 // LayerNorm folded into the consuming Linear: x are the RAW rows, w_packed = pack(gamma (.) W), and with the rows'
@@ -2238,17 +2166,12 @@ extern "C" __attribute__((visibility("default"))) int im360_linear_ln_fwd(const 
     IM360_CHECK_ARG(((uintptr_t)x % 16) == 0 && ((uintptr_t)w_packed % 16) == 0 && ((uintptr_t)y % 16) == 0 && ((uintptr_t)c1 % 16) == 0 &&
                     ((uintptr_t)c2 % 16) == 0 && ((uintptr_t)tab % 16) == 0 && ((uintptr_t)rowstats % 8) == 0, "linear_ln_fwd: misaligned pointer");
     IM360_CHECK_ARG(dtype == 0 || dtype == 1, "linear_ln_fwd: dtype %d unsupported", dtype);
-    ConvParams p = conv_params_zero();
-    p.x = x; p.w = w_packed; p.y = y;
+    ConvParams p = linear_params(x, w_packed, y, M, K, N);
     p.rs_in = (const float*)rowstats; p.rs_p = (int)rs_p; p.ln_eps = eps; p.ln_invc = 1.0f / (float)K;
-    p.ln_c1 = (const float*)c1; p.ln_c2 = (const float*)c2; p.ln_tab = (const float*)tab;
-    p.tab_div = tab ? (int)tab_div : 1; p.tab_mod = tab ? (int)tab_mod : 1;
-    p.N = (int)M; p.Hin = 1; p.Win = 1; p.Cin = (int)K; p.Hout = 1; p.Wout = 1; p.Cout = (int)N; p.ntaps = 1;
-    p.stride = 1; p.imgs_per_temb = 1;
-    p.M = M;
+    p.ln_c1 = (const float*)c1; p.ln_c2 = (const float*)c2;
+    p.ln_tab = (const float*)tab; p.tab_div = tab ? (int)tab_div : 1; p.tab_mod = tab ? (int)tab_mod : 1;
     ProfScope prof(PROF_GEMM, stream);
-    const int v6 = (knob(KNOB_CONV_RING) == 8 || knob(KNOB_CONV_RING) == 10 || knob(KNOB_CONV_RING) == 11) ? knob(KNOB_CONV_RING) : 1;
-    return dtype == 0 ? launch_ring_t<__bf16, 5, 3, true>(p, (hipStream_t)stream, v6) : launch_ring_t<_Float16, 5, 3, true>(p, (hipStream_t)stream, v6);
+    return with_dtype(dtype, "linear_ln_fwd", [&](auto t) { return launch_ring_t<typename decltype(t)::type, 5, 3, true>(p, (hipStream_t)stream, ring_knob().ln_loop()); });
 }
 
 // LayerNorm folded into the fused GEGLU projection (im360_linear_geglu with w_packed = pack_geglu(gamma (.) W) and the
@@ -2264,20 +2187,17 @@ extern "C" __attribute__((visibility("default"))) int im360_linear_geglu_ln(cons
     IM360_CHECK_ARG(((uintptr_t)x % 16) == 0 && ((uintptr_t)w_packed % 16) == 0 && ((uintptr_t)y % 16) == 0 && ((uintptr_t)c1 % 16) == 0 &&
                     ((uintptr_t)c2 % 16) == 0 && ((uintptr_t)rowstats % 8) == 0, "linear_geglu_ln: misaligned pointer");
     IM360_CHECK_ARG(dtype == 0 || dtype == 1, "linear_geglu_ln: dtype %d unsupported", dtype);
-    ConvParams p = conv_params_zero();
-    p.x = x; p.w = w_packed; p.y = y;
+    ConvParams p = linear_params(x, w_packed, y, M, K, 2 * I);
     p.rs_in = (const float*)rowstats; p.rs_p = (int)rs_p; p.ln_eps = eps; p.ln_invc = 1.0f / (float)K;
     p.ln_c1 = (const float*)c1; p.ln_c2 = (const float*)c2;
-    p.N = (int)M; p.Hin = 1; p.Win = 1; p.Cin = (int)K; p.Hout = 1; p.Wout = 1; p.Cout = (int)(2 * I); p.ntaps = 1;
-    p.stride = 1; p.imgs_per_temb = 1;
-    p.M = M;
     ProfScope prof(PROF_GEMM, stream);
-    if (((knob(KNOB_G4) & 2) || knob(KNOB_CONV_RING) == 12) && (K % 64) == 0 && K >= 128 && (M % 256) == 0 && ((2 * I) % 256) == 0 && (M / 256) * (2 * I / 256) >= 256)       // knob g4 bit 1
-        return dtype == 0 ? launch_g4_t<__bf16, 4>(p, (hipStream_t)stream) : launch_g4_t<_Float16, 4>(p, (hipStream_t)stream);
-    if (((knob(KNOB_G4) & 8) || knob(KNOB_CONV_RING) == 13) && (K % 64) == 0 && K >= 128 && (M % 256) == 0 && (M / 256) * (2 * I / 128) >= 512)       // knob g4 bit 3
-        return dtype == 0 ? launch_g4b_t<__bf16, 4>(p, (hipStream_t)stream) : launch_g4b_t<_Float16, 4>(p, (hipStream_t)stream);
-    const int v6 = (knob(KNOB_CONV_RING) == 8 || knob(KNOB_CONV_RING) == 10 || knob(KNOB_CONV_RING) == 11) ? knob(KNOB_CONV_RING) : 1;
-    return dtype == 0 ? launch_ring_t<__bf16, 4, 4, true>(p, (hipStream_t)stream, v6) : launch_ring_t<_Float16, 4, 4, true>(p, (hipStream_t)stream, v6);
+    return with_dtype(dtype, "linear_geglu_ln", [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipStream_t s = (hipStream_t)stream;
+        if (g4_fits(G4_GEGLU_LN, M, K, 2 * I, false)) return launch_g4_t<T, 4>(p, s);
+        if (g4_fits(G4_GEGLU_LN_NARROW, M, K, 2 * I, true)) return launch_g4b_t<T, 4>(p, s);
+        return launch_ring_t<T, 4, 4, true>(p, s, ring_knob().ln_loop());
+    });
 }
 
 extern "C" __attribute__((visibility("default"))) int im360_pack_conv_weight(const void* w, void* out, int64_t Cout, int64_t Cin, int64_t taps,
@@ -2288,17 +2208,11 @@ extern "C" __attribute__((visibility("default"))) int im360_pack_conv_weight(con
                     "pack_conv_weight: CoutPad %% 128 and CinPad %% 32 required");
     const long total = CoutPad * taps * CinPad;
     const unsigned blocks = (unsigned)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == 0)
-        hipLaunchKernelGGL((pack_conv_weight_kernel<__bf16>), dim3(blocks), dim3(256), 0, s, (const __bf16*)w, (__bf16*)out,
+    return with_dtype(dtype, "pack_conv_weight", [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((pack_conv_weight_kernel<T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const T*)w, (T*)out,
                            (int)Cout, (int)Cin, (int)taps, (int)CoutPad, (int)CinPad);
-    else if (dtype == 1)
-        hipLaunchKernelGGL((pack_conv_weight_kernel<_Float16>), dim3(blocks), dim3(256), 0, s, (const _Float16*)w,
-                           (_Float16*)out, (int)Cout, (int)Cin, (int)taps, (int)CoutPad, (int)CinPad);
-    else {
-        im360_set_error("pack_conv_weight: dtype %d unsupported", dtype);
-        return IM360_ERR_UNSUPPORTED;
-    }
-    IM360_CHECK_LAUNCH();
-    return IM360_OK;
+        IM360_CHECK_LAUNCH();
+        return IM360_OK;
+    });
 }

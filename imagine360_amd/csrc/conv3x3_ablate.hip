@@ -1,9 +1,11 @@
-// Ablation-only kernels of the convolution / GEMM family: compiled ONLY into `make ablate` builds (-DIM360_ABLATE), by inclusion
-// from conv3x3.hip INSIDE its `namespace im360` (that file defines ConvParams, tile_epilogue, the LDS-DMA helpers and the launch
-// plumbing used here).  Compiled on its own this file is an empty translation unit.  Both kernels are measured-and-rejected A/B
+// Ablation-only kernels and launch rules of the convolution / GEMM family: compiled ONLY into `make ablate` builds (-DIM360_ABLATE), by
+// inclusion from conv3x3.hip INSIDE its `namespace im360` (that file defines ConvParams, tile_epilogue, the LDS-DMA helpers, the tiles and
+// the launch plumbing used here); the default build gets the four ablate_*() launch hooks at the end as constant false.  Compiled on its
+// own this file is an empty translation unit.  Both kernels are measured-and-rejected A/B
 // variants: gemm_a3_kernel (identical results, 0.85 - 0.97 x the staggered loop, profiles/r04_gemm_a3_ab.log) and conv_halo_kernel
 // (a different fp32 summation order, 4 - 30 % slower than the two-stage kernel, profiles/r02_ab_conv_halo.log); DESIGN.md section 3d.
-#if defined(IM360_ABLATE) && defined(IM360_CONV3X3_INCLUDES_ABLATE)
+#ifdef IM360_CONV3X3_INCLUDES_ABLATE
+#ifdef IM360_ABLATE
 
 // ---- token-major GEMM with TWO activation stages in flight ("A3", round 4, knob conv_ring 10) -----------------------------
 // The staggered loop above holds two 64-channel stages of both operands, so ONE is in flight while the other is consumed, and a
@@ -527,21 +529,134 @@ static bool halo_geometry(ConvParams& p) {
     return true;
 }
 
+static int check_launch() { IM360_CHECK_LAUNCH(); return IM360_OK; }
+static bool launched(int& rc) { rc = check_launch(); return true; }
+
 template <typename T>
 static int launch_halo(ConvParams p, hipStream_t stream) {
     p.tiles_n = p.Cout / 320;
     p.nblocks = (p.M / 256) * p.tiles_n;
     p.dbg = 0;
-    static const int ncu = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 256;
-        return n >= 8 ? n / 8 * 8 : 8;
-    }();
-    const long want = (p.nblocks + 7) / 8 * 8;
-    const unsigned grid = (unsigned)(want < ncu ? want : ncu);
-    hipLaunchKernelGGL((conv_halo_kernel<T>), dim3(grid), dim3(512), 0, stream, p);
-    IM360_CHECK_LAUNCH();
-    return IM360_OK;
+    hipLaunchKernelGGL((conv_halo_kernel<T>), dim3(persistent_grid(p.nblocks)), dim3(512), 0, stream, p);
+    return check_launch();
 }
 
-#endif  // IM360_ABLATE && IM360_CONV3X3_INCLUDES_ABLATE
+// ---- "does an ablation variant take this launch?" -- asked by every launcher of conv3x3.hip in front of its shipped path; true: launched (or failed), status in rc
+// launch_conv_t: p.dbg, cm (taps innermost applies) and the grid fields are set
+template <typename T, typename Tile, int EPI>
+static bool ablate_conv_t(const ConvParams& p, hipStream_t stream, bool cm, int& rc) {
+    constexpr int WM = Tile::WM, WN = Tile::WN, TM = Tile::TM, TN = Tile::TN, NT = Tile::NT;
+    const dim3 grid((unsigned)p.nblocks);
+    if constexpr ((std::is_same<Tile, Tile256x320>::value || std::is_same<Tile, Tile192x320>::value) && EPI == 0) {
+        if (p.dbg && p.Cin % 64 == 0) {         // ablation build of the 256 x 320 conv tile (results are garbage)
+            with_bool(cm, [&](auto c) { hipLaunchKernelGGL((conv_igemm_kernel<T, 64, WM, WN, TM, TN, EPI, decltype(c)::value, true>), grid, dim3(NT), 0, stream, p); });
+            return launched(rc);
+        }
+    }
+    if constexpr (Tile::big && EPI == 0) {
+        // staggered wave groups on this kernel's producer (round 4; knob conv_stag): identical bits, 0.97 - 1.05 x the plain loop's
+        // speed on the nine cfg2 convolution shapes (profiles/r04_conv_stag_ab.log) -- with two stage buffers a step's operands have
+        // one step to arrive either way, and that latency, not the fragment reads the stagger hides, is what the loop waits for
+        if (knob(KNOB_CONV_STAG) && p.Cin % 64 == 0 && knob(KNOB_CONV_BK) != 32) {
+            with_bool(p.gn_out != nullptr, [&](auto gns) { with_bool(cm, [&](auto c) {
+                hipLaunchKernelGGL((conv_igemm_kernel<T, 64, WM, WN, TM, TN, EPI, decltype(c)::value, false, false, decltype(gns)::value, true>), grid, dim3(NT), 0, stream, p);
+            }); });
+            return launched(rc);
+        }
+    }
+    return false;
+}
+
+// launch_ring_t: p.dbg, the grid and the cout groups are set; stag = the loop `variant` puts this launch on the staggered loop
+template <typename T, int TN, int EPI, bool LINEAR>
+static bool ablate_ring_t(const ConvParams& p, hipStream_t stream, int variant, unsigned grid_n, bool stag, int& rc) {
+    const dim3 grid(grid_n), block(512);
+    constexpr bool has_gns = LINEAR && TN == 5 && (EPI == 2 || EPI == 5);
+    if constexpr (!LINEAR && TN == 5 && EPI == 0) {
+        if (variant == RING_CONV_CM) {          // 3 x 3 convolution, taps innermost, on the plain 64-channel loop in the persistent shell (the caller checked that the order applies)
+            with_bool(p.gn_out != nullptr, [&](auto gns) { with_const<1, 2>(p.res ? 1 : 2, [&](auto resm) {
+                hipLaunchKernelGGL((conv_ring_kernel<T, TN, EPI, LINEAR, true, 4 + 128, decltype(gns)::value, decltype(resm)::value>), grid, block, 0, stream, p);
+            }); });
+            return launched(rc);
+        }
+    }
+    if (p.gn_out && !has_gns) return false;     // (the launcher's error)
+    if (!p.gn_out) {
+        if constexpr (LINEAR && TN == 5 && EPI == 2) {
+            if (stag && p.dbg) {                    // ablation builds of the staggered loop (tools/ab_stag.py --ablate)
+                with_const<1, 2, 3, 4, 5, 6, 7>(p.dbg & 7, [&](auto a) { hipLaunchKernelGGL((conv_ring_kernel<T, TN, EPI, LINEAR, true, 3 + 16 * decltype(a)::value>), grid, block, 0, stream, p); });
+                return launched(rc);
+            }
+        }
+        if constexpr (EPI < 3) {
+            if (variant == RING_DMA_BUILTIN) hipLaunchKernelGGL((conv_ring_kernel<T, TN, EPI, LINEAR, false, 0>), grid, block, 0, stream, p);
+            else if (variant == RING_DMA_ASM) hipLaunchKernelGGL((conv_ring_kernel<T, TN, EPI, LINEAR, true, 0>), grid, block, 0, stream, p);
+            else if (variant == RING_STAG_RING) hipLaunchKernelGGL((conv_ring_kernel<T, TN, EPI, LINEAR, true, 1>), grid, block, 0, stream, p);
+            if (variant == RING_DMA_BUILTIN || variant == RING_DMA_ASM || variant == RING_STAG_RING) return launched(rc);
+        }
+    }
+    // measured and not shipped (profiles/r04_gemm_a3_ab.log): identical bits on every shape and epilogue at the first run, but
+    // 0.85 - 0.97 x the staggered loop's speed (only the level-0 GEGLU ties): with the weight tile in 64-byte row segments the
+    // L2 -> LDS path carries 2170 clk of transfers per stage instead of 1385, and that path's throughput -- not only the latency
+    // of the activation rows -- is what the K loop runs against
+    if constexpr (LINEAR && EPI != 3) {             // (EPI 3's two sets of c1 | c2 do not fit next to the A3 kernel's 156 KB)
+        // two activation stages in flight (gemm_a3_kernel); RING_A3_BCM: the same with a CHUNK-MAJOR weight operand (the caller repacked it: kernels.chunk_major)
+        if (stag && (variant == RING_A3 || variant == RING_A3_BCM)) {
+            with_bool(has_gns && p.gn_out, [&](auto gns) { with_bool(variant == RING_A3_BCM, [&](auto bcm) { with_resm<EPI>(p, [&](auto resm) {
+                hipLaunchKernelGGL((gemm_a3_kernel<T, TN, EPI, has_gns && decltype(gns)::value, decltype(resm)::value, decltype(bcm)::value>), grid, block, 0, stream, p);
+            }); }); });
+            return launched(rc);
+        }
+    }
+    // (3x3 convolutions on the staggered loop: 27 spilled registers, 0.90 - 1.13 PF/s against the two-stage kernel's 1.05 - 1.16)
+    if constexpr (!LINEAR) {
+        if (stag) {
+            hipLaunchKernelGGL((conv_ring_kernel<T, TN, EPI, LINEAR, true, 3>), grid, block, 0, stream, p);
+            return launched(rc);
+        }
+    }
+    return false;
+}
+
+// launch_conv, a launch that fills 256 x 320 tiles
+template <typename T>
+static bool ablate_conv(const ConvParams& p, hipStream_t stream, bool linear, int big_env, int& rc) {
+    if (knob(KNOB_CONV_HALO)) {
+        ConvParams ph = p;
+        if (halo_geometry(ph)) { rc = launch_halo<T>(ph, stream); return true; }
+    }
+    // A/B: 128 x 320, 2 workgroups per CU
+    if (big_env == 2) { rc = linear ? launch_conv_t<T, Tile128x320, 2>(p, stream) : launch_conv_t<T, Tile128x320>(p, stream); return true; }
+    // A/B: the same 256 x 320 tile on FOUR waves (128 x 160 each, 320 accumulators in the unified 512-register file, one
+    // wave per SIMD): 144 instead of 224 KB of fragment reads per K step
+    if (big_env == 4 && !linear) { rc = launch_conv_t<T, Tile192x320>(p, stream); return true; }
+    // round 4, measured and not shipped: 3 x 3 convolutions with the taps innermost on the PERSISTENT kernel (next tile's first
+    // stage requested under the epilogue, no workgroup turnover between tiles; knob conv_persist).  Identical bits on nine
+    // shapes incl. stride 2 and the statistics epilogue.  First form 0.93 - 1.04 x conv_igemm_kernel's speed: hipcc kept the 64-bit
+    // tap / chunk offsets in VGPR pairs, spilled one and reloaded it inside the K loop -- a scratch reload is a VMEM load whose
+    // wait also waits for the stage requested in front of it.  With the offsets 32-bit and pinned to SGPRs the loop is clean and
+    // the kernel TIES: 0.96 - 1.05 x (profiles/r04_conv_persist_ab.log) -- workgroup turnover is not what the convolutions lose.
+    if (knob(KNOB_CONV_PERSIST) && !linear && knob(KNOB_CONV_CM) && p.ntaps == 9 && !p.wrap && !p.up && !p.x2 && p.Cin % 64 == 0 && knob(KNOB_CONV_BK) != 32 && p.M <= 0x7fffffffL) {
+        rc = launch_ring_t<T, 5, 0, false>(p, stream, RING_CONV_CM);
+        return true;
+    }
+    return false;
+}
+
+// im360_linear_geglu.  A/B: 128 x 256 tiles, two 4-wave workgroups per CU (one's GELU epilogue under the other's K loop)
+template <typename T>
+static bool ablate_geglu(const ConvParams& p, hipStream_t stream, int& rc) {
+    if (knob(KNOB_CONV_BIG) != 3) return false;
+    rc = launch_conv_t<T, Tile128x256, 1>(p, stream);
+    return true;
+}
+
+#else   // the default build has no ablation variants
+
+template <typename T, typename Tile, int EPI> static bool ablate_conv_t(const ConvParams&, hipStream_t, bool, int&) { return false; }
+template <typename T, int TN, int EPI, bool LINEAR> static bool ablate_ring_t(const ConvParams&, hipStream_t, int, unsigned, bool, int&) { return false; }
+template <typename T> static bool ablate_conv(const ConvParams&, hipStream_t, bool, int, int&) { return false; }
+template <typename T> static bool ablate_geglu(const ConvParams&, hipStream_t, int&) { return false; }
+
+#endif  // IM360_ABLATE
+#endif  // IM360_CONV3X3_INCLUDES_ABLATE

@@ -568,25 +568,8 @@ static int launch_g4b_t(ConvParams p, hipStream_t stream) {
         im360_set_error("gemm_g4b: unsupported shape");
         return IM360_ERR_ARG;
     }
-    static const int ncu = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 256;
-        return n >= 8 ? n / 8 * 8 : 8;
-    }();
-    const long want = (p.nblocks + 7) / 8 * 8;
-    const unsigned grid = (unsigned)(want < 2L * ncu ? want : 2L * ncu);      // two workgroups per CU
-    {
-        const long wbytes = (long)p.tiles_n * BN * p.Cin * 2;
-        int ng = 1;
-        const int force = knob(KNOB_RING_GROUPS);
-        if (force > 0) {
-            if ((force == 2 || force == 4 || force == 8) && p.tiles_n % force == 0) ng = force;
-        } else {
-            while (ng < 8 && wbytes / ng > 3400000L && p.tiles_n % (2 * ng) == 0) ng *= 2;
-            if (wbytes / ng > 3400000L) ng = 1;
-        }
-        p.ngroups = grid >= 8u * ng ? ng : 1;
-    }
+    const unsigned grid = persistent_grid(p.nblocks, 2);      // two workgroups per CU
+    p.ngroups = ring_groups((long)p.tiles_n * BN * p.Cin * 2, p.tiles_n, grid);
     hipLaunchKernelGGL((gemm_g4b_kernel<T, EPI>), dim3(grid), dim3(256), 0, stream, p);
     IM360_CHECK_LAUNCH();
     return IM360_OK;
@@ -601,38 +584,22 @@ static int launch_g4_t(ConvParams p, hipStream_t stream) {
         im360_set_error("gemm_g4: unsupported shape");
         return IM360_ERR_ARG;
     }
-    static const int ncu = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 256;
-        return n >= 8 ? n / 8 * 8 : 8;
-    }();
-    const long want = (p.nblocks + 7) / 8 * 8;
-    const unsigned grid = (unsigned)(want < ncu ? want : ncu);
-    {
-        const long wbytes = (long)p.tiles_n * BN * p.Cin * 2;
-        int ng = 1;
-        const int force = knob(KNOB_RING_GROUPS);
-        if (force > 0) {
-            if ((force == 2 || force == 4 || force == 8) && p.tiles_n % force == 0) ng = force;
-        } else {
-            while (ng < 8 && wbytes / ng > 3400000L && p.tiles_n % (2 * ng) == 0) ng *= 2;
-            if (wbytes / ng > 3400000L) ng = 1;
-        }
-        p.ngroups = grid >= 8u * ng ? ng : 1;
-    }
+    const unsigned grid = persistent_grid(p.nblocks);
+    p.ngroups = ring_groups((long)p.tiles_n * BN * p.Cin * 2, p.tiles_n, grid);
     const bool odd = ((p.Cin / 64) & 1) != 0;
     static_assert(EPI == 1 || EPI == 4, "built for the fused GEGLU epilogues (the plain epilogue on this tile was measured 7 - 33 % slower than the 256 x 320 loop: profiles/r06_g4_first_ab.log)");
 #ifdef IM360_G4_ABL
     if constexpr (EPI == 1 && std::is_same<T, __bf16>::value) {
         // ablation / cycle-stamp builds (make CXXFLAGS+=-DIM360_G4_ABL; tools/g4_stamps.py, knob conv_dbg): 16 = stamps, +1 no stream, +8 no epilogue
-        const int dbg = knob(KNOB_CONV_DBG);
-#define IM360_G4_CASE(a) if (dbg == a) { if (odd) hipLaunchKernelGGL((gemm_g4_kernel<T, EPI, true, 0, a>), dim3(grid), dim3(256), 0, stream, p); else hipLaunchKernelGGL((gemm_g4_kernel<T, EPI, false, 0, a>), dim3(grid), dim3(256), 0, stream, p); IM360_CHECK_LAUNCH(); return IM360_OK; }
-        IM360_G4_CASE(16) IM360_G4_CASE(17) IM360_G4_CASE(25)
-#undef IM360_G4_CASE
+        if (with_const<16, 17, 25>(knob(KNOB_CONV_DBG), [&](auto a) {
+                with_bool(odd, [&](auto o) { hipLaunchKernelGGL((gemm_g4_kernel<T, EPI, decltype(o)::value, 0, decltype(a)::value>), dim3(grid), dim3(256), 0, stream, p); });
+            })) {
+            IM360_CHECK_LAUNCH();
+            return IM360_OK;
+        }
     }
 #endif
-    if (odd) hipLaunchKernelGGL((gemm_g4_kernel<T, EPI, true, 0>), dim3(grid), dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL((gemm_g4_kernel<T, EPI, false, 0>), dim3(grid), dim3(256), 0, stream, p);
+    with_bool(odd, [&](auto o) { hipLaunchKernelGGL((gemm_g4_kernel<T, EPI, decltype(o)::value, 0>), dim3(grid), dim3(256), 0, stream, p); });
     IM360_CHECK_LAUNCH();
     return IM360_OK;
 }

@@ -953,28 +953,24 @@ extern "C" __attribute__((visibility("default"))) int im360_groupnorm_apply_part
     // output is hundreds of MB that the next kernel streams once), 1 / 3 = the same with eight loads in flight (ties), 6 = non-temporal loads too
     const int v = knob(KNOB_GN_APPLY);
     hipStream_t s = (hipStream_t)stream;
-#define IM360_GN_AP(T, NLD, NTS, NTL) hipLaunchKernelGGL((gn_apply_p_kernel<T, NLD, NTS, NTL>), dim3(S, (unsigned)N), dim3(256), dyn, s, (const T*)xa, (const T*)xb, (int)C1, (int)C2, \
-        (const float*)pa, (int)Sa, (const float*)pb, (int)Sb, (const T*)gamma, (const T*)beta, (T*)y, (int)H, (int)W, (int)G, (int)pad, act, S, eps)
-    if (dtype == 0) {
+    auto launch = [&](auto t, auto nld, auto nts, auto ntl) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((gn_apply_p_kernel<T, decltype(nld)::value, decltype(nts)::value, decltype(ntl)::value>), dim3(S, (unsigned)N), dim3(256), dyn, s, (const T*)xa, (const T*)xb, (int)C1, (int)C2,
+                           (const float*)pa, (int)Sa, (const float*)pb, (int)Sb, (const T*)gamma, (const T*)beta, (T*)y, (int)H, (int)W, (int)G, (int)pad, act, S, eps);
+    };
+    using I4 = std::integral_constant<int, 4>;
+    using I8 = std::integral_constant<int, 8>;
+    return with_dtype(dtype, "groupnorm_apply_partials", [&](auto t) {
         switch (v & 7) {
-            case 0: IM360_GN_AP(__bf16, 4, false, false); break;
-            case 1: IM360_GN_AP(__bf16, 8, false, false); break;
-            case 3: IM360_GN_AP(__bf16, 8, true, false); break;
-            case 6: IM360_GN_AP(__bf16, 4, true, true); break;
-            default: IM360_GN_AP(__bf16, 4, true, false); break;
+            case 0: launch(t, I4{}, std::false_type{}, std::false_type{}); break;
+            case 1: launch(t, I8{}, std::false_type{}, std::false_type{}); break;
+            case 3: launch(t, I8{}, std::true_type{}, std::false_type{}); break;
+            case 6: launch(t, I4{}, std::true_type{}, std::true_type{}); break;
+            default: launch(t, I4{}, std::true_type{}, std::false_type{}); break;
         }
-    } else {
-        switch (v & 7) {
-            case 0: IM360_GN_AP(_Float16, 4, false, false); break;
-            case 1: IM360_GN_AP(_Float16, 8, false, false); break;
-            case 3: IM360_GN_AP(_Float16, 8, true, false); break;
-            case 6: IM360_GN_AP(_Float16, 4, true, true); break;
-            default: IM360_GN_AP(_Float16, 4, true, false); break;
-        }
-    }
-#undef IM360_GN_AP
-    IM360_CHECK_LAUNCH();
-    return IM360_OK;
+        IM360_CHECK_LAUNCH();
+        return IM360_OK;
+    });
 }
 
 // GroupNorm (+ SiLU, + circular W pad, on x or on the never-materialised concatenation [xa | xb]) in ONE launch: statistics,
@@ -1102,19 +1098,14 @@ extern "C" __attribute__((visibility("default"))) int im360_cfg_ddim_step(const 
     const long n8 = n / 8;
     const unsigned blocks = (unsigned)((n8 + 255) / 256 > 4096 ? 4096 : (n8 + 255) / 256);
     hipStream_t s = (hipStream_t)stream;
-#define IM360_DDIM_STEP(T)                                                                                              \
-    hipLaunchKernelGGL((cfg_ddim_step_kernel<T>), dim3(blocks), dim3(256), 0, s, (const T*)uncond, (const T*)cond,      \
-                       (const T*)x, (const T*)noise, (T*)out, n8, guidance, sqrt_a, sqrt_b, sqrt_a_prev, dir, sigma, mode, \
-                       (const float*)coef_dev)
-    if (dtype == 0) IM360_DDIM_STEP(__bf16);
-    else if (dtype == 1) IM360_DDIM_STEP(_Float16);
-    else {
-        im360_set_error("cfg_ddim_step: dtype %d unsupported", dtype);
-        return IM360_ERR_UNSUPPORTED;
-    }
-#undef IM360_DDIM_STEP
-    IM360_CHECK_LAUNCH();
-    return IM360_OK;
+    return with_dtype(dtype, "cfg_ddim_step", [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((cfg_ddim_step_kernel<T>), dim3(blocks), dim3(256), 0, s, (const T*)uncond, (const T*)cond,
+                           (const T*)x, (const T*)noise, (T*)out, n8, guidance, sqrt_a, sqrt_b, sqrt_a_prev, dir, sigma, mode,
+                           (const float*)coef_dev);
+        IM360_CHECK_LAUNCH();
+        return IM360_OK;
+    });
 }
 
 // The step of im360_cfg_ddim_step on the per-frame weighted blend of nW sliding-window predictions (see the kernel's comment):
@@ -1136,19 +1127,14 @@ extern "C" __attribute__((visibility("default"))) int im360_cfg_ddim_step_window
     const long nv = (long)(outer * F * inner) / (vec ? 8 : 1);
     const unsigned blocks = (unsigned)((nv + 255) / 256 > 4096 ? 4096 : (nv + 255) / 256);
     hipStream_t s = (hipStream_t)stream;
-#define IM360_DDIM_WIN(T, V)                                                                                              \
-    hipLaunchKernelGGL((cfg_ddim_step_windows_kernel<T, V>), dim3(blocks), dim3(256), 0, s, (const T*)pred, (const T*)x,     \
-                       (const T*)noise, (T*)out, (const int*)start, (const float*)weight, nW, (long)outer, (int)F, (int)L,   \
-                       (long)inner, guidance, sqrt_a, sqrt_b, sqrt_a_prev, dir, sigma, mode, (const float*)coef_dev)
-    if (dtype == 0 && vec) IM360_DDIM_WIN(__bf16, 8);
-    else if (dtype == 0) IM360_DDIM_WIN(__bf16, 1);
-    else if (dtype == 1 && vec) IM360_DDIM_WIN(_Float16, 8);
-    else if (dtype == 1) IM360_DDIM_WIN(_Float16, 1);
-    else {
-        im360_set_error("cfg_ddim_step_windows: dtype %d unsupported", dtype);
-        return IM360_ERR_UNSUPPORTED;
-    }
-#undef IM360_DDIM_WIN
-    IM360_CHECK_LAUNCH();
-    return IM360_OK;
+    return with_dtype(dtype, "cfg_ddim_step_windows", [&](auto t) {
+        using T = typename decltype(t)::type;
+        with_const<1, 8>(vec ? 8 : 1, [&](auto v) {
+            hipLaunchKernelGGL((cfg_ddim_step_windows_kernel<T, decltype(v)::value>), dim3(blocks), dim3(256), 0, s, (const T*)pred, (const T*)x,
+                               (const T*)noise, (T*)out, (const int*)start, (const float*)weight, nW, (long)outer, (int)F, (int)L,
+                               (long)inner, guidance, sqrt_a, sqrt_b, sqrt_a_prev, dir, sigma, mode, (const float*)coef_dev);
+        });
+        IM360_CHECK_LAUNCH();
+        return IM360_OK;
+    });
 }
