@@ -7,7 +7,8 @@ coins drawn from Python's RNG in the reference's order) and calls replay().  The
 inside the graph from torch's device generator (graph-safe philox state), like the reference's GPU path.  Stochastic
 sampling (eta > 0) draws the two variance noises inside the graph as well, right before each branch's update, from the
 caller's generator (registered with the graph) or the default one; the coefficients are then (guidance, sqrt a_t,
-sqrt b_t, sqrt a_prev, dir, sigma) for ``cfg_ddim_step``.
+sqrt b_t, sqrt a_prev, dir, sigma) for ``cfg_ddim_step``.  Guidance rescale (``guidance_rescale`` != 0) adds one captured
+statistics launch in front of each branch's step launch; its workspace is a graph-pool tensor and nothing more is uploaded.
 """
 import random
 
@@ -40,7 +41,7 @@ class GraphedDenoiseStep:
     always_step_kernel = False      # (GraphedWindowedStep) the six-coefficient step kernel for eta = 0 as well
 
     def __init__(self, mv, scheduler, inputs, cameras, pano_latent, pers_latent, guidance, use_fps=True, warmup=2, cfg_pair=None,
-                 eta=0.0, generator=None, use_clipped_model_output=False, frame_shard=None):
+                 eta=0.0, generator=None, use_clipped_model_output=False, frame_shard=None, guidance_rescale=0.0):
         """``inputs``: the keyword tensors of MultiViewBaseModel.forward (CFG-batched, resident on the GPU);
         ``pano_latent`` [1,4,F,H,W] / ``pers_latent`` [1,m,4,F,h,w]: initial noisy latents.
         Frame-sharded models (``mv.set_frame_shard``) capture their all-to-alls with the step: the exchange buffers are
@@ -49,11 +50,12 @@ class GraphedDenoiseStep:
         inside the captured step before the CFG combine.
         ``eta`` / ``generator`` / ``use_clipped_model_output``: DDIMScheduler.step's keywords (defaults: the eta = 0 update).
         ``frame_shard`` (dist.FrameShard): with eta > 0 the variance noise is drawn for the whole clip and cut to the local
-        frames, like the initial noise."""
+        frames, like the initial noise.  ``guidance_rescale``: ``DDIMScheduler.fused_cfg_step``'s keyword."""
         self.mv, self.sch, self.inp, self.cams, self.g = mv, scheduler, inputs, cameras, float(guidance)
         self.cfg_pair = cfg_pair
         self.eta, self.gen, self.clipped, self.shard = float(eta), generator, bool(use_clipped_model_output), frame_shard
-        self.step_kernel = self.always_step_kernel or scheduler.uses_step_kernel(self.eta, self.clipped)
+        self.rescale = float(guidance_rescale)
+        self.step_kernel = self.always_step_kernel or scheduler.uses_step_kernel(self.eta, self.clipped, self.rescale)
         dev = pano_latent.device
         # private copies: the caller's tensors may alias the model-input buffers the body writes into
         init_pano, init_pers = pano_latent.clone(), pers_latent.clone()
@@ -127,7 +129,7 @@ class GraphedDenoiseStep:
         self.pred_pano, self.pred_pers = pred_pano, pred_pers          # static graph-pool tensors (inspection / tests)
         ldt, mdt = self.pano_lat.dtype, pred_pano.dtype    # latents may be kept in another 16-bit type than the model (the reference promotes)
         pred_pano, pred_pers = pred_pano.to(ldt), pred_pers.to(ldt)
-        kw = dict(eta=self.eta, use_clipped_model_output=self.clipped)
+        kw = dict(eta=self.eta, use_clipped_model_output=self.clipped, guidance_rescale=self.rescale)
         new_pano = self.sch.fused_cfg_step(pred_pano[0:1], pred_pano[1:2], self.g, None, self.pano_lat, coef_dev=self.coef,
                                            noise=self._noise(self.pano_lat, mdt, 2), **kw)
         new_pers = self.sch.fused_cfg_step(pred_pers[0:1], pred_pers[1:2], self.g, None, self.pers_lat, coef_dev=self.coef,
@@ -171,7 +173,7 @@ class GraphedWindowedStep(GraphedDenoiseStep):
     always_step_kernel = True
 
     def __init__(self, mv, scheduler, inputs, cameras, pano_latent, pers_latent, guidance, plan, use_fps=True, warmup=1, eta=0.0,
-                 generator=None, use_clipped_model_output=False):
+                 generator=None, use_clipped_model_output=False, guidance_rescale=0.0):
         dev = pano_latent.device
         self.plan = plan
         self.static = plan.static_inputs(inputs)
@@ -179,7 +181,7 @@ class GraphedWindowedStep(GraphedDenoiseStep):
         self.coins = torch.zeros(len(plan), 8, dtype=torch.int32, device=dev)
         self._up_k = _PinnedUploads(self.coins)
         super().__init__(mv, scheduler, inputs, cameras, pano_latent, pers_latent, guidance, use_fps=use_fps, warmup=warmup, eta=eta,
-                         generator=generator, use_clipped_model_output=use_clipped_model_output)
+                         generator=generator, use_clipped_model_output=use_clipped_model_output, guidance_rescale=guidance_rescale)
 
     def _body(self):
         inp = self.inp
@@ -188,7 +190,7 @@ class GraphedWindowedStep(GraphedDenoiseStep):
         self.plan.forward(self.mv, inp, self.static, self.cams, self.timestep, self.use_fps, self.preds_pers, self.preds_pano,
                           coins=self.coins)
         mdt = self.mv.unet.dtype
-        kw = dict(coef_dev=self.coef, eta=self.eta, use_clipped_model_output=self.clipped)
+        kw = dict(coef_dev=self.coef, eta=self.eta, use_clipped_model_output=self.clipped, guidance_rescale=self.rescale)
         new_pano = self.sch.fused_cfg_step_windows(self.preds_pano, self.plan.starts_dev, self.plan.weights, self.g, None,
                                                    self.pano_lat, noise=self._noise(self.pano_lat, mdt, 2), **kw)
         new_pers = self.sch.fused_cfg_step_windows(self.preds_pers, self.plan.starts_dev, self.plan.weights, self.g, None,

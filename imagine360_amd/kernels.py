@@ -53,6 +53,13 @@ _SIGNATURES = {
     "im360_cfg_ddim_update": (_INT, [_PTR] * 4 + [_I64] + [_F32] * 3 + [_INT, _PTR, _PTR]),
     "im360_cfg_ddim_step": (_INT, [_PTR] * 5 + [_I64] + [_F32] * 6 + [_INT, _INT, _PTR, _PTR]),
     "im360_cfg_ddim_step_windows": (_INT, [_PTR] * 6 + [_INT] + [_I64] * 4 + [_F32] * 6 + [_INT, _INT, _PTR, _PTR]),
+    "im360_cfg_rescale_records": (_I64, [_I64]),
+    "im360_cfg_rescale_stats": (_INT, [_PTR] * 2 + [_I64, _F32, _PTR, _I64, _INT, _PTR, _PTR]),
+    "im360_cfg_rescale_stats_windows": (_INT, [_PTR] * 3 + [_INT] + [_I64] * 4 + [_F32, _PTR, _I64, _INT, _PTR, _PTR]),
+    "im360_cfg_rescale_factor": (_INT, [_PTR, _I64, _I64, _F32, _PTR, _PTR]),
+    "im360_cfg_ddim_step_rescale": (_INT, [_PTR] * 5 + [_I64] + [_F32] * 6 + [_INT, _F32, _PTR, _I64, _INT, _PTR, _PTR]),
+    "im360_cfg_ddim_step_windows_rescale": (_INT, [_PTR] * 6 + [_INT] + [_I64] * 4 + [_F32] * 6 + [_INT, _F32, _PTR, _I64, _INT, _PTR,
+                                                                                                  _PTR]),
     "im360_layernorm": (_INT, [_PTR] * 6 + [_I64] * 5 + [_F32, _INT, _PTR]),
     "im360_geglu": (_INT, [_PTR] * 2 + [_I64] * 2 + [_INT, _PTR]),
     "im360_linear_geglu": (_INT, [_PTR] * 4 + [_I64] * 3 + [_INT, _PTR]),
@@ -847,11 +854,44 @@ DDIM_PRED_MODE = {"epsilon": 0, "v_prediction": 1, "sample": 2}
 DDIM_CLIP_SAMPLE, DDIM_CLIPPED_OUTPUT = 4, 8
 
 
-def cfg_ddim_step(uncond, cond, sample, noise, mode, coefs, coef_dev=None):
+RESCALE_RECORD = 8         # floats per partial-moment record of the guidance-rescale statistics pass (csrc/groupnorm.hip)
+
+
+def _rescale_workspace(like):
+    """fp32 workspace for the partial-moment records of a guidance-rescale statistics pass over ``like``: a torch allocation (inside
+    a graph capture it comes from the graph's pool, like the noise tensors)."""
+    return torch.empty(lib().im360_cfg_rescale_records(like.numel()) * RESCALE_RECORD, dtype=torch.float32, device=like.device)
+
+
+def _rescale_stats(uncond, cond, guidance, coef_dev):
+    ws = _rescale_workspace(cond)
+    rc = lib().im360_cfg_rescale_stats(_p(uncond), _p(cond), cond.numel(), float(guidance), _p(ws), ws.numel(), _dt(cond), _stream(),
+                                       _p(coef_dev))
+    _check(rc, "im360_cfg_rescale_stats")
+    return ws
+
+
+def cfg_rescale_factor(uncond, cond, guidance, rescale, coef_dev=None):
+    """The guidance-rescale factor r = rescale * std(cond) / std(m) + (1 - rescale), m = uncond + guidance * (cond - uncond) in fp32,
+    std = torch.std (correction 1) over the whole tensor: a device float32 scalar, no synchronisation.  Two launches: the statistics
+    pass ``cfg_ddim_step(..., rescale=)`` runs, then the merge of its per-workgroup records that every workgroup of the step kernel
+    makes -- the bits the step multiplies by.  ``coef_dev``: device float32 whose element 0 is read as the guidance instead."""
+    _dev(uncond, cond, coef_dev)
+    assert uncond.is_contiguous() and cond.is_contiguous() and uncond.shape == cond.shape and uncond.dtype == cond.dtype
+    ws = _rescale_stats(uncond, cond, guidance, coef_dev)
+    out = torch.empty((), dtype=torch.float32, device=cond.device)
+    _check(lib().im360_cfg_rescale_factor(_p(ws), ws.numel(), cond.numel(), float(rescale), _p(out), _stream()), "im360_cfg_rescale_factor")
+    return out
+
+
+def cfg_ddim_step(uncond, cond, sample, noise, mode, coefs, coef_dev=None, rescale=0.0):
     """DDIMScheduler.step(uncond + g (cond - uncond), t, sample) for any prediction type / clip / eta in one pass.
     ``mode``: DDIM_PRED_MODE | DDIM_CLIP_SAMPLE | DDIM_CLIPPED_OUTPUT; ``coefs`` = (guidance, sqrt_a, sqrt_b, sqrt_a_prev,
     dir, sigma) (DDIMScheduler.step_coefficients); ``noise``: variance noise like ``sample`` or None (zero noise, refused
-    with sigma > 0); ``coef_dev`` = device float32[6] holding ``coefs``, read by the kernel instead (graph replay)."""
+    with sigma > 0); ``coef_dev`` = device float32[6] holding ``coefs``, read by the kernel instead (graph replay).
+    ``rescale`` != 0: guidance rescale (arXiv 2305.08891, 3.4) -- the step sees r (uncond + g (cond - uncond)) with
+    r = rescale * std(cond) / std(uncond + g (cond - uncond)) + (1 - rescale) over the whole tensor; a statistics launch in front of
+    the step launch, no host read.  0 is the single launch without it."""
     _dev(uncond, cond, sample, noise)
     assert uncond.is_contiguous() and cond.is_contiguous() and sample.is_contiguous()
     assert uncond.shape == cond.shape == sample.shape and uncond.dtype == cond.dtype == sample.dtype
@@ -862,18 +902,26 @@ def cfg_ddim_step(uncond, cond, sample, noise, mode, coefs, coef_dev=None):
     if coef_dev is not None:
         assert coef_dev.dtype == torch.float32 and coef_dev.numel() == 6 and coef_dev.is_cuda
     out = torch.empty_like(sample)
+    if rescale != 0.0:
+        ws = _rescale_stats(uncond, cond, coefs[0], coef_dev)
+        rc = lib().im360_cfg_ddim_step_rescale(_p(uncond), _p(cond), _p(sample), _p(noise), _p(out), sample.numel(),
+                                               *(float(v) for v in coefs), int(mode), float(rescale), _p(ws), ws.numel(), _dt(sample),
+                                               _stream(), _p(coef_dev))
+        _check(rc, "im360_cfg_ddim_step_rescale")
+        return out
     rc = lib().im360_cfg_ddim_step(_p(uncond), _p(cond), _p(sample), _p(noise), _p(out), sample.numel(),
                                    *(float(v) for v in coefs), int(mode), _dt(sample), _stream(), _p(coef_dev))
     _check(rc, "im360_cfg_ddim_step")
     return out
 
 
-def cfg_ddim_step_windows(preds, sample, noise, starts, weights, mode, coefs, coef_dev=None):
+def cfg_ddim_step_windows(preds, sample, noise, starts, weights, mode, coefs, coef_dev=None, rescale=0.0):
     """``cfg_ddim_step`` on the per-frame weighted blend of sliding-window predictions, one pass.  ``sample`` (and ``noise`` /
     the result): a panorama latent [1, 4, F, H, W] or a perspective latent [1, m, 4, F, h, w];  ``preds`` [nW, 2, *sample.shape
     with F -> L]: window k's CFG-batched prediction in slot k;  ``starts`` device int32 [nW] ascending window start frames
     (context.context_windows);  ``weights`` device float32 [L] (context.context_weights).  ``mode`` / ``coefs`` / ``coef_dev`` as in
-    ``cfg_ddim_step``."""
+    ``cfg_ddim_step``.  ``rescale`` != 0: guidance rescale with both standard deviations over the whole clip of blends (the text
+    halves blended with the same weights), a statistics launch in front of the step launch."""
     _dev(preds, sample, noise, starts, weights)
     assert preds.is_contiguous() and sample.is_contiguous() and preds.dtype == sample.dtype
     assert sample.dim() in (5, 6) and sample.shape[0] == 1, "sample must be [1, 4, F, H, W] or [1, m, 4, F, h, w]"
@@ -890,6 +938,16 @@ def cfg_ddim_step_windows(preds, sample, noise, starts, weights, mode, coefs, co
     if coef_dev is not None:
         assert coef_dev.dtype == torch.float32 and coef_dev.numel() == 6 and coef_dev.is_cuda
     out = torch.empty_like(sample)
+    if rescale != 0.0:
+        ws = _rescale_workspace(sample)
+        rc = lib().im360_cfg_rescale_stats_windows(_p(preds), _p(starts), _p(weights), nW, outer, F, L, inner, float(coefs[0]), _p(ws),
+                                                   ws.numel(), _dt(sample), _stream(), _p(coef_dev))
+        _check(rc, "im360_cfg_rescale_stats_windows")
+        rc = lib().im360_cfg_ddim_step_windows_rescale(_p(preds), _p(sample), _p(noise), _p(out), _p(starts), _p(weights), nW, outer, F,
+                                                       L, inner, *(float(v) for v in coefs), int(mode), float(rescale), _p(ws),
+                                                       ws.numel(), _dt(sample), _stream(), _p(coef_dev))
+        _check(rc, "im360_cfg_ddim_step_windows_rescale")
+        return out
     rc = lib().im360_cfg_ddim_step_windows(_p(preds), _p(sample), _p(noise), _p(out), _p(starts), _p(weights), nW, outer, F, L,
                                            inner, *(float(v) for v in coefs), int(mode), _dt(sample), _stream(), _p(coef_dev))
     _check(rc, "im360_cfg_ddim_step_windows")

@@ -11,6 +11,8 @@ surface, rebuilt for the MI355X:
     on the same seeds; ``rng="device"`` (default) draws on the GPU like the reference's GPU path;
   * stochastic DDIM (``eta > 0``): per step, after the model's IP-adapter noise, the panorama then the perspective variance
     noise is drawn (from ``generator`` when given), exactly where the reference's ``scheduler.step`` draws it;
+  * guidance rescale (``guidance_rescale=phi``, arXiv 2305.08891 section 3.4): the guided prediction of each branch scaled towards
+    the text prediction's standard deviation inside the CFG + DDIM kernels (a statistics launch in front of the step launch);
   * long clips (``context_frames=L``): sliding temporal context windows -- one forward of the unmodified model per window
     of L frames, the windows' predictions blended per frame inside the CFG + DDIM kernel (imagine360_amd/context.py).
 
@@ -216,7 +218,7 @@ class AnimationPipeline:
                  output_type="tensor", return_dict=True, callback=None, callback_steps=1, latents_dtype=torch.float16,
                  video_batch=None, use_outpaint=False, use_ip_plus_cross_attention=False, use_fps_condition=False,
                  ip_plus_condition="image", prompt_embeds=None, sam_features=None, trace=None, frame_shard=None,
-                 context_frames=None, context_overlap=4, context_weights="pyramid", **kwargs):
+                 context_frames=None, context_overlap=4, context_weights="pyramid", guidance_rescale=0.0, **kwargs):
         """``frame_shard`` (imagine360_amd.dist.FrameShard): this rank denoises a contiguous chunk of the frames (BASELINE
         configs 4 / 5); all ranks must be called with the same seeds and inputs.  Noise is drawn for the whole clip and
         cut, the VAE encodes / the loop runs / the VAE decodes only the local frames, the motion modules exchange tokens
@@ -225,10 +227,18 @@ class AnimationPipeline:
         overlapping windows of ``context_frames`` frames (the motion modules' trained length; frame positions 0 .. L-1 inside
         every window, which lifts the temporal_position_encoding_max_len ceiling), ``context_overlap`` frames shared between
         neighbours, and the windows' predictions are blended per frame with ``context_weights`` ("pyramid" / "uniform") inside
-        the CFG + DDIM kernel.  ``context_frames >= video_length`` is the call without it."""
+        the CFG + DDIM kernel.  ``context_frames >= video_length`` is the call without it.
+        ``guidance_rescale`` (0.0: off; the paper uses 0.7): ``scheduler.rescale_noise_cfg`` on each branch's guided prediction
+        before the update (arXiv 2305.08891, section 3.4: with zero-terminal-SNR betas a guidance of 7.5 over-exposes without it),
+        the standard deviations over the whole panorama latent / over all views of the perspective latent (with context windows:
+        over the whole clip of blends), computed inside the fused CFG + DDIM kernels."""
         device = self.device
         vb = video_batch
         plan = None
+        guidance_rescale = float(guidance_rescale)
+        if guidance_rescale != 0.0 and frame_shard is not None:
+            raise ValueError("guidance_rescale cannot be combined with frame_shard (the standard deviations span the frames of all "
+                             "ranks and would need an all-reduce inside the step, which is not implemented)")
         if context_frames is not None and int(context_frames) < vb["video_length"]:
             if frame_shard is not None:
                 raise ValueError("context_frames cannot be combined with frame_shard (windows under frame sharding are not implemented)")
@@ -292,7 +302,7 @@ class AnimationPipeline:
                               reference_images_clip_feat_pers=feat_pers, relative_position_tensor=rel, pitchs_tensor=pitch)
                 pano_latent, pers_latent = self._windowed_loop(plan, inputs, cameras, pano_latent, pers_latent, steps_host, ts_dev,
                                                                guidance_scale_text, use_fps_condition, eta, generator, trace,
-                                                               callback, callback_steps)
+                                                               callback, callback_steps, guidance_rescale)
             graphed = None
             import torch.distributed as tdist
             capturable = sh is None or (tdist.is_initialized() and tdist.get_backend(sh.group) == "nccl")     # RCCL all-to-alls are stream ops
@@ -304,7 +314,7 @@ class AnimationPipeline:
                               reference_images_clip_feat_pers=feat_pers, relative_position_tensor=rel, pitchs_tensor=pitch)
                 stoch = dict(eta=eta, generator=generator, frame_shard=sh) if eta > 0 else {}
                 graphed = GraphedDenoiseStep(self.mv_base_model, self.scheduler, inputs, cameras, pano_latent, pers_latent,
-                                             guidance_scale_text, use_fps=use_fps_condition, warmup=1, **stoch)       # one eager step fills every cache
+                                             guidance_scale_text, use_fps=use_fps_condition, warmup=1, guidance_rescale=guidance_rescale, **stoch)       # one eager step fills every cache
             for i, t in enumerate(self.progress_bar(steps_host) if plan is None else ()):
                 if graphed is not None:
                     pano_latent, pers_latent = graphed.step(t)
@@ -317,8 +327,8 @@ class AnimationPipeline:
                     use_ip_plus_cross_attention=use_ip_plus_cross_attention, fps_tensor_pano=fps_pano, fps_tensor_pers=fps_pers,
                     reference_images_clip_feat_pano=feat_pano, reference_images_clip_feat_pers=feat_pers,
                     relative_position_tensor=rel, pitchs_tensor=pitch)
-                pano_latent = self._cfg_step(pred_pano, guidance_scale_text, t, pano_latent, eta, generator, sh, 2)
-                pers_latent = self._cfg_step(pred_pers, guidance_scale_text, t, pers_latent, eta, generator, sh, 3)
+                pano_latent = self._cfg_step(pred_pano, guidance_scale_text, t, pano_latent, eta, generator, sh, 2, guidance_rescale)
+                pers_latent = self._cfg_step(pred_pers, guidance_scale_text, t, pers_latent, eta, generator, sh, 3, guidance_rescale)
                 if trace is not None:
                     trace.append(pano_latent.clone())
                 if callback is not None and i % callback_steps == 0:
@@ -339,15 +349,15 @@ class AnimationPipeline:
             if sh is not None:
                 self.mv_base_model.set_frame_shard(None)      # also when the loop raises: the model must not stay sharded
 
-    def _cfg_step(self, pred, g, t, latent, eta=0.0, generator=None, shard=None, frame_dim=2):
+    def _cfg_step(self, pred, g, t, latent, eta=0.0, generator=None, shard=None, frame_dim=2, guidance_rescale=0.0):
         u, c = pred.to(latent.dtype).chunk(2)          # latents_dtype may differ from the model dtype (the reference promotes)
         if eta > 0:
             z = variance_noise(self.scheduler, latent, pred.dtype, generator, self.rng, shard, frame_dim)
-            return self.scheduler.fused_cfg_step(u, c, g, t, latent, eta=eta, noise=z)
-        return self.scheduler.fused_cfg_step(u, c, g, t, latent)
+            return self.scheduler.fused_cfg_step(u, c, g, t, latent, eta=eta, noise=z, guidance_rescale=guidance_rescale)
+        return self.scheduler.fused_cfg_step(u, c, g, t, latent, guidance_rescale=guidance_rescale)
 
     def _windowed_loop(self, plan, inputs, cameras, pano_latent, pers_latent, steps_host, ts_dev, g, use_fps, eta, generator,
-                       trace, callback, callback_steps):
+                       trace, callback, callback_steps, guidance_rescale=0.0):
         """The denoising loop over sliding temporal context windows: per step one forward per window (ascending), then ONE
         blend + CFG + DDIM kernel per branch, panorama first.  RNG: as len(plan) successive calls of the model, then (eta > 0)
         the whole clip's panorama and perspective variance noise.  Captured in one hipGraph under the conditions of the
@@ -358,7 +368,7 @@ class AnimationPipeline:
             if self.use_graph and self.rng == "device" and pano_latent.is_cuda and trace is None and callback is None:
                 from .graph_step import GraphedWindowedStep
                 graphed = GraphedWindowedStep(mv, sch, inputs, cameras, pano_latent, pers_latent, g, plan, use_fps=use_fps, warmup=1,
-                                              eta=eta, generator=generator)
+                                              eta=eta, generator=generator, guidance_rescale=guidance_rescale)
                 for t in self.progress_bar(steps_host):
                     pano_latent, pers_latent = graphed.step(t)
                 return pano_latent, pers_latent
@@ -369,7 +379,7 @@ class AnimationPipeline:
                 inputs["latents"][:, :, :4] = pers_latent
                 plan.forward(mv, inputs, static, cameras, ts_dev[i], use_fps, preds_pers, preds_pano)
                 mdt = mv.unet.dtype
-                kw = dict(eta=eta)
+                kw = dict(eta=eta, guidance_rescale=guidance_rescale)
                 z = variance_noise(sch, pano_latent, mdt, generator, self.rng) if eta > 0 else None
                 pano_latent = sch.fused_cfg_step_windows(preds_pano, plan.starts_dev, plan.weights, g, t, pano_latent, noise=z, **kw)
                 z = variance_noise(sch, pers_latent, mdt, generator, self.rng, frame_dim=3) if eta > 0 else None

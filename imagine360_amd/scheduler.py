@@ -5,7 +5,8 @@ Coefficients are tabulated on the host in fp32 exactly like the reference (so ``
 bit for bit) and combined in fp64 python floats; on the GPU the whole CFG + update chain of the
 pipeline is one elementwise HIP kernel (``fused_cfg_step``): the eta = 0 v / epsilon update of the dual pipeline on
 ``cfg_ddim_update``, everything else ``step`` supports (eta > 0, clip_sample, prediction_type="sample",
-use_clipped_model_output) on ``cfg_ddim_step``.
+use_clipped_model_output) on ``cfg_ddim_step``; with ``guidance_rescale`` (arXiv 2305.08891, section 3.4) a statistics launch
+precedes ``cfg_ddim_step``.
 """
 import math
 from dataclasses import dataclass
@@ -51,6 +52,25 @@ def rescale_zero_terminal_snr(betas):
     abar = abar_sqrt ** 2
     alphas = torch.cat([abar[0:1], abar[1:] / abar[:-1]])
     return 1 - alphas
+
+
+def rescale_noise_cfg(noise_cfg, noise_pred_text, guidance_rescale=0.0):
+    """arXiv 2305.08891, section 3.4 (diffusers' function of the same name): the guided prediction scaled back towards the standard
+    deviation of the text-conditioned one, ``noise_cfg * (guidance_rescale * std(noise_pred_text) / std(noise_cfg) + 1 -
+    guidance_rescale)``, std = torch.std (correction 1) over every dimension but the batch dimension.  The eager definition, in
+    torch ops on any device; the pipeline's kernels compute the same factor inside the fused CFG + DDIM step."""
+    if guidance_rescale == 0.0:
+        return noise_cfg
+    dims = list(range(1, noise_pred_text.ndim))
+    std_text = noise_pred_text.std(dim=dims, keepdim=True)
+    std_cfg = noise_cfg.std(dim=dims, keepdim=True)
+    return noise_cfg * (guidance_rescale * std_text / std_cfg + (1.0 - guidance_rescale))
+
+
+def _rescale_kw(guidance_rescale):
+    """``rescale=`` for kernels.cfg_ddim_step / cfg_ddim_step_windows, left out when it is off: with phi = 0 the kernels are
+    called with exactly the arguments of before."""
+    return dict(rescale=float(guidance_rescale)) if guidance_rescale != 0.0 else {}
 
 
 class DDIMScheduler:
@@ -113,10 +133,10 @@ class DDIMScheduler:
             raise ValueError(f"prediction_type {self.config.prediction_type} unsupported")
         return cx, cv
 
-    def uses_step_kernel(self, eta=0.0, use_clipped_model_output=False):
-        """True when an update needs ``cfg_ddim_step``: anything but the eta = 0, unclipped v / epsilon update that
-        ``coefficients`` / ``cfg_ddim_update`` compute."""
-        return (eta != 0.0 or bool(self.config.clip_sample) or bool(use_clipped_model_output)
+    def uses_step_kernel(self, eta=0.0, use_clipped_model_output=False, guidance_rescale=0.0):
+        """True when an update needs ``cfg_ddim_step``: anything but the eta = 0, unclipped v / epsilon update without guidance
+        rescale that ``coefficients`` / ``cfg_ddim_update`` compute."""
+        return (eta != 0.0 or bool(self.config.clip_sample) or bool(use_clipped_model_output) or guidance_rescale != 0.0
                 or self.config.prediction_type not in ("v_prediction", "epsilon"))
 
     def kernel_mode(self, use_clipped_model_output=False):
@@ -186,31 +206,33 @@ class DDIMScheduler:
         return DDIMSchedulerOutput(prev_sample=prev, pred_original_sample=x0) if return_dict else (prev,)
 
     def fused_cfg_step(self, pred_uncond, pred_text, guidance_scale, timestep, sample, coef_dev=None, *, eta=0.0, noise=None,
-                       use_clipped_model_output=False):
+                       use_clipped_model_output=False, guidance_rescale=0.0):
         """CFG combine + update in one HIP kernel (pipeline_animation_inference_dual.py:791-800).  ``coef_dev``: device
         float32 coefficients read by the kernel instead of host scalars (graph replay): [3] = (guidance, cx, cv) for the
         eta = 0 v / epsilon update, [6] = ``step_coefficients`` otherwise.  ``noise``: the variance noise (like ``sample``),
-        used when eta > 0."""
+        used when eta > 0.  ``guidance_rescale`` != 0: ``rescale_noise_cfg`` on the combination before the update, inside the step
+        kernel (always the six-coefficient one)."""
         u, c, x = pred_uncond.contiguous(), pred_text.contiguous(), sample.contiguous()
-        if not self.uses_step_kernel(eta, use_clipped_model_output):
+        if not self.uses_step_kernel(eta, use_clipped_model_output, guidance_rescale):
             cx, cv = (0.0, 0.0) if coef_dev is not None else self.coefficients(timestep)
             return kernels.cfg_ddim_update(u, c, x, guidance_scale, cx, cv, coef_dev=coef_dev)
         if eta > 0 and noise is None:
             raise ValueError("fused_cfg_step: eta > 0 needs the variance noise")
         coefs = (0.0,) * 6 if coef_dev is not None else self.step_coefficients(timestep, eta, guidance_scale)
         return kernels.cfg_ddim_step(u, c, x, noise.to(x.dtype).contiguous() if eta > 0 else None,
-                                     self.kernel_mode(use_clipped_model_output), coefs, coef_dev=coef_dev)
+                                     self.kernel_mode(use_clipped_model_output), coefs, coef_dev=coef_dev, **_rescale_kw(guidance_rescale))
 
     def fused_cfg_step_windows(self, preds, starts, weights, guidance_scale, timestep, sample, coef_dev=None, *, eta=0.0,
-                               noise=None, use_clipped_model_output=False):
+                               noise=None, use_clipped_model_output=False, guidance_rescale=0.0):
         """``fused_cfg_step`` over sliding temporal context windows: the per-frame weighted blend of the windows' CFG-combined
         predictions + the update, one HIP kernel (``kernels.cfg_ddim_step_windows``).  ``preds`` [nW, 2, ...]: window k's
         CFG-batched prediction in slot k, in ``sample``'s layout with L frames;  ``starts`` device int32 [nW], ``weights`` device
         float32 [L] (imagine360_amd.context).  The step kernel serves eta = 0 as well, so ``coef_dev`` is always float32[6] =
-        ``step_coefficients``."""
+        ``step_coefficients``.  ``guidance_rescale`` != 0: ``rescale_noise_cfg`` on the blends (guided and text), the standard
+        deviations over the whole clip."""
         if eta > 0 and noise is None:
             raise ValueError("fused_cfg_step_windows: eta > 0 needs the variance noise")
         x = sample.contiguous()
         coefs = (0.0,) * 6 if coef_dev is not None else self.step_coefficients(timestep, eta, guidance_scale)
         return kernels.cfg_ddim_step_windows(preds.contiguous(), x, noise.to(x.dtype).contiguous() if eta > 0 else None, starts,
-                                             weights, self.kernel_mode(use_clipped_model_output), coefs, coef_dev=coef_dev)
+                                             weights, self.kernel_mode(use_clipped_model_output), coefs, coef_dev=coef_dev, **_rescale_kw(guidance_rescale))

@@ -261,6 +261,56 @@ int im360_cfg_ddim_step_windows(const void* pred, const void* x, const void* noi
                                 float sqrt_a, float sqrt_b, float sqrt_a_prev, float dir, float sigma, int mode, int dtype,
                                 void* stream, const void* coef_dev);
 
+/* ---- guidance rescale (arXiv 2305.08891, section 3.4) inside the CFG + DDIM step: the step sees m' = r * m instead of
+ * m = uncond + guidance * (cond - uncond), with one scalar per tensor
+ *   r = phi * std(cond) / std(m) + (1 - phi),   std = torch.std (correction 1) over all n elements, m formed in fp32.
+ * Two launches per step, no host read, no atomics, no counter: a statistics pass writes one record of partial moments
+ * (count, mean and M2 = sum (v - mean)^2 of cond and of m; 8 floats, five used) per workgroup into ws, and every workgroup of the
+ * step kernel merges all records itself with Chan's formula in one fixed order, so all of them use the same bits and the result is
+ * bit-identical from run to run.  std(m) = 0 or n = 1 give inf / NaN, as the formula does. ---- */
+
+/* Number of records the statistics pass writes for n elements (= its grid: one workgroup per 256 groups of 8 elements, at most
+ * 256): ws must hold 8 * im360_cfg_rescale_records(n) floats.  Host code. */
+int64_t im360_cfg_rescale_records(int64_t n);
+
+/* Statistics pass over cond and m = uncond + guidance * (cond - uncond): n elements (n % 8 == 0, 16-byte aligned), both tensors
+ * of the same 16-bit dtype; ws: device float[ws_floats], ws_floats >= 8 * im360_cfg_rescale_records(n).  coef_dev (optional):
+ * device float[>= 1] whose element 0 overrides guidance (the coefficient buffer of the step: hipGraph replay).
+ * Replaces: nothing in the reference (its pipeline has no guidance_rescale); the std reductions of diffusers' rescale_noise_cfg. */
+int im360_cfg_rescale_stats(const void* uncond, const void* cond, int64_t n, float guidance, void* ws, int64_t ws_floats,
+                            int dtype, void* stream, const void* coef_dev);
+
+/* The same over the per-frame blends of sliding context windows: layout, tables and preconditions of
+ * im360_cfg_ddim_step_windows; m is that entry point's blend, cond is blended with the same weights in the same order,
+ *   c = (sum_k weight[f - start[k]] * c_k) / (sum_k weight[f - start[k]]),
+ * and the moments span the whole clip [outer, F, inner].  nW = 1, start = {0}, weight all 1, L = F writes the records of
+ * im360_cfg_rescale_stats bit for bit (for any inner).
+ * Replaces: nothing in the reference (no temporal windows, no guidance_rescale). */
+int im360_cfg_rescale_stats_windows(const void* pred, const void* start, const void* weight, int nW, int64_t outer, int64_t F,
+                                    int64_t L, int64_t inner, float guidance, void* ws, int64_t ws_floats, int dtype,
+                                    void* stream, const void* coef_dev);
+
+/* out[0] (device float) = r from the records a statistics pass over n elements left in ws: one workgroup making the merge every
+ * workgroup of the step kernels makes (the same bits).  For tests and tools; phi must be finite.
+ * Replaces: nothing in the reference. */
+int im360_cfg_rescale_factor(const void* ws, int64_t ws_floats, int64_t n, float phi, void* out, void* stream);
+
+/* im360_cfg_ddim_step on r * m: same arguments, mode word, six coefficients, optional noise and coef_dev[6]; phi (finite) and the
+ * records im360_cfg_rescale_stats wrote into ws for the same uncond / cond / n / guidance (ws_floats as there).
+ * Replaces: nothing in the reference; diffusers' rescale_noise_cfg between the CFG combine and DDIMScheduler.step. */
+int im360_cfg_ddim_step_rescale(const void* uncond, const void* cond, const void* x, const void* noise, void* out, int64_t n,
+                                float guidance, float sqrt_a, float sqrt_b, float sqrt_a_prev, float dir, float sigma, int mode,
+                                float phi, const void* ws, int64_t ws_floats, int dtype, void* stream, const void* coef_dev);
+
+/* im360_cfg_ddim_step_windows on r * m, r from the records of im360_cfg_rescale_stats_windows over the same clip.  One uniform
+ * window with L = F gives im360_cfg_ddim_step_rescale's result bit for bit.
+ * Replaces: nothing in the reference. */
+int im360_cfg_ddim_step_windows_rescale(const void* pred, const void* x, const void* noise, void* out, const void* start,
+                                        const void* weight, int nW, int64_t outer, int64_t F, int64_t L, int64_t inner,
+                                        float guidance, float sqrt_a, float sqrt_b, float sqrt_a_prev, float dir, float sigma,
+                                        int mode, float phi, const void* ws, int64_t ws_floats, int dtype, void* stream,
+                                        const void* coef_dev);
+
 /* y[r] = LayerNorm(x[r] + pre[r % pre_period]) * gamma + beta + post[(r / post_div) % post_mod] on token rows
  * [rows, C]; pre / post are optional [*, C] tables (the WarpAttn spherical PE added before norm1, the motion
  * module's frame PE added after the norm).

@@ -5,7 +5,8 @@ variants' replays alternated round by round so that clock ramps and box noise hi
 and whether the updated latents are bit-identical to the first variant's.
     python tools/ab_step.py "base" "nt=1" "tattn_nt=1" "nt=1,tattn_nt=3" "GN_MODE=three" [--steps 6] [--rounds 4]
 A variant is a comma-separated list of knob=value (kernels.KNOBS) or NAME=value for an upper-case attribute of imagine360_amd.kernels
-/ imagine360_amd.layers (GN_MODE=three, ROUTE_MIN_TOKENS=32768, ...), or LIB=<path of another build of libim360_kernels.so>."""
+/ imagine360_amd.layers (GN_MODE=three, ROUTE_MIN_TOKENS=32768, ...), or LIB=<path of another build of libim360_kernels.so>, or
+RESCALE=<phi>: the step captured with guidance_rescale = phi (the statistics launch + the rescaled step kernel of each branch)."""
 import os
 import statistics
 import sys
@@ -88,9 +89,11 @@ def main():
     pers_lat = inp["latents"][:1, :, :4].contiguous()
     graphs, finals = [], []
     for spec in variants:
-        undo = apply(parse(spec))
+        settings = parse(spec)
+        rescale = {"guidance_rescale": float(v) for k, v in settings if k == "RESCALE"}
+        undo = apply([kv for kv in settings if kv[0] != "RESCALE"])
         try:
-            gs = GraphedDenoiseStep(mv, sch, inp, cams, pano_lat, pers_lat, 7.5, warmup=1)
+            gs = GraphedDenoiseStep(mv, sch, inp, cams, pano_lat, pers_lat, 7.5, warmup=1, **rescale)
         finally:
             revert(undo)
         graphs.append(gs)
