@@ -3,22 +3,34 @@
 A clip of ``frames`` frames is denoised as overlapping windows of ``length`` frames (the length the motion modules were
 trained on); per step every window is one forward of the unmodified model with frame positions 0 .. length-1, and the
 windows' predictions are blended per frame -- weighted by ``context_weights`` and divided by the per-frame sum of the weights of
-the windows that cover the frame -- inside the CFG + DDIM kernel (``kernels.cfg_ddim_step_windows``).  No wrap-around in time.
+the windows that cover the frame -- inside the CFG + DDIM kernel (``kernels.cfg_ddim_step_windows``).
+
+A clip that is played as a loop takes its windows on a ring (``loop=True``): window k covers the frames (s_k + j) mod frames, so the
+windows that cross the end of the clip show the model ... F-2, F-1, 0, 1 ... as consecutive frames, and the last and the first frame
+are blended like any other pair of neighbours.  The default is the line: no wrap-around in time.
 """
 import torch
 
 WEIGHT_KINDS = ("uniform", "pyramid")
 
 
-def context_windows(frames, length, overlap):
+def context_windows(frames, length, overlap, loop=False):
     """Start frames of the windows, ascending: k (length - overlap) while the window ends before the last frame, then one
     last window shifted back so that it ends on the last frame.  ``length >= frames``: the single window [0] (of ``frames``
-    frames).  Every frame lies in at least one window and in at most ceil(length / (length - overlap)) + 1."""
+    frames).  Every frame lies in at least one window and in at most ceil(length / (length - overlap)) + 1.
+    ``loop``: the windows of a ring of ``frames`` frames -- k (length - overlap) for k = 0 .. ceil(frames / (length - overlap)) - 1,
+    all below ``frames``, no shifted last window; window k covers the frames (start + j) mod frames.  Needs length < frames."""
     frames, length, overlap = int(frames), int(length), int(overlap)
     if frames < 1 or length < 1:
         raise ValueError(f"context_windows: frames={frames} and length={length} must be positive")
     if not 0 <= overlap < length:
         raise ValueError(f"context_windows: overlap={overlap} must satisfy 0 <= overlap < length={length}")
+    if loop:
+        if length >= frames:
+            raise ValueError(f"context_windows: a looping clip needs context_frames < video_length (one window cannot wrap around), "
+                             f"got length={length}, frames={frames}")
+        stride = length - overlap
+        return [k * stride for k in range(-(-frames // stride))]
     if length >= frames:
         return [0]
     stride = length - overlap
@@ -50,41 +62,65 @@ def context_weights(length, kind="pyramid"):
     raise ValueError(f"context_weights: kind {kind!r} must be one of {WEIGHT_KINDS}")
 
 
-def coverage(frames, length, starts):
-    """Number of windows covering each frame (list of ``frames`` ints)."""
+def coverage(frames, length, starts, loop=False):
+    """Number of windows covering each frame (list of ``frames`` ints).  ``loop``: the windows wrap around the end of the clip."""
     cov = [0] * frames
     for s in starts:
         for f in range(s, s + length):
-            cov[f] += 1
+            cov[f % frames if loop else f] += 1
     return cov
 
 
 class WindowPlan:
     """The windows of one clip: ``starts`` (host ints), ``length``, the device tables the blend kernel reads, and the per-window
-    model inputs.  ``inputs``: the keyword tensors of MultiViewBaseModel.forward for the WHOLE clip."""
+    model inputs.  ``inputs``: the keyword tensors of MultiViewBaseModel.forward for the WHOLE clip.  ``loop``: the windows of a
+    ring (context_windows(loop=True)); ``frame_index[k]`` is then the device int64 vector (s_k + arange(L)) % F of window k's frames,
+    and a window that crosses the end of the clip is cut with one ``index_select`` per tensor instead of a slice view."""
 
-    def __init__(self, frames, length, overlap=4, kind="pyramid", device="cpu"):
+    def __init__(self, frames, length, overlap=4, kind="pyramid", device="cpu", loop=False):
         self.frames, self.length = int(frames), window_length(frames, length)
-        self.starts = context_windows(frames, length, overlap)
+        self.loop = bool(loop)
+        self.starts = context_windows(frames, length, overlap, loop=True) if self.loop else context_windows(frames, length, overlap)
         self.kind = kind
         self.weights = context_weights(self.length, kind).to(device)
         self.starts_dev = torch.tensor(self.starts, dtype=torch.int32, device=device)
+        self.frame_index = None
+        if self.loop:
+            self.frame_index = [(s + torch.arange(self.length, dtype=torch.int64, device=device)) % self.frames for s in self.starts]
 
     def __len__(self):
         return len(self.starts)
 
+    def wraps(self, k):
+        """True when window k crosses the end of the clip (looping plans only)."""
+        return self.starts[k] + self.length > self.frames
+
+    def _cut(self, x, dim, k):
+        """Window k's frames of ``x`` along ``dim``: the slice view, or -- the window wraps -- one gather."""
+        if self.wraps(k):
+            return x.index_select(dim, self.frame_index[k])
+        return x.narrow(dim, self.starts[k], self.length)
+
     def static_inputs(self, inputs):
         """Per window, the step-invariant frame-indexed conditioning cut to the window's frames: the SAM features as one
         contiguous tensor per window (the model caches the IP tokens it derives from them on the tensor's identity; the
-        perspective one keeps its stride-0 view axis), crop rectangles and pitches as views."""
+        perspective one keeps its stride-0 view axis), crop rectangles and pitches as views.  A window that wraps gathers all
+        four here, once."""
         out = []
-        for s in self.starts:
+        for k, s in enumerate(self.starts):
             e = s + self.length
             fp = inputs["reference_images_clip_feat_pers"]
             shared = fp.stride(1) == 0
+            rel, pitch = inputs["relative_position_tensor"], inputs["pitchs_tensor"]
+            if self.wraps(k):
+                fp_w = (self._cut(fp[:, 0], 1, k).unsqueeze(1).expand(-1, fp.shape[1], -1, -1, -1) if shared else self._cut(fp, 2, k))
+                out.append(dict(reference_images_clip_feat_pano=self._cut(inputs["reference_images_clip_feat_pano"], 1, k),
+                                reference_images_clip_feat_pers=fp_w,
+                                relative_position_tensor=None if rel is None else self._cut(rel, 1, k),
+                                pitchs_tensor=None if pitch is None else self._cut(pitch, 1, k)))
+                continue
             fp_w = (fp[:, 0, s:e].contiguous().unsqueeze(1).expand(-1, fp.shape[1], -1, -1, -1) if shared
                     else fp[:, :, s:e].contiguous())
-            rel, pitch = inputs["relative_position_tensor"], inputs["pitchs_tensor"]
             out.append(dict(reference_images_clip_feat_pano=inputs["reference_images_clip_feat_pano"][:, s:e].contiguous(),
                             reference_images_clip_feat_pers=fp_w,
                             relative_position_tensor=None if rel is None else rel[:, s:e],
@@ -92,20 +128,20 @@ class WindowPlan:
         return out
 
     def forward(self, mv, inputs, static, cameras, timestep, use_fps, preds_pers, preds_pano, coins=None):
-        """One forward of the unmodified model per window, ascending: window k sees frames s_k .. s_k + L - 1 of both model
-        inputs (``inputs["latents"]`` [2,m,9,F,h,w], ``inputs["pano_latent"]`` [2,9,F,H,W]) and ``static[k]``; text embeddings,
+        """One forward of the unmodified model per window, ascending: window k sees frames s_k .. s_k + L - 1 (on a ring: modulo
+        F; a window that wraps gathers them with one index_select per input, every call -- their first four channels change) of both
+        model inputs (``inputs["latents"]`` [2,m,9,F,h,w], ``inputs["pano_latent"]`` [2,9,F,H,W]) and ``static[k]``; text embeddings,
         fps and cameras are shared.  Its CFG-batched predictions go to slot k of ``preds_pers`` [nW,2,m,4,L,h,w] / ``preds_pano``
         [nW,2,4,L,H,W] (cast to their dtype by the copy).  Each call draws its IP-adapter noise (panorama, perspective) and its
         seven WarpAttn coins, like nW successive calls of the model; ``coins`` [nW, 8] device int32: preloaded coins, row k for
         window k (captured steps)."""
-        L = self.length
         saved = mv._coins_dev, mv.coins_preloaded
         try:
-            for k, s in enumerate(self.starts):
+            for k in range(len(self.starts)):
                 if coins is not None:
                     mv._coins_dev, mv.coins_preloaded = coins[k], True
                 pred_pers, pred_pano = mv(
-                    latents=inputs["latents"][:, :, :, s:s + L], pano_latent=inputs["pano_latent"][:, :, s:s + L],
+                    latents=self._cut(inputs["latents"], 3, k), pano_latent=self._cut(inputs["pano_latent"], 2, k),
                     timestep=timestep, prompt_embd=inputs["prompt_embd"], pano_prompt_embd=inputs["pano_prompt_embd"],
                     cameras=cameras, use_fps_condition=use_fps, use_ip_plus_cross_attention=True,
                     fps_tensor_pano=inputs["fps_tensor_pano"], fps_tensor_pers=inputs["fps_tensor_pers"], **static[k])

@@ -834,11 +834,15 @@ __global__ __launch_bounds__(RS ? 256 : 1024) void cfg_ddim_step_kernel(const T*
 //      (a fixed summation order: deterministic), then ddim_step_elem; one rounding, at the store.  V = 8: 16-byte lanes (inner % 8
 //      == 0, so a lane never straddles a frame); V = 1: the scalar path for any inner.  The first covering window initialises the
 //      sums, so one window with weight 1 gives m = 1 * m_0 / 1 = m_0 exactly: bit-identical to cfg_ddim_step_kernel.
+//      wrap = 0: the windows lie on a line (above).  wrap = F: they lie on a ring of F frames, window k covers the frames
+//      (s_k + j) mod F, j = 0 .. L - 1, and a frame in front of s_k is at position f - s_k + F.  One integer compare-and-add per
+//      window and lane; slot order and float arithmetic are those of the line.  j indexes pred / weight only when 0 <= j < L,
+//      whatever the table holds.
 // The blend of the V elements from element e0 on (V = 8: one 16-byte lane inside one frame): mb[] = the guided prediction m above;
 // cb[] (CB only) = the same blend of the text half c_k alone, what the guidance rescale takes std(c) of.
 template <typename T, int V, bool CB>
 __device__ __forceinline__ void windows_blend(const T* __restrict__ pred, const int* __restrict__ start, const float* __restrict__ weight,
-                                              int nW, int F, int L, long inner, long half, long e0, float g, float* mb, float* cb) {
+                                              int nW, int F, int L, int wrap, long inner, long half, long e0, float g, float* mb, float* cb) {
     const long r = e0 % inner, of = e0 / inner;
     const int f = (int)(of % F);
     const long o = of / F;
@@ -848,7 +852,8 @@ __device__ __forceinline__ void windows_blend(const T* __restrict__ pred, const 
     float wsum = 0.0f;
     bool first = true;
     for (int w = 0; w < nW; ++w) {
-        const int j = f - start[w];
+        int j = f - start[w];
+        if (j < 0) j += wrap;
         if (j < 0 || j >= L) continue;
         const float wt = weight[j];
         const long at = (long)w * 2 * half + (o * L + j) * inner + r;
@@ -885,7 +890,7 @@ __device__ __forceinline__ void windows_blend(const T* __restrict__ pred, const 
 template <typename T, int V>
 __global__ __launch_bounds__(256) void cfg_rescale_stats_windows_kernel(const T* __restrict__ pred, const int* __restrict__ start,
                                                                          const float* __restrict__ weight, int nW, long outer, int F, int L,
-                                                                         long inner, float g, const float* __restrict__ coef,
+                                                                         int wrap, long inner, float g, const float* __restrict__ coef,
                                                                          float* __restrict__ ws) {
     __shared__ CfgMoments lds[4];
     if (coef != nullptr) g = coef[0];
@@ -896,12 +901,12 @@ __global__ __launch_bounds__(256) void cfg_rescale_stats_windows_kernel(const T*
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
         float c[8], m[8];
         int cnt = 8;
-        if (V == 8) windows_blend<T, 8, true>(pred, start, weight, nW, F, L, inner, half, i * 8, g, m, c);
+        if (V == 8) windows_blend<T, 8, true>(pred, start, weight, nW, F, L, wrap, inner, half, i * 8, g, m, c);
         else {
             cnt = (int)(n - i * 8 < 8 ? n - i * 8 : 8);
 #pragma unroll
             for (int e = 0; e < 8; ++e)
-                if (e < cnt) windows_blend<T, 1, true>(pred, start, weight, nW, F, L, inner, half, i * 8 + e, g, &m[e], &c[e]);
+                if (e < cnt) windows_blend<T, 1, true>(pred, start, weight, nW, F, L, wrap, inner, half, i * 8 + e, g, &m[e], &c[e]);
         }
         moments_add(a, c, m, cnt);
     }
@@ -912,7 +917,7 @@ __global__ __launch_bounds__(256) void cfg_rescale_stats_windows_kernel(const T*
 template <typename T, int V, bool RS>
 __global__ __launch_bounds__(RS ? 256 : 1024) void cfg_ddim_step_windows_kernel(const T* __restrict__ pred, const T* __restrict__ x, const T* __restrict__ noise,
                                              T* __restrict__ out, const int* __restrict__ start, const float* __restrict__ weight,
-                                             int nW, long outer, int F, int L, long inner, float g, float sa, float sb, float sap,
+                                             int nW, long outer, int F, int L, int wrap, long inner, float g, float sa, float sb, float sap,
                                              float dir, float sigma, int mode, const float* __restrict__ coef,
                                              const float* __restrict__ ws, int nrec, float phi) {
     const DdimCoefs k = ddim_coefs(g, sa, sb, sap, dir, sigma, mode, coef);
@@ -922,7 +927,7 @@ __global__ __launch_bounds__(RS ? 256 : 1024) void cfg_ddim_step_windows_kernel(
     const long half = outer * L * inner;              // one CFG half of one window
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
         float m[V], s[V], z[V];
-        windows_blend<T, V, false>(pred, start, weight, nW, F, L, inner, half, i * V, k.g, m, nullptr);
+        windows_blend<T, V, false>(pred, start, weight, nW, F, L, wrap, inner, half, i * V, k.g, m, nullptr);
         if (V == 8) {
             unpack8<T>(((const uint4*)x)[i], s);
             if (noise != nullptr) unpack8<T>(((const uint4*)noise)[i], z);
@@ -1311,30 +1316,51 @@ extern "C" __attribute__((visibility("default"))) int im360_cfg_rescale_stats(co
     });
 }
 
-// the same over the per-frame blends of nW sliding-window predictions (layout and tables of im360_cfg_ddim_step_windows)
-extern "C" __attribute__((visibility("default"))) int im360_cfg_rescale_stats_windows(const void* pred, const void* start, const void* weight, int nW,
-                                   int64_t outer, int64_t F, int64_t L, int64_t inner, float guidance, void* ws, int64_t ws_floats,
-                                   int dtype, void* stream, const void* coef_dev) {
-    using namespace im360;
-    IM360_CHECK_ARG(pred && start && weight, "cfg_rescale_stats_windows: null pointer");
-    IM360_CHECK_ARG(nW > 0 && outer > 0 && inner > 0 && L > 0 && L <= F && F < (1 << 30),
-                    "cfg_rescale_stats_windows: nW=%d outer=%ld F=%ld L=%ld inner=%ld out of range", nW, (long)outer, (long)F, (long)L, (long)inner);
-    IM360_CHECK_ARG(((uintptr_t)start % 4) == 0 && ((uintptr_t)weight % 4) == 0, "cfg_rescale_stats_windows: misaligned table");
-    const int64_t n = outer * F * inner;
-    IM360_CHECK_RESCALE_WS("cfg_rescale_stats_windows", n);
+namespace im360 {
+// im360_cfg_rescale_stats_windows (wrap = 0) and im360_cfg_rescale_stats_windows_ring (wrap = F) behind their argument checks
+static int launch_cfg_rescale_stats_windows(const char* name, const void* pred, const void* start, const void* weight, int nW, int64_t outer,
+                                            int64_t F, int64_t L, int wrap, int64_t inner, float guidance, void* ws, int dtype, void* stream,
+                                            const void* coef_dev) {
     const bool vec = (inner % 8) == 0 && ((uintptr_t)pred % 16) == 0;
-    const unsigned blocks = (unsigned)im360_cfg_rescale_records(n);
+    const unsigned blocks = (unsigned)im360_cfg_rescale_records(outer * F * inner);
     hipStream_t s = (hipStream_t)stream;
-    return with_dtype(dtype, "cfg_rescale_stats_windows", [&](auto t) {
+    return with_dtype(dtype, name, [&](auto t) {
         using T = typename decltype(t)::type;
         with_const<1, 8>(vec ? 8 : 1, [&](auto v) {
             hipLaunchKernelGGL((cfg_rescale_stats_windows_kernel<T, decltype(v)::value>), dim3(blocks), dim3(256), 0, s, (const T*)pred,
-                               (const int*)start, (const float*)weight, nW, (long)outer, (int)F, (int)L, (long)inner, guidance,
+                               (const int*)start, (const float*)weight, nW, (long)outer, (int)F, (int)L, wrap, (long)inner, guidance,
                                (const float*)coef_dev, (float*)ws);
         });
         IM360_CHECK_LAUNCH();
         return IM360_OK;
     });
+}
+}  // namespace im360
+
+#define IM360_CHECK_CFG_RESCALE_STATS_WINDOWS(name)                                                                                  \
+    IM360_CHECK_ARG(pred && start && weight, name ": null pointer");                                                                 \
+    IM360_CHECK_ARG(nW > 0 && outer > 0 && inner > 0 && L > 0 && L <= F && F < (1 << 30),                                            \
+                    name ": nW=%d outer=%ld F=%ld L=%ld inner=%ld out of range", nW, (long)outer, (long)F, (long)L, (long)inner);    \
+    IM360_CHECK_ARG(((uintptr_t)start % 4) == 0 && ((uintptr_t)weight % 4) == 0, name ": misaligned table");                         \
+    IM360_CHECK_RESCALE_WS(name, outer * F * inner)
+
+// the same over the per-frame blends of nW sliding-window predictions (layout and tables of im360_cfg_ddim_step_windows)
+extern "C" __attribute__((visibility("default"))) int im360_cfg_rescale_stats_windows(const void* pred, const void* start, const void* weight, int nW,
+                                   int64_t outer, int64_t F, int64_t L, int64_t inner, float guidance, void* ws, int64_t ws_floats,
+                                   int dtype, void* stream, const void* coef_dev) {
+    IM360_CHECK_CFG_RESCALE_STATS_WINDOWS("cfg_rescale_stats_windows");
+    return im360::launch_cfg_rescale_stats_windows("cfg_rescale_stats_windows", pred, start, weight, nW, outer, F, L, 0, inner, guidance, ws,
+                                                   dtype, stream, coef_dev);
+}
+
+// the same with the windows on a ring of F frames (tables of im360_cfg_ddim_step_windows_ring).  The host cannot see the tables:
+// the caller guarantees 0 <= start[k] < F, every frame covered, L <= F.
+extern "C" __attribute__((visibility("default"))) int im360_cfg_rescale_stats_windows_ring(const void* pred, const void* start, const void* weight,
+                                   int nW, int64_t outer, int64_t F, int64_t L, int64_t inner, float guidance, void* ws,
+                                   int64_t ws_floats, int dtype, void* stream, const void* coef_dev) {
+    IM360_CHECK_CFG_RESCALE_STATS_WINDOWS("cfg_rescale_stats_windows_ring");
+    return im360::launch_cfg_rescale_stats_windows("cfg_rescale_stats_windows_ring", pred, start, weight, nW, outer, F, L, (int)F, inner,
+                                                   guidance, ws, dtype, stream, coef_dev);
 }
 
 // out[0] = r = phi std(c) / std(m) + (1 - phi) from the records a statistics pass over n elements left in ws
@@ -1372,7 +1398,7 @@ static int launch_cfg_ddim_step(const char* name, const void* uncond, const void
 }
 
 static int launch_cfg_ddim_step_windows(const char* name, const void* pred, const void* x, const void* noise, void* out, const void* start,
-                                        const void* weight, int nW, int64_t outer, int64_t F, int64_t L, int64_t inner, float guidance,
+                                        const void* weight, int nW, int64_t outer, int64_t F, int64_t L, int wrap, int64_t inner, float guidance,
                                         float sqrt_a, float sqrt_b, float sqrt_a_prev, float dir, float sigma, int mode, int dtype,
                                         void* stream, const void* coef_dev, const void* ws, float phi) {
     const bool vec = (inner % 8) == 0 && ((uintptr_t)pred % 16) == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)noise % 16) == 0 &&
@@ -1386,7 +1412,7 @@ static int launch_cfg_ddim_step_windows(const char* name, const void* pred, cons
         with_const<1, 8>(vec ? 8 : 1, [&](auto v) { with_bool(ws != nullptr, [&](auto rs) {
             hipLaunchKernelGGL((cfg_ddim_step_windows_kernel<T, decltype(v)::value, decltype(rs)::value>), dim3(blocks), dim3(256), 0, s,
                                (const T*)pred, (const T*)x, (const T*)noise, (T*)out, (const int*)start, (const float*)weight, nW,
-                               (long)outer, (int)F, (int)L, (long)inner, guidance, sqrt_a, sqrt_b, sqrt_a_prev, dir, sigma, mode,
+                               (long)outer, (int)F, (int)L, wrap, (long)inner, guidance, sqrt_a, sqrt_b, sqrt_a_prev, dir, sigma, mode,
                                (const float*)coef_dev, (const float*)ws, nrec, phi);
         }); });
         IM360_CHECK_LAUNCH();
@@ -1441,7 +1467,7 @@ extern "C" __attribute__((visibility("default"))) int im360_cfg_ddim_step_window
                                    int64_t inner, float guidance, float sqrt_a, float sqrt_b, float sqrt_a_prev, float dir,
                                    float sigma, int mode, int dtype, void* stream, const void* coef_dev) {
     IM360_CHECK_CFG_DDIM_STEP_WINDOWS("cfg_ddim_step_windows");
-    return im360::launch_cfg_ddim_step_windows("cfg_ddim_step_windows", pred, x, noise, out, start, weight, nW, outer, F, L, inner, guidance,
+    return im360::launch_cfg_ddim_step_windows("cfg_ddim_step_windows", pred, x, noise, out, start, weight, nW, outer, F, L, 0, inner, guidance,
                                                sqrt_a, sqrt_b, sqrt_a_prev, dir, sigma, mode, dtype, stream, coef_dev, nullptr, 0.0f);
 }
 
@@ -1454,6 +1480,32 @@ extern "C" __attribute__((visibility("default"))) int im360_cfg_ddim_step_window
     IM360_CHECK_CFG_DDIM_STEP_WINDOWS("cfg_ddim_step_windows_rescale");
     IM360_CHECK_ARG(std::isfinite(phi), "cfg_ddim_step_windows_rescale: rescale=%g must be finite", (double)phi);
     IM360_CHECK_RESCALE_WS("cfg_ddim_step_windows_rescale", outer * F * inner);
-    return im360::launch_cfg_ddim_step_windows("cfg_ddim_step_windows_rescale", pred, x, noise, out, start, weight, nW, outer, F, L, inner,
+    return im360::launch_cfg_ddim_step_windows("cfg_ddim_step_windows_rescale", pred, x, noise, out, start, weight, nW, outer, F, L, 0, inner,
                                                guidance, sqrt_a, sqrt_b, sqrt_a_prev, dir, sigma, mode, dtype, stream, coef_dev, ws, phi);
+}
+
+// im360_cfg_ddim_step_windows with the windows on a ring of F frames: window k covers the frames (start[k] + j) mod F, j = 0 .. L - 1,
+// position j of its prediction.  Same blend, same slot order, same step.  The host cannot see the tables: the caller guarantees
+// 0 <= start[k] < F, every frame covered, L <= F (imagine360_amd/context.py, loop=True).
+extern "C" __attribute__((visibility("default"))) int im360_cfg_ddim_step_windows_ring(const void* pred, const void* x, const void* noise, void* out,
+                                   const void* start, const void* weight, int nW, int64_t outer, int64_t F, int64_t L,
+                                   int64_t inner, float guidance, float sqrt_a, float sqrt_b, float sqrt_a_prev, float dir,
+                                   float sigma, int mode, int dtype, void* stream, const void* coef_dev) {
+    IM360_CHECK_CFG_DDIM_STEP_WINDOWS("cfg_ddim_step_windows_ring");
+    return im360::launch_cfg_ddim_step_windows("cfg_ddim_step_windows_ring", pred, x, noise, out, start, weight, nW, outer, F, L, (int)F, inner,
+                                               guidance, sqrt_a, sqrt_b, sqrt_a_prev, dir, sigma, mode, dtype, stream, coef_dev, nullptr, 0.0f);
+}
+
+// the same on r times the blend, r from the records im360_cfg_rescale_stats_windows_ring left in ws for the same clip; the
+// precondition of im360_cfg_ddim_step_windows_ring: 0 <= start[k] < F, every frame covered, L <= F
+extern "C" __attribute__((visibility("default"))) int im360_cfg_ddim_step_windows_ring_rescale(const void* pred, const void* x, const void* noise,
+                                   void* out, const void* start, const void* weight, int nW, int64_t outer, int64_t F, int64_t L,
+                                   int64_t inner, float guidance, float sqrt_a, float sqrt_b, float sqrt_a_prev, float dir,
+                                   float sigma, int mode, float phi, const void* ws, int64_t ws_floats, int dtype, void* stream,
+                                   const void* coef_dev) {
+    IM360_CHECK_CFG_DDIM_STEP_WINDOWS("cfg_ddim_step_windows_ring_rescale");
+    IM360_CHECK_ARG(std::isfinite(phi), "cfg_ddim_step_windows_ring_rescale: rescale=%g must be finite", (double)phi);
+    IM360_CHECK_RESCALE_WS("cfg_ddim_step_windows_ring_rescale", outer * F * inner);
+    return im360::launch_cfg_ddim_step_windows("cfg_ddim_step_windows_ring_rescale", pred, x, noise, out, start, weight, nW, outer, F, L, (int)F,
+                                               inner, guidance, sqrt_a, sqrt_b, sqrt_a_prev, dir, sigma, mode, dtype, stream, coef_dev, ws, phi);
 }

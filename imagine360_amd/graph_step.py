@@ -163,7 +163,8 @@ class GraphedDenoiseStep:
 
 class GraphedWindowedStep(GraphedDenoiseStep):
     """One denoising step over sliding temporal context windows (imagine360_amd.context) in ONE hipGraph: the forwards of all
-    windows in ascending order, each reading its frames of the full-length model-input buffers and its own cached conditioning
+    windows in slot order, each reading its frames of the full-length model-input buffers (a window of a looping plan that crosses
+    the end of the clip gathers them with one index_select per buffer, inside the capture) and its own cached conditioning
     and writing its prediction into slot k of the [nW, 2, ...] buffers, then the blend + CFG + DDIM kernel of each branch.
     Captured: the nW forwards with their IP-adapter noise draws, (eta > 0) the two whole-clip variance noises, both updates.
     Not captured, per step on the host: three small pinned uploads -- the timestep, the six coefficients, the [nW, 8] table of
@@ -190,7 +191,8 @@ class GraphedWindowedStep(GraphedDenoiseStep):
         self.plan.forward(self.mv, inp, self.static, self.cams, self.timestep, self.use_fps, self.preds_pers, self.preds_pano,
                           coins=self.coins)
         mdt = self.mv.unet.dtype
-        kw = dict(coef_dev=self.coef, eta=self.eta, use_clipped_model_output=self.clipped, guidance_rescale=self.rescale)
+        kw = dict(coef_dev=self.coef, eta=self.eta, use_clipped_model_output=self.clipped, guidance_rescale=self.rescale,
+                  ring=self.plan.loop)
         new_pano = self.sch.fused_cfg_step_windows(self.preds_pano, self.plan.starts_dev, self.plan.weights, self.g, None,
                                                    self.pano_lat, noise=self._noise(self.pano_lat, mdt, 2), **kw)
         new_pers = self.sch.fused_cfg_step_windows(self.preds_pers, self.plan.starts_dev, self.plan.weights, self.g, None,

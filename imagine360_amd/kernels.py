@@ -60,6 +60,10 @@ _SIGNATURES = {
     "im360_cfg_ddim_step_rescale": (_INT, [_PTR] * 5 + [_I64] + [_F32] * 6 + [_INT, _F32, _PTR, _I64, _INT, _PTR, _PTR]),
     "im360_cfg_ddim_step_windows_rescale": (_INT, [_PTR] * 6 + [_INT] + [_I64] * 4 + [_F32] * 6 + [_INT, _F32, _PTR, _I64, _INT, _PTR,
                                                                                                   _PTR]),
+    "im360_cfg_ddim_step_windows_ring": (_INT, [_PTR] * 6 + [_INT] + [_I64] * 4 + [_F32] * 6 + [_INT, _INT, _PTR, _PTR]),
+    "im360_cfg_rescale_stats_windows_ring": (_INT, [_PTR] * 3 + [_INT] + [_I64] * 4 + [_F32, _PTR, _I64, _INT, _PTR, _PTR]),
+    "im360_cfg_ddim_step_windows_ring_rescale": (_INT, [_PTR] * 6 + [_INT] + [_I64] * 4 + [_F32] * 6 + [_INT, _F32, _PTR, _I64, _INT,
+                                                                                                       _PTR, _PTR]),
     "im360_layernorm": (_INT, [_PTR] * 6 + [_I64] * 5 + [_F32, _INT, _PTR]),
     "im360_geglu": (_INT, [_PTR] * 2 + [_I64] * 2 + [_INT, _PTR]),
     "im360_linear_geglu": (_INT, [_PTR] * 4 + [_I64] * 3 + [_INT, _PTR]),
@@ -915,14 +919,8 @@ def cfg_ddim_step(uncond, cond, sample, noise, mode, coefs, coef_dev=None, resca
     return out
 
 
-def cfg_ddim_step_windows(preds, sample, noise, starts, weights, mode, coefs, coef_dev=None, rescale=0.0):
-    """``cfg_ddim_step`` on the per-frame weighted blend of sliding-window predictions, one pass.  ``sample`` (and ``noise`` /
-    the result): a panorama latent [1, 4, F, H, W] or a perspective latent [1, m, 4, F, h, w];  ``preds`` [nW, 2, *sample.shape
-    with F -> L]: window k's CFG-batched prediction in slot k;  ``starts`` device int32 [nW] ascending window start frames
-    (context.context_windows);  ``weights`` device float32 [L] (context.context_weights).  ``mode`` / ``coefs`` / ``coef_dev`` as in
-    ``cfg_ddim_step``.  ``rescale`` != 0: guidance rescale with both standard deviations over the whole clip of blends (the text
-    halves blended with the same weights), a statistics launch in front of the step launch."""
-    _dev(preds, sample, noise, starts, weights)
+def _windows_geometry(preds, sample, starts, weights):
+    """(nW, outer, F, L, inner) of a windowed step after the layout checks of ``cfg_ddim_step_windows``."""
     assert preds.is_contiguous() and sample.is_contiguous() and preds.dtype == sample.dtype
     assert sample.dim() in (5, 6) and sample.shape[0] == 1, "sample must be [1, 4, F, H, W] or [1, m, 4, F, h, w]"
     fd = sample.dim() - 3
@@ -931,6 +929,41 @@ def cfg_ddim_step_windows(preds, sample, noise, starts, weights, mode, coefs, co
     assert tuple(preds.shape) == (nW, 2, *sample.shape[1:fd], L, *sample.shape[fd + 1:]), (tuple(preds.shape), tuple(sample.shape))
     assert starts.dtype == torch.int32 and starts.is_contiguous() and starts.numel() == nW
     assert weights.dtype == torch.float32 and weights.is_contiguous() and weights.numel() == L and 1 <= L <= F
+    return nW, outer, F, L, inner
+
+
+def _rescale_stats_windows(preds, sample, starts, weights, geometry, guidance, coef_dev, ring):
+    ws = _rescale_workspace(sample)
+    name = "im360_cfg_rescale_stats_windows_ring" if ring else "im360_cfg_rescale_stats_windows"
+    rc = getattr(lib(), name)(_p(preds), _p(starts), _p(weights), *geometry, float(guidance), _p(ws), ws.numel(), _dt(sample), _stream(),
+                              _p(coef_dev))
+    _check(rc, name)
+    return ws
+
+
+def cfg_rescale_factor_windows(preds, sample, starts, weights, guidance, rescale, coef_dev=None, ring=False):
+    """``cfg_rescale_factor`` over the per-frame blends of sliding-window predictions (arguments of ``cfg_ddim_step_windows``; only
+    the shape of ``sample`` is used): the statistics pass ``cfg_ddim_step_windows(..., rescale=)`` runs, then the merge every
+    workgroup of its step kernel makes.  A device float32 scalar, no synchronisation.  ``ring``: the windows lie on a ring."""
+    _dev(preds, sample, starts, weights, coef_dev)
+    geometry = _windows_geometry(preds, sample, starts, weights)
+    ws = _rescale_stats_windows(preds, sample, starts, weights, geometry, guidance, coef_dev, ring)
+    out = torch.empty((), dtype=torch.float32, device=sample.device)
+    _check(lib().im360_cfg_rescale_factor(_p(ws), ws.numel(), sample.numel(), float(rescale), _p(out), _stream()), "im360_cfg_rescale_factor")
+    return out
+
+
+def cfg_ddim_step_windows(preds, sample, noise, starts, weights, mode, coefs, coef_dev=None, rescale=0.0, ring=False):
+    """``cfg_ddim_step`` on the per-frame weighted blend of sliding-window predictions, one pass.  ``sample`` (and ``noise`` /
+    the result): a panorama latent [1, 4, F, H, W] or a perspective latent [1, m, 4, F, h, w];  ``preds`` [nW, 2, *sample.shape
+    with F -> L]: window k's CFG-batched prediction in slot k;  ``starts`` device int32 [nW] ascending window start frames
+    (context.context_windows);  ``weights`` device float32 [L] (context.context_weights).  ``mode`` / ``coefs`` / ``coef_dev`` as in
+    ``cfg_ddim_step``.  ``rescale`` != 0: guidance rescale with both standard deviations over the whole clip of blends (the text
+    halves blended with the same weights), a statistics launch in front of the step launch.  ``ring``: the windows lie on a ring
+    of F frames (context.context_windows(loop=True)) -- window k covers the frames (starts[k] + j) mod F, 0 <= starts[k] < F; the
+    ``_ring`` entry points, the same blend and step."""
+    _dev(preds, sample, noise, starts, weights)
+    nW, outer, F, L, inner = geometry = _windows_geometry(preds, sample, starts, weights)
     if noise is not None:
         assert noise.is_contiguous() and noise.shape == sample.shape and noise.dtype == sample.dtype
     elif coef_dev is None and coefs[5] != 0.0:
@@ -939,18 +972,17 @@ def cfg_ddim_step_windows(preds, sample, noise, starts, weights, mode, coefs, co
         assert coef_dev.dtype == torch.float32 and coef_dev.numel() == 6 and coef_dev.is_cuda
     out = torch.empty_like(sample)
     if rescale != 0.0:
-        ws = _rescale_workspace(sample)
-        rc = lib().im360_cfg_rescale_stats_windows(_p(preds), _p(starts), _p(weights), nW, outer, F, L, inner, float(coefs[0]), _p(ws),
-                                                   ws.numel(), _dt(sample), _stream(), _p(coef_dev))
-        _check(rc, "im360_cfg_rescale_stats_windows")
-        rc = lib().im360_cfg_ddim_step_windows_rescale(_p(preds), _p(sample), _p(noise), _p(out), _p(starts), _p(weights), nW, outer, F,
-                                                       L, inner, *(float(v) for v in coefs), int(mode), float(rescale), _p(ws),
-                                                       ws.numel(), _dt(sample), _stream(), _p(coef_dev))
-        _check(rc, "im360_cfg_ddim_step_windows_rescale")
+        ws = _rescale_stats_windows(preds, sample, starts, weights, geometry, coefs[0], coef_dev, ring)
+        name = "im360_cfg_ddim_step_windows_ring_rescale" if ring else "im360_cfg_ddim_step_windows_rescale"
+        rc = getattr(lib(), name)(_p(preds), _p(sample), _p(noise), _p(out), _p(starts), _p(weights), nW, outer, F, L, inner,
+                                  *(float(v) for v in coefs), int(mode), float(rescale), _p(ws), ws.numel(), _dt(sample), _stream(),
+                                  _p(coef_dev))
+        _check(rc, name)
         return out
-    rc = lib().im360_cfg_ddim_step_windows(_p(preds), _p(sample), _p(noise), _p(out), _p(starts), _p(weights), nW, outer, F, L,
-                                           inner, *(float(v) for v in coefs), int(mode), _dt(sample), _stream(), _p(coef_dev))
-    _check(rc, "im360_cfg_ddim_step_windows")
+    name = "im360_cfg_ddim_step_windows_ring" if ring else "im360_cfg_ddim_step_windows"
+    rc = getattr(lib(), name)(_p(preds), _p(sample), _p(noise), _p(out), _p(starts), _p(weights), nW, outer, F, L, inner,
+                              *(float(v) for v in coefs), int(mode), _dt(sample), _stream(), _p(coef_dev))
+    _check(rc, name)
     return out
 
 

@@ -218,7 +218,8 @@ class AnimationPipeline:
                  output_type="tensor", return_dict=True, callback=None, callback_steps=1, latents_dtype=torch.float16,
                  video_batch=None, use_outpaint=False, use_ip_plus_cross_attention=False, use_fps_condition=False,
                  ip_plus_condition="image", prompt_embeds=None, sam_features=None, trace=None, frame_shard=None,
-                 context_frames=None, context_overlap=4, context_weights="pyramid", guidance_rescale=0.0, **kwargs):
+                 context_frames=None, context_overlap=4, context_weights="pyramid", guidance_rescale=0.0, context_loop=False,
+                 **kwargs):
         """``frame_shard`` (imagine360_amd.dist.FrameShard): this rank denoises a contiguous chunk of the frames (BASELINE
         configs 4 / 5); all ranks must be called with the same seeds and inputs.  Noise is drawn for the whole clip and
         cut, the VAE encodes / the loop runs / the VAE decodes only the local frames, the motion modules exchange tokens
@@ -228,6 +229,10 @@ class AnimationPipeline:
         every window, which lifts the temporal_position_encoding_max_len ceiling), ``context_overlap`` frames shared between
         neighbours, and the windows' predictions are blended per frame with ``context_weights`` ("pyramid" / "uniform") inside
         the CFG + DDIM kernel.  ``context_frames >= video_length`` is the call without it.
+        ``context_loop`` (False: off): the clip is played as a loop -- the windows lie on a ring of ``video_length`` frames
+        (context_windows(loop=True)), so a window that crosses the end of the clip shows the motion modules ... F-2, F-1, 0, 1 ...
+        as consecutive frames and the loop point is denoised like every other pair of neighbours.  Needs ``context_frames <
+        video_length`` (one window cannot wrap); not with ``frame_shard``.
         ``guidance_rescale`` (0.0: off; the paper uses 0.7): ``scheduler.rescale_noise_cfg`` on each branch's guided prediction
         before the update (arXiv 2305.08891, section 3.4: with zero-terminal-SNR betas a guidance of 7.5 over-exposes without it),
         the standard deviations over the whole panorama latent / over all views of the perspective latent (with context windows:
@@ -239,11 +244,16 @@ class AnimationPipeline:
         if guidance_rescale != 0.0 and frame_shard is not None:
             raise ValueError("guidance_rescale cannot be combined with frame_shard (the standard deviations span the frames of all "
                              "ranks and would need an all-reduce inside the step, which is not implemented)")
+        if context_loop and frame_shard is not None:
+            raise ValueError("context_loop cannot be combined with frame_shard (windows under frame sharding are not implemented)")
+        if context_loop and (context_frames is None or int(context_frames) >= vb["video_length"]):
+            raise ValueError(f"context_loop needs context_frames < video_length = {vb['video_length']} (one window cannot wrap around), "
+                             f"got context_frames={context_frames}")
         if context_frames is not None and int(context_frames) < vb["video_length"]:
             if frame_shard is not None:
                 raise ValueError("context_frames cannot be combined with frame_shard (windows under frame sharding are not implemented)")
             from .context import WindowPlan
-            plan = WindowPlan(vb["video_length"], context_frames, context_overlap, context_weights, device)
+            plan = WindowPlan(vb["video_length"], context_frames, context_overlap, context_weights, device, loop=bool(context_loop))
         assert use_outpaint and use_ip_plus_cross_attention, "the dual pipeline runs with use_outpaint and the IP adapter"
         cfg = guidance_scale_text > 1.0
         assert cfg, "the reference only binds its model inputs under classifier-free guidance (:744-751)"
@@ -358,7 +368,7 @@ class AnimationPipeline:
 
     def _windowed_loop(self, plan, inputs, cameras, pano_latent, pers_latent, steps_host, ts_dev, g, use_fps, eta, generator,
                        trace, callback, callback_steps, guidance_rescale=0.0):
-        """The denoising loop over sliding temporal context windows: per step one forward per window (ascending), then ONE
+        """The denoising loop over sliding temporal context windows: per step one forward per window (slot order), then ONE
         blend + CFG + DDIM kernel per branch, panorama first.  RNG: as len(plan) successive calls of the model, then (eta > 0)
         the whole clip's panorama and perspective variance noise.  Captured in one hipGraph under the conditions of the
         one-block loop (graph_step.GraphedWindowedStep), issued eagerly otherwise."""
@@ -379,7 +389,7 @@ class AnimationPipeline:
                 inputs["latents"][:, :, :4] = pers_latent
                 plan.forward(mv, inputs, static, cameras, ts_dev[i], use_fps, preds_pers, preds_pano)
                 mdt = mv.unet.dtype
-                kw = dict(eta=eta, guidance_rescale=guidance_rescale)
+                kw = dict(eta=eta, guidance_rescale=guidance_rescale, ring=plan.loop)
                 z = variance_noise(sch, pano_latent, mdt, generator, self.rng) if eta > 0 else None
                 pano_latent = sch.fused_cfg_step_windows(preds_pano, plan.starts_dev, plan.weights, g, t, pano_latent, noise=z, **kw)
                 z = variance_noise(sch, pers_latent, mdt, generator, self.rng, frame_dim=3) if eta > 0 else None

@@ -73,6 +73,12 @@ def _rescale_kw(guidance_rescale):
     return dict(rescale=float(guidance_rescale)) if guidance_rescale != 0.0 else {}
 
 
+def _ring_kw(ring):
+    """``ring=True`` for kernels.cfg_ddim_step_windows, left out for the linear plan: it is then called with exactly the arguments
+    of before."""
+    return dict(ring=True) if ring else {}
+
+
 class DDIMScheduler:
     order = 1
 
@@ -223,16 +229,18 @@ class DDIMScheduler:
                                      self.kernel_mode(use_clipped_model_output), coefs, coef_dev=coef_dev, **_rescale_kw(guidance_rescale))
 
     def fused_cfg_step_windows(self, preds, starts, weights, guidance_scale, timestep, sample, coef_dev=None, *, eta=0.0,
-                               noise=None, use_clipped_model_output=False, guidance_rescale=0.0):
+                               noise=None, use_clipped_model_output=False, guidance_rescale=0.0, ring=False):
         """``fused_cfg_step`` over sliding temporal context windows: the per-frame weighted blend of the windows' CFG-combined
         predictions + the update, one HIP kernel (``kernels.cfg_ddim_step_windows``).  ``preds`` [nW, 2, ...]: window k's
         CFG-batched prediction in slot k, in ``sample``'s layout with L frames;  ``starts`` device int32 [nW], ``weights`` device
         float32 [L] (imagine360_amd.context).  The step kernel serves eta = 0 as well, so ``coef_dev`` is always float32[6] =
         ``step_coefficients``.  ``guidance_rescale`` != 0: ``rescale_noise_cfg`` on the blends (guided and text), the standard
-        deviations over the whole clip."""
+        deviations over the whole clip.  ``ring``: the windows of a looping clip (context.WindowPlan(loop=True)), ``starts`` on a
+        ring of F frames."""
         if eta > 0 and noise is None:
             raise ValueError("fused_cfg_step_windows: eta > 0 needs the variance noise")
         x = sample.contiguous()
         coefs = (0.0,) * 6 if coef_dev is not None else self.step_coefficients(timestep, eta, guidance_scale)
         return kernels.cfg_ddim_step_windows(preds.contiguous(), x, noise.to(x.dtype).contiguous() if eta > 0 else None, starts,
-                                             weights, self.kernel_mode(use_clipped_model_output), coefs, coef_dev=coef_dev, **_rescale_kw(guidance_rescale))
+                                             weights, self.kernel_mode(use_clipped_model_output), coefs, coef_dev=coef_dev, **_rescale_kw(guidance_rescale),
+                                             **_ring_kw(ring))

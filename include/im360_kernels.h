@@ -311,6 +311,35 @@ int im360_cfg_ddim_step_windows_rescale(const void* pred, const void* x, const v
                                         int mode, float phi, const void* ws, int64_t ws_floats, int dtype, void* stream,
                                         const void* coef_dev);
 
+/* ---- the windows of a looping clip: im360_cfg_ddim_step_windows with the windows placed on a ring of F frames.  Window k covers
+ * the frames (start[k] + j) mod F, j = 0 .. L - 1, and position j of its prediction belongs to that frame: per element at frame f
+ * the position is j = f - start[k], plus F when that is negative, and the window takes part when 0 <= j < L.  Blend, slot order
+ * (k ascending), step, lanes and arguments are those of im360_cfg_ddim_step_windows; with tables no window of which crosses the
+ * end of the clip the result is that entry point's, bit for bit.
+ * Precondition (the host cannot see the tables): 0 <= start[k] < F, every frame covered, L <= F.
+ * Replaces: nothing in the reference (it has no temporal windows). */
+int im360_cfg_ddim_step_windows_ring(const void* pred, const void* x, const void* noise, void* out, const void* start,
+                                     const void* weight, int nW, int64_t outer, int64_t F, int64_t L, int64_t inner, float guidance,
+                                     float sqrt_a, float sqrt_b, float sqrt_a_prev, float dir, float sigma, int mode, int dtype,
+                                     void* stream, const void* coef_dev);
+
+/* im360_cfg_rescale_stats_windows over the blends of windows on a ring: tables and positions of
+ * im360_cfg_ddim_step_windows_ring, everything else as in the linear entry point.
+ * Precondition: 0 <= start[k] < F, every frame covered, L <= F.
+ * Replaces: nothing in the reference. */
+int im360_cfg_rescale_stats_windows_ring(const void* pred, const void* start, const void* weight, int nW, int64_t outer, int64_t F,
+                                         int64_t L, int64_t inner, float guidance, void* ws, int64_t ws_floats, int dtype,
+                                         void* stream, const void* coef_dev);
+
+/* im360_cfg_ddim_step_windows_ring on r * m, r from the records of im360_cfg_rescale_stats_windows_ring over the same clip.
+ * Precondition: 0 <= start[k] < F, every frame covered, L <= F.
+ * Replaces: nothing in the reference. */
+int im360_cfg_ddim_step_windows_ring_rescale(const void* pred, const void* x, const void* noise, void* out, const void* start,
+                                             const void* weight, int nW, int64_t outer, int64_t F, int64_t L, int64_t inner,
+                                             float guidance, float sqrt_a, float sqrt_b, float sqrt_a_prev, float dir, float sigma,
+                                             int mode, float phi, const void* ws, int64_t ws_floats, int dtype, void* stream,
+                                             const void* coef_dev);
+
 /* y[r] = LayerNorm(x[r] + pre[r % pre_period]) * gamma + beta + post[(r / post_div) % post_mod] on token rows
  * [rows, C]; pre / post are optional [*, C] tables (the WarpAttn spherical PE added before norm1, the motion
  * module's frame PE added after the norm).

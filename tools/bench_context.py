@@ -5,7 +5,11 @@
 synchronise; and the blend + CFG + DDIM kernel alone next to cfg_ddim_step_kernel on the same perspective latent, timed with
 device events, with the bytes each has to move computed from the shapes.  Prints one line of JSON (and writes it to --out).
     python tools/bench_context.py [--steps 3] [--rounds 3] [--kernel-iters 200] [--out profiles/context_windows.json]
-    python tools/bench_context.py --kernel-only       # skip the two whole steps"""
+    python tools/bench_context.py --kernel-only       # skip the two whole steps
+    python tools/bench_context.py --loop [--passes 2] # the looping clip: the ring plan's captured step next to the linear plan's (same F, L,
+                                                      # overlap; ms per step and per window), and the ring entry point of the blend kernel next to
+                                                      # the linear one on the SAME non-wrapping tables and on the ring's own; every measurement is
+                                                      # made --passes times over, so the spread between identical passes stands next to the numbers"""
 import argparse
 import json
 import os
@@ -28,12 +32,14 @@ def kernel_bytes(sample, plan):
     """Bytes the two kernels have to move for ``sample`` (no variance noise): the windowed one reads both CFG halves of every
     window once (2 x sum of coverage) + the sample and writes one latent; the plain one reads uncond, cond, sample and writes one."""
     per_frame = sample.numel() // plan.frames * sample.element_size()
-    cov = sum(coverage(plan.frames, plan.length, plan.starts))
+    cov = sum(coverage(plan.frames, plan.length, plan.starts, loop=plan.loop))
     return dict(windows=(2 * cov + 2 * plan.frames) * per_frame, plain=4 * plan.frames * per_frame)
 
 
-def time_kernels(sch, plan, sample, iters, rounds=5):
-    """Device-event time of the two kernels on ``sample`` (alternated round by round, ``iters`` back-to-back launches each)."""
+def time_kernels(sch, plan, sample, iters, rounds=5, ring_plan=None):
+    """Device-event time of the two kernels on ``sample`` (alternated round by round, ``iters`` back-to-back launches each).
+    ``ring_plan``: instead the linear entry point, the ring entry point on the same (non-wrapping) tables, and the ring entry point on
+    the ring plan's tables."""
     t = sch._timesteps_host[8]
     coefs = sch.step_coefficients(t, 0.0, 7.5)
     mode = sch.kernel_mode()
@@ -44,6 +50,12 @@ def time_kernels(sch, plan, sample, iters, rounds=5):
     u, c = (torch.randn(sample.shape, device=sample.device).to(sample.dtype) for _ in range(2))
     fns = dict(windows=lambda: kernels.cfg_ddim_step_windows(preds, sample, None, plan.starts_dev, plan.weights, mode, coefs),
                plain=lambda: kernels.cfg_ddim_step(u, c, sample, None, mode, coefs))
+    if ring_plan is not None:
+        assert len(ring_plan) == len(plan) and ring_plan.length == plan.length        # the same prediction buffer serves all three
+        fns = dict(linear=fns["windows"],
+                   ring_entry_linear_tables=lambda: kernels.cfg_ddim_step_windows(preds, sample, None, plan.starts_dev, plan.weights, mode, coefs,
+                                                                                  ring=True),
+                   ring=lambda: kernels.cfg_ddim_step_windows(preds, sample, None, ring_plan.starts_dev, ring_plan.weights, mode, coefs, ring=True))
     times = {k: [] for k in fns}
     for r in range(rounds + 1):
         for name, fn in fns.items():
@@ -59,12 +71,77 @@ def time_kernels(sch, plan, sample, iters, rounds=5):
     return {k: dict(us_min=min(v), us_median=statistics.median(v)) for k, v in times.items()}
 
 
+def time_steps(graphs, ts_host, steps, rounds):
+    """Host-clock ms per step of captured steps, replays alternated round by round; round 0 warms every graph up."""
+    times = {k: [] for k in graphs}
+    for r in range(rounds + 1):
+        for name, gs in graphs.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for i in range(steps):
+                gs.step(ts_host[i % len(ts_host)])
+            torch.cuda.synchronize()
+            if r:
+                times[name].append((time.perf_counter() - t0) / steps * 1e3)
+    return {k: dict(ms_min=min(v), ms_median=statistics.median(v), rounds=len(v), steps_per_round=steps) for k, v in times.items()}
+
+
+def spread(passes, key):
+    """Largest relative difference of ``key`` between identical passes."""
+    v = [p[key] for p in passes]
+    return (max(v) - min(v)) / min(v)
+
+
+def loop_bench(args, sch, dev, dt, ts_host):
+    """--loop: the ring plan against the linear plan of the same frames / length / overlap."""
+    line = WindowPlan(FRAMES, LENGTH, OVERLAP, "pyramid", dev)
+    ring = WindowPlan(FRAMES, LENGTH, OVERLAP, "pyramid", dev, loop=True)
+    res = dict(tool="bench_context --loop", frames=FRAMES, context_frames=LENGTH, context_overlap=OVERLAP, linear_windows=line.starts,
+               ring_windows=ring.starts, pano_hw=PANO_HW, pers_hw=PERS_HW, dtype="bfloat16", device=torch.cuda.get_device_name(0),
+               passes=args.passes)
+    pers = torch.randn(1, 20, 4, FRAMES, *PERS_HW, device=dev).to(dt)
+    kp = [time_kernels(sch, line, pers, args.kernel_iters, ring_plan=ring) for _ in range(args.passes)]
+    res["blend_kernel"] = {k: dict(us_min=[p[k]["us_min"] for p in kp], us_median=[p[k]["us_median"] for p in kp],
+                                   spread_between_passes=spread([p[k] for p in kp], "us_min")) for k in kp[0]}
+    best = {k: min(v["us_min"]) for k, v in res["blend_kernel"].items()}
+    res["blend_kernel"]["ring_entry_over_linear_same_tables"] = best["ring_entry_linear_tables"] / best["linear"]
+    res["blend_kernel"]["ring_over_linear"] = best["ring"] / best["linear"]
+    res["blend_kernel"]["tensor"] = list(pers.shape)
+    res["blend_kernel"]["bytes"] = dict(linear=kernel_bytes(pers, line)["windows"], ring=kernel_bytes(pers, ring)["windows"])
+    if not args.kernel_only:
+        mv = configs.build_mv_model(1, device=dev, dtype=dt, xformers=True)
+        mv.dual_stream, mv.warp_streams = True, True
+        inp = synthetic.mv_inputs(frames=FRAMES, pano_hw=PANO_HW, pers_hw=PERS_HW, seed=1, dtype=dt, device=dev)
+        inp.pop("timestep")
+        cams = synthetic.icosahedron_cameras(90, PERS_PX, device=dev)
+        pano_lat, pers_lat = inp["pano_latent"][:1, :4].contiguous(), inp["latents"][:1, :, :4].contiguous()
+        from imagine360_amd.graph_step import GraphedWindowedStep
+        graphs = {}
+        for name, plan in (("linear_step", line), ("ring_step", ring)):
+            with ip_cache_slots(mv, len(plan)):
+                graphs[name] = GraphedWindowedStep(mv, sch, inp, cams, pano_lat, pers_lat, 7.5, plan, warmup=1)
+            torch.cuda.synchronize()
+            print(f"captured: {name}", file=sys.stderr, flush=True)
+        sp = [time_steps(graphs, ts_host, args.steps, args.rounds) for _ in range(args.passes)]
+        for name, plan in (("linear_step", line), ("ring_step", ring)):
+            ms = min(p[name]["ms_min"] for p in sp)
+            res[name] = dict(ms_min=[p[name]["ms_min"] for p in sp], ms_median=[p[name]["ms_median"] for p in sp], windows=len(plan),
+                             ms_per_window=ms / len(plan), spread_between_passes=spread([p[name] for p in sp], "ms_min"),
+                             rounds=args.rounds, steps_per_round=args.steps)
+        res["ring_over_linear_step"] = min(res["ring_step"]["ms_min"]) / min(res["linear_step"]["ms_min"])
+        res["ring_over_linear_per_window"] = res["ring_step"]["ms_per_window"] / res["linear_step"]["ms_per_window"]
+        res["finite"] = bool(all(torch.isfinite(g.pano_lat.float()).all() and torch.isfinite(g.pers_lat.float()).all() for g in graphs.values()))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--kernel-iters", type=int, default=200)
     ap.add_argument("--kernel-only", action="store_true")
+    ap.add_argument("--loop", action="store_true", help="the ring plan of a looping clip against the linear plan")
+    ap.add_argument("--passes", type=int, default=2, help="--loop: identical passes of every measurement")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_context.py measures on the MI355X; there is nothing to time without one"
@@ -74,6 +151,8 @@ def main():
     sch = DDIMScheduler(**configs.NOISE_SCHEDULER_KWARGS)
     sch.set_timesteps(25)
     ts_host = [int(t) for t in sch._timesteps_host]
+    if args.loop:
+        return emit(loop_bench(args, sch, dev, dt, ts_host), args.out)
     plan = WindowPlan(FRAMES, LENGTH, OVERLAP, "pyramid", dev)
     res = dict(tool="bench_context", frames=FRAMES, context_frames=LENGTH, context_overlap=OVERLAP, windows=plan.starts,
                pano_hw=PANO_HW, pers_hw=PERS_HW, dtype="bfloat16", device=torch.cuda.get_device_name(0))
@@ -101,24 +180,17 @@ def main():
         torch.cuda.synchronize()
         print("captured: 48-frame full-attention step", file=sys.stderr, flush=True)
         graphs = dict(windowed_step=windowed, full_attention_step=full)
-        times = {k: [] for k in graphs}
-        for r in range(args.rounds + 1):
-            for name, gs in graphs.items():
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                for i in range(args.steps):
-                    gs.step(ts_host[i % len(ts_host)])
-                torch.cuda.synchronize()
-                if r:                               # round 0 warms every graph up
-                    times[name].append((time.perf_counter() - t0) / args.steps * 1e3)
-        for name, v in times.items():
-            res[name] = dict(ms_min=min(v), ms_median=statistics.median(v), rounds=len(v), steps_per_round=args.steps)
+        res.update(time_steps(graphs, ts_host, args.steps, args.rounds))
         res["finite"] = bool(torch.isfinite(windowed.pano_lat.float()).all() and torch.isfinite(windowed.pers_lat.float()).all())
+    emit(res, args.out)
+
+
+def emit(res, out):
     line = json.dumps(res)
     print(line, flush=True)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as fh:
             fh.write(line + "\n")
 
 
