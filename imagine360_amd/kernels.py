@@ -692,7 +692,7 @@ def layer_norm(x, gamma, beta, eps=1e-5, pre=None, post=None, post_div=1):
     C = x.shape[-1]
     assert x.is_contiguous() and gamma.dtype == x.dtype
     rows = x.numel() // C
-    y = torch.empty_like(x)
+    y = torch.empty(x.shape, dtype=x.dtype, device=x.device)
     for t in (pre, post):
         assert t is None or (t.is_contiguous() and t.shape[-1] == C and t.dtype == x.dtype)
     rc = lib().im360_layernorm(_p(x), _p(gamma), _p(beta), _p(pre), _p(post), _p(y), rows, C,
@@ -756,7 +756,7 @@ def softmax_rows(x, scale=1.0, out=None):
     _dev(x, out)
     assert x.dim() == 2 and x.stride(1) == 1
     if out is None:
-        out = torch.empty_like(x)
+        out = torch.empty(x.shape, dtype=x.dtype, device=x.device)
     else:
         _written(out)
     rc = lib().im360_softmax_rows(_p(x), _p(out), x.shape[0], x.shape[1], x.stride(0), out.stride(0), float(scale),
@@ -847,7 +847,7 @@ def cfg_ddim_update(uncond, cond, sample, guidance, cx, cv, coef_dev=None):
     _dev(uncond, cond, sample)
     assert uncond.is_contiguous() and cond.is_contiguous() and sample.is_contiguous()
     assert uncond.shape == cond.shape == sample.shape and uncond.dtype == sample.dtype
-    out = torch.empty_like(sample)
+    out = torch.empty(sample.shape, dtype=sample.dtype, device=sample.device)
     rc = lib().im360_cfg_ddim_update(_p(uncond), _p(cond), _p(sample), _p(out), sample.numel(),
                                      float(guidance), float(cx), float(cv), _dt(sample), _stream(), _p(coef_dev))
     _check(rc, "im360_cfg_ddim_update")
@@ -905,7 +905,7 @@ def cfg_ddim_step(uncond, cond, sample, noise, mode, coefs, coef_dev=None, resca
         raise ValueError("cfg_ddim_step: sigma > 0 needs a noise tensor")
     if coef_dev is not None:
         assert coef_dev.dtype == torch.float32 and coef_dev.numel() == 6 and coef_dev.is_cuda
-    out = torch.empty_like(sample)
+    out = torch.empty(sample.shape, dtype=sample.dtype, device=sample.device)
     if rescale != 0.0:
         ws = _rescale_stats(uncond, cond, coefs[0], coef_dev)
         rc = lib().im360_cfg_ddim_step_rescale(_p(uncond), _p(cond), _p(sample), _p(noise), _p(out), sample.numel(),
@@ -970,7 +970,7 @@ def cfg_ddim_step_windows(preds, sample, noise, starts, weights, mode, coefs, co
         raise ValueError("cfg_ddim_step_windows: sigma > 0 needs a noise tensor")
     if coef_dev is not None:
         assert coef_dev.dtype == torch.float32 and coef_dev.numel() == 6 and coef_dev.is_cuda
-    out = torch.empty_like(sample)
+    out = torch.empty(sample.shape, dtype=sample.dtype, device=sample.device)
     if rescale != 0.0:
         ws = _rescale_stats_windows(preds, sample, starts, weights, geometry, coefs[0], coef_dev, ring)
         name = "im360_cfg_ddim_step_windows_ring_rescale" if ring else "im360_cfg_ddim_step_windows_rescale"

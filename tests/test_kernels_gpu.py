@@ -842,6 +842,25 @@ def test_bad_arguments_fail_loudly():
         K.attention(x.cpu(), x.cpu(), x.cpu(), heads=1)
     with pytest.raises(TypeError):
         K.group_norm(torch.zeros(1, 2, 2, 32, device="cuda"), torch.ones(32, device="cuda"), torch.zeros(32, device="cuda"), 32, 1e-5)
+    # a base pointer 2 bytes off its alignment: refused by the host check of an entry point of every .hip file that takes 16-bit tensors
+    # (preprocess.hip checks float32 / int16 tables, which a tensor view cannot put 2 bytes off), before any launch
+    # (the result the wrapper allocated still holds the guard pattern in every element)
+    from _guarded import PATTERN, Guarded
+    bf = torch.bfloat16
+    ones = lambda *shape: torch.ones(shape, dtype=bf, device="cuda")
+    calls = [lambda t: K.attention(t(ones(1, 16, 64)), ones(1, 16, 64), ones(1, 16, 64), heads=1),                      # attn_fwd.hip
+             lambda t: K.temporal_attention(t(ones(8, 48)), 1, 4, 2, heads=2),                                          # temporal_attn.hip
+             lambda t: K.conv2d(t(ones(1, 4, 4, 32)), ones(128, 9, 32), 8),                                             # conv3x3.hip
+             lambda t: K.layer_norm(t(ones(4, 64)), ones(64), ones(64)),                                                # elementwise.hip
+             lambda t: K.circular_pad_w(t(ones(2, 4, 8)), 1)]                                                           # groupnorm.hip
+    for call in calls:
+        g = Guarded(K)
+        with pytest.raises(RuntimeError, match="misaligned"):
+            with g:
+                call(lambda t: g.guard(t, misalign=2))
+        torch.cuda.synchronize()
+        made = [a for a in g.allocs if a.label.startswith("empty")]
+        assert made and all(bool((a.raw[a.off:a.off + a.span].view(torch.int16) == PATTERN).all()) for a in made)
 
 
 @pytest.mark.parametrize("dt", DTYPES)
