@@ -80,6 +80,8 @@ class GraphedDenoiseStep:
         mv.dual_stream_eager = bool(getattr(mv, "dual_stream", False))
         try:
             with torch.cuda.stream(side):            # eager warm-up off the default stream (caches, allocator)
+                # (the schedule's first timestep also when the run enters it later -- pipeline ``strength`` < 1: the warm-up only has to
+                # issue every launch once; its numbers are dropped, the start latents restored below, and step() uploads the real one)
                 self._upload(scheduler._timesteps_host[0], draw=False)
                 for _ in range(warmup):
                     self._body()

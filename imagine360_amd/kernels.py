@@ -64,6 +64,7 @@ _SIGNATURES = {
     "im360_cfg_rescale_stats_windows_ring": (_INT, [_PTR] * 3 + [_INT] + [_I64] * 4 + [_F32, _PTR, _I64, _INT, _PTR, _PTR]),
     "im360_cfg_ddim_step_windows_ring_rescale": (_INT, [_PTR] * 6 + [_INT] + [_I64] * 4 + [_F32] * 6 + [_INT, _F32, _PTR, _I64, _INT,
                                                                                                        _PTR, _PTR]),
+    "im360_noise_latents": (_INT, [_PTR] * 6 + [_I64] * 5 + [_F32, _F32, _INT, _PTR]),
     "im360_layernorm": (_INT, [_PTR] * 6 + [_I64] * 5 + [_F32, _INT, _PTR]),
     "im360_geglu": (_INT, [_PTR] * 2 + [_I64] * 2 + [_INT, _PTR]),
     "im360_linear_geglu": (_INT, [_PTR] * 4 + [_I64] * 3 + [_INT, _PTR]),
@@ -984,6 +985,36 @@ def cfg_ddim_step_windows(preds, sample, noise, starts, weights, mode, coefs, co
                               *(float(v) for v in coefs), int(mode), _dt(sample), _stream(), _p(coef_dev))
     _check(rc, name)
     return out
+
+
+def noise_latents(x0, noise, idx, ok, sqrt_a, sqrt_b):
+    """The start latents of a run that begins from a given clip, one launch: ``pano = T(sqrt_a * x0 + sqrt_b * noise)`` (fp32, one
+    rounding) and ``pers`` = the nearest-neighbour E2P gather of the ROUNDED ``pano``, zero where a view sees nothing.
+    ``x0`` 16-bit [1, C, F, h, w] (a clean panorama latent);  ``noise`` float32 [1, F, C, h, w] (the layout ``init_noise`` draws in);
+    ``idx`` int32 / ``ok`` uint8 [M, ph, pw]: ``pano_geometry.nearest_e2p_index`` (values of ``idx`` in [0, h * w): a precondition);
+    ``sqrt_a``, ``sqrt_b``: ``DDIMScheduler.noise_coefficients``.  Returns (pano [1, C, F, h, w], pers [1, M, C, F, ph, pw])."""
+    _dev(x0, noise, idx, ok)
+    dt = _dt(x0)
+    if noise.dtype != torch.float32:
+        raise TypeError(f"noise_latents: noise must be float32 (the dtype init_noise draws in), got {noise.dtype}")
+    if idx.dtype != torch.int32 or ok.dtype != torch.uint8:
+        raise TypeError(f"noise_latents: idx must be int32 and ok uint8, got {idx.dtype} and {ok.dtype}")
+    if x0.dim() != 5 or x0.shape[0] != 1:
+        raise ValueError(f"noise_latents: x0 must be [1, C, F, h, w], got {list(x0.shape)}")
+    _, C, F, h, w = x0.shape
+    if tuple(noise.shape) != (1, F, C, h, w):
+        raise ValueError(f"noise_latents: noise must be {[1, F, C, h, w]} for x0 {list(x0.shape)}, got {list(noise.shape)}")
+    if idx.dim() != 3 or idx.shape != ok.shape:
+        raise ValueError(f"noise_latents: idx and ok must be one [M, ph, pw], got {list(idx.shape)} and {list(ok.shape)}")
+    if not all(t.is_contiguous() and t.device == x0.device for t in (x0, noise, idx, ok)):
+        raise ValueError("noise_latents: x0, noise, idx and ok must be contiguous and on one device")
+    M, ph, pw = idx.shape
+    pano = torch.empty((1, C, F, h, w), dtype=x0.dtype, device=x0.device)
+    pers = torch.empty((1, M, C, F, ph, pw), dtype=x0.dtype, device=x0.device)
+    rc = lib().im360_noise_latents(_p(x0), _p(noise), _p(idx), _p(ok), _p(pano), _p(pers), F, C, h * w, M, ph * pw, float(sqrt_a),
+                                   float(sqrt_b), dt, _stream())
+    _check(rc, "im360_noise_latents")
+    return pano, pers
 
 
 # ------------------------------------------------------------------------------------------ tuning knobs

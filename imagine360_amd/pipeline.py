@@ -15,6 +15,9 @@ surface, rebuilt for the MI355X:
     the text prediction's standard deviation inside the CFG + DDIM kernels (a statistics launch in front of the step launch);
   * long clips (``context_frames=L``): sliding temporal context windows -- one forward of the unmodified model per window
     of L frames, the windows' predictions blended per frame inside the CFG + DDIM kernel (imagine360_amd/context.py).
+  * a start from a clip that exists (``init_latents`` / ``init_video`` with ``strength``): the clean latent noised to the timestep at
+    which the shortened schedule is entered and resampled to the views in ONE kernel (``kernels.noise_latents``); only the
+    remaining steps run.
 
 CLIP text encoding and SAM feature extraction are outside the hot path: the
 pipeline uses ``text_encoder``/``tokenizer``/``image_encoder`` when given, and also accepts precomputed
@@ -132,17 +135,47 @@ class AnimationPipeline:
             return torch.randn(shape, dtype=torch.float32).to(device=device, dtype=dtype)
         return torch.randn(shape, device=device, dtype=dtype)
 
+    def pano_noise_and_index(self, bs, video_length, equi_h, equi_w, pers_h, pers_w, cameras, device):
+        """The first half of ``init_noise``: the ONE panorama noise draw, float32 [bs, F, 1, 4, h, w], and the frame-invariant
+        nearest-neighbour E2P tables (index, validity flag; [m, ph, pw]) on ``device``.  A run that starts from a given clip
+        (``init_latents`` / ``init_video``) takes these and leaves the second half to ``kernels.noise_latents``."""
+        pano = self._randn((bs, video_length, 1, 4, equi_h, equi_w), device)
+        idx, ok = G.nearest_e2p_index(equi_h, equi_w, pers_h, pers_w, cameras)            # [m, ph, pw]
+        return pano, idx.to(device), ok.to(device)
+
     def init_noise(self, bs, video_length, equi_h, equi_w, pers_h, pers_w, cameras, device, latents_dtype=torch.float16):
         """One panorama noise; the perspective noise is its nearest-neighbour E2P resampling, so both branches
         start from consistent noise (pipeline...dual.py:361-387).  The index maps are frame-invariant and
         built once instead of 16 x 20 host-side map builds."""
-        pano = self._randn((bs, video_length, 1, 4, equi_h, equi_w), device)
-        idx, ok = G.nearest_e2p_index(equi_h, equi_w, pers_h, pers_w, cameras)            # [m, ph, pw]
-        idx, ok = idx.to(device), ok.to(device)
+        pano, idx, ok = self.pano_noise_and_index(bs, video_length, equi_h, equi_w, pers_h, pers_w, cameras, device)
         flat = pano.squeeze(2).reshape(bs, video_length, 4, equi_h * equi_w)
         pers = flat[..., idx.reshape(-1)].reshape(bs, video_length, 4, *idx.shape) * ok   # b f c m h w
         return (pano.squeeze(2).permute(0, 2, 1, 3, 4).contiguous().to(latents_dtype),
                 pers.permute(0, 3, 2, 1, 4, 5).contiguous().to(latents_dtype))
+
+    def encode_init_video(self, video, chunk=8):
+        """A clip [1, F, 3, H, W] in [-1, 1] -> its clean panorama latent [1, 4, F, H/8, W/8], scaled by ``VAE_SCALE``: the VAE
+        encoder in chunks of ``chunk`` frames, the posterior's mode -- no draw from any RNG, so every other draw of the call keeps
+        its place."""
+        b, f = video.shape[:2]
+        x = video.reshape(b * f, *video.shape[2:])
+        lat = torch.cat([self.vae.encode(x[i:i + chunk], min(chunk, b * f - i)).latent_dist.mode() for i in range(0, b * f, chunk)])
+        return lat.reshape(b, f, *lat.shape[1:]).permute(0, 2, 1, 3, 4) * VAE_SCALE
+
+    def init_from_clip(self, x0, strength, video_length, equi_h, equi_w, pers_h, pers_w, cameras, device, latents_dtype=torch.float16):
+        """The start of a run from a given clean panorama latent ``x0`` [1, 4, F, h, w] (SDEdit): ``init_noise``'s panorama noise
+        draw at its place in the RNG order, the schedule entered at ``scheduler.timesteps_for_strength(strength)``, and ``x0`` noised
+        to the first timestep that is run, the perspective start being the nearest-neighbour E2P resampling of the panorama start
+        (``kernels.noise_latents``, one launch).  Returns (pano_latent, pers_latent, steps)."""
+        if tuple(x0.shape) != (1, 4, video_length, equi_h, equi_w):
+            raise ValueError(f"the init latent must be [1, 4, {video_length}, {equi_h}, {equi_w}] (a clean panorama latent, multiplied by "
+                             f"VAE_SCALE, such as pipe.last_latents[0]), got {tuple(x0.shape)}")
+        noise, idx, ok = self.pano_noise_and_index(1, video_length, equi_h, equi_w, pers_h, pers_w, cameras, device)
+        _, steps = self.scheduler.timesteps_for_strength(strength)
+        sqrt_a, sqrt_b = self.scheduler.noise_coefficients(steps[0])
+        pano, pers = kernels.noise_latents(x0.to(device=device, dtype=latents_dtype).contiguous(), noise.squeeze(2), idx.to(torch.int32),
+                                           ok.to(torch.uint8), sqrt_a, sqrt_b)
+        return pano, pers, steps
 
     def _encode_chunks(self, x, chunk=8, keep_rows=None):
         """VAE-encode images [n, 3, H, W] in chunks of ``chunk`` and sample the posteriors (one randn per chunk, in order).
@@ -219,7 +252,7 @@ class AnimationPipeline:
                  video_batch=None, use_outpaint=False, use_ip_plus_cross_attention=False, use_fps_condition=False,
                  ip_plus_condition="image", prompt_embeds=None, sam_features=None, trace=None, frame_shard=None,
                  context_frames=None, context_overlap=4, context_weights="pyramid", guidance_rescale=0.0, context_loop=False,
-                 **kwargs):
+                 init_latents=None, init_video=None, strength=1.0, **kwargs):
         """``frame_shard`` (imagine360_amd.dist.FrameShard): this rank denoises a contiguous chunk of the frames (BASELINE
         configs 4 / 5); all ranks must be called with the same seeds and inputs.  Noise is drawn for the whole clip and
         cut, the VAE encodes / the loop runs / the VAE decodes only the local frames, the motion modules exchange tokens
@@ -236,7 +269,17 @@ class AnimationPipeline:
         ``guidance_rescale`` (0.0: off; the paper uses 0.7): ``scheduler.rescale_noise_cfg`` on each branch's guided prediction
         before the update (arXiv 2305.08891, section 3.4: with zero-terminal-SNR betas a guidance of 7.5 over-exposes without it),
         the standard deviations over the whole panorama latent / over all views of the perspective latent (with context windows:
-        over the whole clip of blends), computed inside the fused CFG + DDIM kernels."""
+        over the whole clip of blends), computed inside the fused CFG + DDIM kernels.
+        ``init_latents`` / ``init_video`` (at most one; None: start from pure noise) with ``strength`` in (0, 1]: start from a clip
+        that exists (SDEdit, the video-to-video call of diffusers' pipelines).  ``init_latents``: a clean panorama latent
+        [1, 4, F, H/8, W/8], already multiplied by ``VAE_SCALE`` -- ``pipe.last_latents[0]`` of an earlier call is one; ``init_video``:
+        [1, F, 3, H, W] in [-1, 1], encoded here (``encode_init_video``: the posterior's mode, no RNG draw).  The clip is noised to the
+        timestep at which the schedule is entered and only the last ``int(num_inference_steps * strength)`` steps are run
+        (``scheduler.timesteps_for_strength``); ``callback`` and ``trace`` count these steps from 0.  The panorama noise is the draw
+        ``init_noise`` makes, at the same place in the RNG order; both start latents come from one launch (``kernels.noise_latents``).
+        Every loop variant runs the shortened schedule (graph replay, context windows, ``context_loop``, ``eta``,
+        ``guidance_rescale``); not with ``frame_shard``.  Without an init, ``strength`` must be 1.0 and the call is the one without
+        these keywords."""
         device = self.device
         vb = video_batch
         plan = None
@@ -246,6 +289,15 @@ class AnimationPipeline:
                              "ranks and would need an all-reduce inside the step, which is not implemented)")
         if context_loop and frame_shard is not None:
             raise ValueError("context_loop cannot be combined with frame_shard (windows under frame sharding are not implemented)")
+        if init_latents is not None and init_video is not None:
+            raise ValueError("give at most one of init_latents and init_video")
+        has_init = init_latents is not None or init_video is not None
+        strength = float(strength)
+        if not has_init and strength != 1.0:
+            raise ValueError(f"strength={strength} needs init_latents or init_video (a run from pure noise always runs the whole schedule)")
+        if has_init and frame_shard is not None:
+            raise ValueError("init_latents / init_video cannot be combined with frame_shard (the cut of the noised start latents to a "
+                             "rank's frames and the sharded encode of an init clip are not implemented)")
         if context_loop and (context_frames is None or int(context_frames) >= vb["video_length"]):
             raise ValueError(f"context_loop needs context_frames < video_length = {vb['video_length']} (one window cannot wrap around), "
                              f"got context_frames={context_frames}")
@@ -268,7 +320,13 @@ class AnimationPipeline:
         pers_pix_masked = (pers_pix * (pers_masks < 0.5)).to(device)
         self.scheduler.set_timesteps(num_inference_steps, device=device)
         steps_host = self.scheduler._timesteps_host
-        pano_latent, pers_latent = self.init_noise(1, f, H // 8, W // 8, ps // 8, ps // 8, cameras, device, latents_dtype)
+        if has_init:
+            # the encode draws nothing, so it may come first: the panorama noise is then drawn where init_noise draws it
+            x0 = init_latents if init_latents is not None else self.encode_init_video(init_video.to(device))
+            pano_latent, pers_latent, steps_host = self.init_from_clip(x0, strength, f, H // 8, W // 8, ps // 8, ps // 8, cameras, device,
+                                                                       latents_dtype)
+        else:
+            pano_latent, pers_latent = self.init_noise(1, f, H // 8, W // 8, ps // 8, ps // 8, cameras, device, latents_dtype)
         sh = frame_shard
         if sh is not None:
             # every rank drew the whole clip's noise from the same seed: cut to the local frames

@@ -1,5 +1,5 @@
-"""DDIMScheduler with the reference's constructor keywords, attributes and ``step`` contract
-(diffusers/schedulers/scheduling_ddim.py:113-373) for the configuration of configs/prompt-dual.yaml:48-56.
+"""DDIMScheduler with the reference's constructor keywords, attributes, ``step`` contract, ``add_noise``, ``get_velocity`` and
+``__len__`` (diffusers/schedulers/scheduling_ddim.py:113-419) for the configuration of configs/prompt-dual.yaml:48-56.
 
 Coefficients are tabulated on the host in fp32 exactly like the reference (so ``alphas_cumprod`` matches
 bit for bit) and combined in fp64 python floats; on the GPU the whole CFG + update chain of the
@@ -164,6 +164,49 @@ class DDIMScheduler:
         sigma = eta * _sqrt(var)
         return (float(guidance), _sqrt(a_t), _sqrt(b_t), _sqrt(a_prev), _sqrt(1.0 - a_prev - sigma ** 2),
                 sigma if eta > 0 else 0.0)
+
+    def noise_coefficients(self, timestep):
+        """(sqrt(a_t), sqrt(1 - a_t)) of ``add_noise`` at one timestep as host floats: fp64 from the fp32 ``alphas_cumprod``, the
+        ``sqrt_a`` / ``sqrt_b`` of ``step_coefficients`` for the same ``timestep`` (arguments of ``kernels.noise_latents``)."""
+        a_t = float(self.alphas_cumprod[int(timestep)])
+        return _sqrt(a_t), _sqrt(1.0 - a_t)
+
+    def timesteps_for_strength(self, strength):
+        """Where a run that starts from a given clip enters the schedule of ``set_timesteps(N)`` (diffusers' img2img ``get_timesteps``):
+        ``k = min(int(N * strength), N)`` steps are run, the last k of the schedule.  Returns ``(i0, steps)`` with ``i0 = N - k`` and
+        ``steps = _timesteps_host[i0:]``; the clip is noised to ``steps[0]``.  ``strength`` in (0, 1]; 1.0 runs the whole schedule."""
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        n, strength = self.num_inference_steps, float(strength)
+        if not 0.0 < strength <= 1.0:
+            raise ValueError(f"strength must be in (0, 1], got {strength}")
+        k = min(int(n * strength), n)
+        if k == 0:
+            raise ValueError(f"strength={strength} leaves no step to run out of num_inference_steps N={n} (int(N * strength) = 0): "
+                             f"raise one of them")
+        return n - k, self._timesteps_host[n - k:]
+
+    def _noise_factors(self, like, timesteps):
+        """sqrt(a_t) and sqrt(1 - a_t) of ``timesteps`` in ``like``'s dtype on its device, shaped to broadcast from the left over
+        ``like``.  Works on a cast COPY of ``alphas_cumprod``: the table itself stays fp32 on the host, where ``_alphas`` reads it
+        (the reference re-types the attribute in place)."""
+        abar = self.alphas_cumprod.to(device=like.device, dtype=like.dtype)[timesteps.to(like.device)]
+        shape = (-1,) + (1,) * (like.dim() - 1)
+        return (abar ** 0.5).flatten().reshape(shape), ((1 - abar) ** 0.5).flatten().reshape(shape)
+
+    def add_noise(self, original_samples, noise, timesteps):
+        """scheduling_ddim.py:375-396: ``sqrt(a_t) x_0 + sqrt(1 - a_t) noise``, the coefficients taken from ``alphas_cumprod`` cast to the
+        samples' dtype, in torch ops on the tensors' device; ``timesteps``: an integer tensor of 1 element or one per batch entry."""
+        sa, sb = self._noise_factors(original_samples, timesteps)
+        return sa * original_samples + sb * noise
+
+    def get_velocity(self, sample, noise, timesteps):
+        """scheduling_ddim.py:398-416: the v-prediction target ``sqrt(a_t) noise - sqrt(1 - a_t) sample``, as ``add_noise``."""
+        sa, sb = self._noise_factors(sample, timesteps)
+        return sa * noise - sb * sample
+
+    def __len__(self):
+        return self.config.num_train_timesteps
 
     def noise_dtype(self, model_dtype, sample_dtype, use_clipped_model_output=False):
         """dtype the reference's ``step`` draws its variance noise in: that of ``model_output`` after the v_prediction /

@@ -340,6 +340,25 @@ int im360_cfg_ddim_step_windows_ring_rescale(const void* pred, const void* x, co
                                              int mode, float phi, const void* ws, int64_t ws_floats, int dtype, void* stream,
                                              const void* coef_dev);
 
+/* ---- start latents of a run that begins from a given clip (AnimationPipeline init_latents / init_video, strength < 1), one launch:
+ *   out_pano[c, f, p]    = T(sqrt_a * x0[c, f, p] + sqrt_b * noise[f, c, p])        fp32, one rounding, at the store
+ *   out_pers[m, c, f, q] = ok[m, q] ? out_pano[c, f, idx[m, q]] : 0                 the gather of the ROUNDED panorama start, bit for bit
+ * x0 / out_pano: 16-bit [C, F, HW] (the pipeline's panorama latent [1, 4, F, h, w]); noise: fp32 [F, C, HW] (the layout init_noise
+ * draws in); idx int32 / ok uint8 [M, Q]: the table and validity flags of pano_geometry.nearest_e2p_index; out_pers: 16-bit
+ * [M, C, F, Q] (the perspective latent [1, m, 4, F, h, w]).  sqrt_a, sqrt_b = sqrt(a_t), sqrt(1 - a_t) of the first timestep that is run
+ * (DDIMScheduler.noise_coefficients).  One workgroup per (c, f) plane: planes of up to 64 KiB (2 * HW bytes) are kept in LDS and
+ * all M * Q gathers served from there; larger planes form every gathered element again from x0 and noise (same expression, same
+ * bits).  16-byte lanes when HW % 8 == 0, Q % 8 == 0 and every pointer is aligned for them, a scalar path otherwise.
+ * Refused: a null pointer, a size <= 0, HW / C * F / M * Q >= 2^31 (32-bit indices inside a plane, a table and the grid; element
+ * offsets are 64-bit), noise or idx off 4 bytes, an unknown dtype.
+ * Precondition (the host cannot see the table): 0 <= idx[m, q] < HW.  The kernel clamps, so a bad table gives wrong elements and
+ * no read outside the plane.
+ * Replaces: pipeline_animation_inference_dual.py:361-387 (the E2P of the noise, applied here to the noised latent) and
+ *   DDIMScheduler.add_noise, scheduling_ddim.py:375-396.  The reference pipeline itself has no strength argument: it always starts
+ *   from pure noise. */
+int im360_noise_latents(const void* x0, const float* noise, const int32_t* idx, const uint8_t* ok, void* out_pano, void* out_pers,
+                        int64_t F, int64_t C, int64_t HW, int64_t M, int64_t Q, float sqrt_a, float sqrt_b, int dtype, void* stream);
+
 /* y[r] = LayerNorm(x[r] + pre[r % pre_period]) * gamma + beta + post[(r / post_div) % post_mod] on token rows
  * [rows, C]; pre / post are optional [*, C] tables (the WarpAttn spherical PE added before norm1, the motion
  * module's frame PE added after the norm).

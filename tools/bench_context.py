@@ -9,7 +9,13 @@ device events, with the bytes each has to move computed from the shapes.  Prints
     python tools/bench_context.py --loop [--passes 2] # the looping clip: the ring plan's captured step next to the linear plan's (same F, L,
                                                       # overlap; ms per step and per window), and the ring entry point of the blend kernel next to
                                                       # the linear one on the SAME non-wrapping tables and on the ring's own; every measurement is
-                                                      # made --passes times over, so the spread between identical passes stands next to the numbers"""
+                                                      # made --passes times over, so the spread between identical passes stands next to the numbers
+    python tools/bench_context.py --strength 0.5 [--frames 48] [--num-steps 6] [--loop]
+                                                      # the refinement pass: whole pipeline calls (encode, loop, decode; host clock around a call that
+                                                      # ends in a device synchronise) from pure noise and, with init_latents taken from a first call,
+                                                      # at this strength, alternated --rounds times; over context windows when --frames > 16 (--loop:
+                                                      # on a ring); and kernels.noise_latents at the size of that clip next to the torch-op composition
+                                                      # it replaces (device events, alternated), with the bytes the launch has to move"""
 import argparse
 import json
 import os
@@ -134,6 +140,102 @@ def loop_bench(args, sch, dev, dt, ts_host):
     return res
 
 
+def torch_noise_latents(x0, noise, idx, ok, sqrt_a, sqrt_b):
+    """What ``kernels.noise_latents`` replaces, in torch ops: the noised panorama start in fp32, rounded, and its gather by the
+    tables of ``init_noise``, masked, in the perspective latent's layout (``idx`` int64, ``ok`` bool, as ``init_noise`` holds them)."""
+    _, C, F, h, w = x0.shape
+    pano = (sqrt_a * x0.float() + sqrt_b * noise.permute(0, 2, 1, 3, 4)).to(x0.dtype)
+    flat = pano.permute(0, 2, 1, 3, 4).reshape(1, F, C, h * w)
+    pers = flat[..., idx.reshape(-1)].reshape(1, F, C, *idx.shape) * ok
+    return pano.contiguous(), pers.permute(0, 3, 2, 1, 4, 5).contiguous()
+
+
+def time_noise_latents(sch, frames, dev, dt, iters, rounds=5):
+    """Device-event time of ``kernels.noise_latents`` and of the torch-op composition on one clip (alternated round by round, ``iters``
+    back-to-back calls each, allocation of the results included), and the bytes of noise, x0 and the two results."""
+    from imagine360_amd import pano_geometry as G
+    cams = synthetic.icosahedron_cameras(90, PERS_PX)
+    idx64, okb = (t.to(dev) for t in G.nearest_e2p_index(*PANO_HW, *PERS_HW, cams))
+    idx32, ok8 = idx64.to(torch.int32), okb.to(torch.uint8)
+    x0 = torch.randn(1, 4, frames, *PANO_HW, device=dev).to(dt)
+    noise = torch.randn(1, frames, 4, *PANO_HW, device=dev)
+    sa, sb = sch.noise_coefficients(sch.timesteps_for_strength(0.5)[1][0])
+    fns = dict(kernel=lambda: kernels.noise_latents(x0, noise, idx32, ok8, sa, sb), torch_ops=lambda: torch_noise_latents(x0, noise, idx64, okb, sa, sb))
+    a, b = fns["kernel"](), fns["torch_ops"]()
+    # the two are not the same bits: torch rounds sqrt_a * x0 to fp32 before the add, the kernel fuses the product into one fma
+    differ = float((a[0] != b[0]).float().mean())
+    max_diff = float((a[0].float() - b[0].float()).abs().max())
+    times = {k: [] for k in fns}
+    for r in range(rounds + 1):
+        for name, fn in fns.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            for _ in range(iters):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            if r:                                   # round 0 warms both up
+                times[name].append(e0.elapsed_time(e1) / iters * 1e3)
+    nbytes = noise.numel() * 4 + 2 * x0.numel() * 2 + a[1].numel() * 2
+    res = {k: dict(us_min=min(v), us_median=statistics.median(v)) for k, v in times.items()}
+    res.update(bytes=nbytes, tables_bytes=idx32.numel() * 5, gb_per_s_kernel=nbytes / (res["kernel"]["us_min"] * 1e-6) / 1e9,
+               x0=list(x0.shape), pers=list(a[1].shape), pano_fraction_differing_from_torch_ops=differ, pano_max_abs_diff=max_diff,
+               note="event time over back-to-back calls; the working set fits the Infinity Cache, so GB/s is an effective rate")
+    return res
+
+
+def strength_bench(args, sch, dev, dt):
+    """--strength S: whole pipeline calls from pure noise and from the first call's latent at strength S."""
+    import random
+
+    from imagine360_amd.pipeline import AnimationPipeline
+    frames = args.frames
+    res = dict(tool="bench_context --strength", strength=args.strength, frames=frames, num_inference_steps=args.num_steps,
+               pano_hw=PANO_HW, pers_hw=PERS_HW, dtype="bfloat16", device=torch.cuda.get_device_name(0))
+    res["noise_latents"] = time_noise_latents(sch, frames, dev, dt, args.kernel_iters)
+    if args.kernel_only:
+        return res
+    mv = configs.build_mv_model(1, device=dev, dtype=dt, xformers=True)
+    mv.dual_stream, mv.warp_streams = True, True
+    vae = configs.build_vae(1, device=dev, dtype=dt)
+    pipe = AnimationPipeline(vae, None, None, mv.unet, mv.pano_unet, mv, DDIMScheduler(**configs.NOISE_SCHEDULER_KWARGS), None, "SAM").to(dev)
+    pipe._no_progress = True
+    vb = synthetic.video_batch(frames=frames, pano_hw=(PANO_HW[0] * 8, PANO_HW[1] * 8), seed=1)
+    cond = synthetic.conditioning(frames=max(frames, 16), seed=1)
+    windows = dict(context_frames=LENGTH, context_overlap=OVERLAP, context_loop=args.loop) if frames > LENGTH else {}
+    res["windows"] = windows
+
+    def call(**kw):
+        torch.manual_seed(21)
+        random.seed(21)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        vid = pipe("synthetic", num_inference_steps=args.num_steps, guidance_scale_text=7.5, negative_prompt="", latents_dtype=dt,
+                   video_batch=vb, use_outpaint=True, use_ip_plus_cross_attention=True, use_fps_condition=True, ip_plus_condition="video",
+                   prompt_embeds=(cond["text_pano"], cond["text_pers"]), sam_features=(cond["sam_pano"], cond["sam_pers"]), **windows, **kw).videos
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, bool(torch.isfinite(vid).all())
+
+    res["first_call_ms"], fin = call()                       # warms every shape up; its latent is the init of the refinement passes
+    x0 = pipe.last_latents[0].clone()
+    print("first call done", file=sys.stderr, flush=True)
+    sch.set_timesteps(args.num_steps)
+    steps = dict(from_noise=args.num_steps, refine=len(sch.timesteps_for_strength(args.strength)[1]))
+    times = dict(from_noise=[], refine=[])
+    for _ in range(args.rounds):
+        for name, kw in (("from_noise", {}), ("refine", dict(init_latents=x0, strength=args.strength))):
+            ms, ok = call(**kw)
+            times[name].append(ms)
+            fin = fin and ok
+    for k, v in times.items():
+        res[k] = dict(call_ms=v, call_ms_min=min(v), steps=steps[k])
+    res["ms_per_skipped_step"] = (res["from_noise"]["call_ms_min"] - res["refine"]["call_ms_min"]) / max(steps["from_noise"] - steps["refine"], 1)
+    res["refine_over_from_noise"] = res["refine"]["call_ms_min"] / res["from_noise"]["call_ms_min"]
+    res["finite"] = fin
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=3)
@@ -142,6 +244,9 @@ def main():
     ap.add_argument("--kernel-only", action="store_true")
     ap.add_argument("--loop", action="store_true", help="the ring plan of a looping clip against the linear plan")
     ap.add_argument("--passes", type=int, default=2, help="--loop: identical passes of every measurement")
+    ap.add_argument("--strength", type=float, default=None, help="the refinement pass: pipeline calls with init_latents at this strength next to calls from pure noise")
+    ap.add_argument("--frames", type=int, default=FRAMES, help="--strength: frames of the clip (context windows above 16)")
+    ap.add_argument("--num-steps", type=int, default=6, help="--strength: num_inference_steps of every call")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_context.py measures on the MI355X; there is nothing to time without one"
@@ -151,6 +256,8 @@ def main():
     sch = DDIMScheduler(**configs.NOISE_SCHEDULER_KWARGS)
     sch.set_timesteps(25)
     ts_host = [int(t) for t in sch._timesteps_host]
+    if args.strength is not None:
+        return emit(strength_bench(args, sch, dev, dt), args.out)
     if args.loop:
         return emit(loop_bench(args, sch, dev, dt, ts_host), args.out)
     plan = WindowPlan(FRAMES, LENGTH, OVERLAP, "pyramid", dev)
