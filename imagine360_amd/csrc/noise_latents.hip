@@ -18,13 +18,15 @@
 // idx is clamped into [0, HW) as an unsigned value: a table that breaks the precondition gives a wrong element, never a read
 // outside the plane.
 #include "common.h"
+#include "fma_f32.h"
 
 namespace im360 {
 
 constexpr int kNoiseLdsBytes = 64 * 1024;        // the plane of a 128 x 256 latent; what a workgroup gets without asking for more
 
-// explicit fma: the two places that form an element (plane pass, global-path gather) must round alike whatever hipcc contracts
-__device__ __forceinline__ float noised(float x, float n, float sa, float sb) { return __fmaf_rn(sa, x, sb * n); }
+// explicit fma: the two places that form an element (plane pass, global-path gather) must round alike whatever hipcc contracts or
+// folds into the conversion that follows (fma_f32.h)
+__device__ __forceinline__ float noised(float x, float n, float sa, float sb) { return fma_f32(sa, x, sb * n); }
 
 template <typename T> __device__ __forceinline__ uint16_t bits16(float v) {
     const T t = from_f32<T>(v);

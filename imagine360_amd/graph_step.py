@@ -9,6 +9,8 @@ sampling (eta > 0) draws the two variance noises inside the graph as well, right
 caller's generator (registered with the graph) or the default one; the coefficients are then (guidance, sqrt a_t,
 sqrt b_t, sqrt a_prev, dir, sigma) for ``cfg_ddim_step``.  Guidance rescale (``guidance_rescale`` != 0) adds one captured
 statistics launch in front of each branch's step launch; its workspace is a graph-pool tensor and nothing more is uploaded.
+A partly regenerated clip (``keep``, pipeline ``regenerate_mask``) adds one captured ``keep_latents`` launch after the two step launches;
+its two coefficients are a fifth tiny buffer, refreshed per step through a pinned ring of its own.
 """
 import random
 
@@ -41,7 +43,7 @@ class GraphedDenoiseStep:
     always_step_kernel = False      # (GraphedWindowedStep) the six-coefficient step kernel for eta = 0 as well
 
     def __init__(self, mv, scheduler, inputs, cameras, pano_latent, pers_latent, guidance, use_fps=True, warmup=2, cfg_pair=None,
-                 eta=0.0, generator=None, use_clipped_model_output=False, frame_shard=None, guidance_rescale=0.0):
+                 eta=0.0, generator=None, use_clipped_model_output=False, frame_shard=None, guidance_rescale=0.0, keep=None):
         """``inputs``: the keyword tensors of MultiViewBaseModel.forward (CFG-batched, resident on the GPU);
         ``pano_latent`` [1,4,F,H,W] / ``pers_latent`` [1,m,4,F,h,w]: initial noisy latents.
         Frame-sharded models (``mv.set_frame_shard``) capture their all-to-alls with the step: the exchange buffers are
@@ -50,7 +52,8 @@ class GraphedDenoiseStep:
         inside the captured step before the CFG combine.
         ``eta`` / ``generator`` / ``use_clipped_model_output``: DDIMScheduler.step's keywords (defaults: the eta = 0 update).
         ``frame_shard`` (dist.FrameShard): with eta > 0 the variance noise is drawn for the whole clip and cut to the local
-        frames, like the initial noise.  ``guidance_rescale``: ``DDIMScheduler.fused_cfg_step``'s keyword."""
+        frames, like the initial noise.  ``guidance_rescale``: ``DDIMScheduler.fused_cfg_step``'s keyword.
+        ``keep`` (pipeline.KeepRegion): the kept region of a given clip, blended into both latents after the two updates."""
         self.mv, self.sch, self.inp, self.cams, self.g = mv, scheduler, inputs, cameras, float(guidance)
         self.cfg_pair = cfg_pair
         self.eta, self.gen, self.clipped, self.shard = float(eta), generator, bool(use_clipped_model_output), frame_shard
@@ -66,6 +69,10 @@ class GraphedDenoiseStep:
         self.use_fps = use_fps
         self.graph = None
         self._up_t, self._up_c = _PinnedUploads(self.timestep), _PinnedUploads(self.coef)
+        self.keep = keep
+        if keep is not None:
+            self.keep_coef = torch.zeros(2, dtype=torch.float32, device=dev)
+            self._up_keep = _PinnedUploads(self.keep_coef)
         # Building the graph must not consume randomness: the warm-up steps draw device noise (the per-step IP-adapter
         # noise) and allocating the coin buffer used to take 7 Python draws, which shifted the streams of the default
         # (graphed) pipeline relative to the eager one and to the reference for the same seeds.
@@ -136,8 +143,18 @@ class GraphedDenoiseStep:
                                            noise=self._noise(self.pano_lat, mdt, 2), **kw)
         new_pers = self.sch.fused_cfg_step(pred_pers[0:1], pred_pers[1:2], self.g, None, self.pers_lat, coef_dev=self.coef,
                                            noise=self._noise(self.pers_lat, mdt, 3), **kw)
+        self._keep(new_pano, new_pers)
         self.pano_lat.copy_(new_pano)
         self.pers_lat.copy_(new_pers)
+
+    def _keep(self, new_pano, new_pers):
+        """The kept region blended into the two fresh latents, in place (``keep`` only), coefficients from the device."""
+        if self.keep is not None:
+            self.keep.blend(new_pano, new_pers, coef_dev=self.keep_coef)
+
+    def _upload_keep(self, t_host):
+        if self.keep is not None:
+            self._up_keep.upload(self.keep_coef, list(self.keep.coefficients_at(t_host)))
 
     def _noise(self, latent, model_dtype, frame_dim):
         """Variance noise of one branch (eta > 0 only), drawn where the reference's ``step`` draws it."""
@@ -153,6 +170,7 @@ class GraphedDenoiseStep:
         else:
             cx, cv = self.sch.coefficients(t_host)
             self._up_c.upload(self.coef, [self.g, cx, cv])
+        self._upload_keep(t_host)
         if draw:
             self.mv.draw_coins(self.timestep.device)
 
@@ -176,7 +194,7 @@ class GraphedWindowedStep(GraphedDenoiseStep):
     always_step_kernel = True
 
     def __init__(self, mv, scheduler, inputs, cameras, pano_latent, pers_latent, guidance, plan, use_fps=True, warmup=1, eta=0.0,
-                 generator=None, use_clipped_model_output=False, guidance_rescale=0.0):
+                 generator=None, use_clipped_model_output=False, guidance_rescale=0.0, keep=None):
         dev = pano_latent.device
         self.plan = plan
         self.static = plan.static_inputs(inputs)
@@ -184,7 +202,7 @@ class GraphedWindowedStep(GraphedDenoiseStep):
         self.coins = torch.zeros(len(plan), 8, dtype=torch.int32, device=dev)
         self._up_k = _PinnedUploads(self.coins)
         super().__init__(mv, scheduler, inputs, cameras, pano_latent, pers_latent, guidance, use_fps=use_fps, warmup=warmup, eta=eta,
-                         generator=generator, use_clipped_model_output=use_clipped_model_output, guidance_rescale=guidance_rescale)
+                         generator=generator, use_clipped_model_output=use_clipped_model_output, guidance_rescale=guidance_rescale, keep=keep)
 
     def _body(self):
         inp = self.inp
@@ -199,12 +217,14 @@ class GraphedWindowedStep(GraphedDenoiseStep):
                                                    self.pano_lat, noise=self._noise(self.pano_lat, mdt, 2), **kw)
         new_pers = self.sch.fused_cfg_step_windows(self.preds_pers, self.plan.starts_dev, self.plan.weights, self.g, None,
                                                    self.pers_lat, noise=self._noise(self.pers_lat, mdt, 3), **kw)
+        self._keep(new_pano, new_pers)
         self.pano_lat.copy_(new_pano)
         self.pers_lat.copy_(new_pers)
 
     def _upload(self, t_host, draw=True):
         self._up_t.upload(self.timestep, [int(t_host)])
         self._up_c.upload(self.coef, list(self.sch.step_coefficients(t_host, self.eta, self.g)))
+        self._upload_keep(t_host)
         if draw:
             # the coins of nW successive forwards: 7 per window in execution order (MultiViewBaseModel.draw_coins)
             self._up_k.upload(self.coins, [[1 if random.random() < 0.4 else 0 for _ in range(7)] + [0] for _ in range(len(self.plan))])

@@ -65,6 +65,7 @@ _SIGNATURES = {
     "im360_cfg_ddim_step_windows_ring_rescale": (_INT, [_PTR] * 6 + [_INT] + [_I64] * 4 + [_F32] * 6 + [_INT, _F32, _PTR, _I64, _INT,
                                                                                                        _PTR, _PTR]),
     "im360_noise_latents": (_INT, [_PTR] * 6 + [_I64] * 5 + [_F32, _F32, _INT, _PTR]),
+    "im360_keep_latents": (_INT, [_PTR] * 7 + [_I64] * 5 + [_F32, _F32, _INT, _PTR, _PTR]),
     "im360_layernorm": (_INT, [_PTR] * 6 + [_I64] * 5 + [_F32, _INT, _PTR]),
     "im360_geglu": (_INT, [_PTR] * 2 + [_I64] * 2 + [_INT, _PTR]),
     "im360_linear_geglu": (_INT, [_PTR] * 4 + [_I64] * 3 + [_INT, _PTR]),
@@ -1014,6 +1015,51 @@ def noise_latents(x0, noise, idx, ok, sqrt_a, sqrt_b):
     rc = lib().im360_noise_latents(_p(x0), _p(noise), _p(idx), _p(ok), _p(pano), _p(pers), F, C, h * w, M, ph * pw, float(sqrt_a),
                                    float(sqrt_b), dt, _stream())
     _check(rc, "im360_noise_latents")
+    return pano, pers
+
+
+def keep_latents(pano, pers, x0, noise, mask, idx, ok, sqrt_a, sqrt_b, coef_dev=None):
+    """Regenerating part of a given clip: both latents blended IN PLACE with ``known = T(sqrt_a * x0 + sqrt_b * noise)`` (the expression
+    of ``noise_latents``, one rounding), one launch: ``pano = blend(pano, known, mask)`` and, where ``ok``, ``pers = blend(pers, known
+    at idx, mask at idx)``; ``blend(x, k, w)`` is x untouched for w >= 1, k bit for bit for w <= 0 and ``T(fma(w, x - k, k))`` between.
+    ``pano`` / ``x0`` 16-bit [1, C, F, h, w];  ``pers`` [1, M, C, F, ph, pw];  ``noise`` float32 [1, F, C, h, w];  ``mask`` float32
+    [F, h, w] (1: regenerate, 0: keep);  ``idx`` int32 / ``ok`` uint8 [M, ph, pw] as for ``noise_latents``;  ``sqrt_a``, ``sqrt_b``:
+    ``DDIMScheduler.keep_coefficients``;  ``coef_dev`` = device float32[2] holding them, read by the kernel instead (graph replay).
+    Returns (pano, pers), the tensors given."""
+    _dev(pano, pers, x0, noise, mask, idx, ok, coef_dev)
+    dt = _dt(pano)
+    if pers.dtype != pano.dtype or x0.dtype != pano.dtype:
+        raise TypeError(f"keep_latents: pano, pers and x0 must have one dtype, got {pano.dtype}, {pers.dtype} and {x0.dtype}")
+    if noise.dtype != torch.float32 or mask.dtype != torch.float32:
+        raise TypeError(f"keep_latents: noise and mask must be float32, got {noise.dtype} and {mask.dtype}")
+    if idx.dtype != torch.int32 or ok.dtype != torch.uint8:
+        raise TypeError(f"keep_latents: idx must be int32 and ok uint8, got {idx.dtype} and {ok.dtype}")
+    if pano.dim() != 5 or pano.shape[0] != 1:
+        raise ValueError(f"keep_latents: pano must be [1, C, F, h, w], got {list(pano.shape)}")
+    _, C, F, h, w = pano.shape
+    if x0.shape != pano.shape:
+        raise ValueError(f"keep_latents: x0 must be {list(pano.shape)} like pano, got {list(x0.shape)}")
+    if tuple(noise.shape) != (1, F, C, h, w):
+        raise ValueError(f"keep_latents: noise must be {[1, F, C, h, w]} for pano {list(pano.shape)}, got {list(noise.shape)}")
+    if tuple(mask.shape) != (F, h, w):
+        raise ValueError(f"keep_latents: mask must be {[F, h, w]} for pano {list(pano.shape)}, got {list(mask.shape)}")
+    if idx.dim() != 3 or idx.shape != ok.shape:
+        raise ValueError(f"keep_latents: idx and ok must be one [M, ph, pw], got {list(idx.shape)} and {list(ok.shape)}")
+    M, ph, pw = idx.shape
+    if tuple(pers.shape) != (1, M, C, F, ph, pw):
+        raise ValueError(f"keep_latents: pers must be {[1, M, C, F, ph, pw]}, got {list(pers.shape)}")
+    if not all(t.is_contiguous() and t.device == pano.device for t in (pano, pers, x0, noise, mask, idx, ok)):
+        raise ValueError("keep_latents: pano, pers, x0, noise, mask, idx and ok must be contiguous and on one device")
+    if x0.data_ptr() == pano.data_ptr():
+        raise ValueError("keep_latents: x0 aliases pano (the update is in place: the clean clip would be overwritten)")
+    if coef_dev is not None:
+        if coef_dev.dtype != torch.float32:
+            raise TypeError(f"keep_latents: coef_dev must be float32, got {coef_dev.dtype}")
+        if coef_dev.numel() != 2 or not coef_dev.is_contiguous() or coef_dev.device != pano.device:
+            raise ValueError("keep_latents: coef_dev must be a contiguous float32[2] on the latents' device")
+    rc = lib().im360_keep_latents(_p(pano), _p(pers), _p(x0), _p(noise), _p(mask), _p(idx), _p(ok), F, C, h * w, M, ph * pw,
+                                  float(sqrt_a), float(sqrt_b), dt, _stream(), _p(coef_dev))
+    _check(rc, "im360_keep_latents")
     return pano, pers
 
 

@@ -18,6 +18,9 @@ surface, rebuilt for the MI355X:
   * a start from a clip that exists (``init_latents`` / ``init_video`` with ``strength``): the clean latent noised to the timestep at
     which the shortened schedule is entered and resampled to the views in ONE kernel (``kernels.noise_latents``); only the
     remaining steps run.
+  * regenerating part of such a clip (``regenerate_mask``): after the two step kernels of every step ONE more kernel
+    (``kernels.keep_latents``) blends both latents with the clean clip noised to the level they now have, so the kept region ends as
+    the input, bit for bit.
 
 CLIP text encoding and SAM feature extraction are outside the hot path: the
 pipeline uses ``text_encoder``/``tokenizer``/``image_encoder`` when given, and also accepts precomputed
@@ -52,6 +55,30 @@ def variance_noise(scheduler, latent, model_dtype, generator, rng, shard=None, f
     if shard is not None:
         z = shard.take(z, frame_dim)
     return z.to(device=latent.device, dtype=latent.dtype).contiguous()
+
+
+class KeepRegion:
+    """What ``regenerate_mask`` pins while the rest of a given clip is regenerated: the clean panorama latent ``x0`` [1, 4, F, h, w],
+    the fp32 panorama noise [1, F, 4, h, w] the start latents were noised with, the mask [F, h, w] (float32; 1: regenerate, 0: keep),
+    the nearest-E2P tables of the views and the timesteps that are run.  ``apply`` is the launch after the two step launches of step
+    ``i``; the graphed steps call ``kernels.keep_latents`` themselves with ``coefficients_at`` uploaded to the device."""
+
+    def __init__(self, scheduler, steps, x0, noise, mask, idx, ok):
+        self.scheduler, self.steps = scheduler, list(steps)
+        self.x0, self.noise, self.mask, self.idx, self.ok = x0, noise, mask, idx, ok
+
+    def coefficients_at(self, t_host):
+        """``scheduler.keep_coefficients`` for the step at timestep ``t_host``; (1.0, 0.0) for a timestep the run does not hold (the
+        warm-up of a graphed step, whose numbers are dropped)."""
+        t = int(t_host)
+        return self.scheduler.keep_coefficients(self.steps, self.steps.index(t)) if t in self.steps else (1.0, 0.0)
+
+    def blend(self, pano_latent, pers_latent, sqrt_a=1.0, sqrt_b=0.0, coef_dev=None):
+        return kernels.keep_latents(pano_latent, pers_latent, self.x0, self.noise, self.mask, self.idx, self.ok, sqrt_a, sqrt_b,
+                                    coef_dev=coef_dev)
+
+    def apply(self, pano_latent, pers_latent, i):
+        return self.blend(pano_latent, pers_latent, *self.scheduler.keep_coefficients(self.steps, i))
 
 
 @dataclass
@@ -162,20 +189,36 @@ class AnimationPipeline:
         lat = torch.cat([self.vae.encode(x[i:i + chunk], min(chunk, b * f - i)).latent_dist.mode() for i in range(0, b * f, chunk)])
         return lat.reshape(b, f, *lat.shape[1:]).permute(0, 2, 1, 3, 4) * VAE_SCALE
 
-    def init_from_clip(self, x0, strength, video_length, equi_h, equi_w, pers_h, pers_w, cameras, device, latents_dtype=torch.float16):
+    def init_from_clip(self, x0, strength, video_length, equi_h, equi_w, pers_h, pers_w, cameras, device, latents_dtype=torch.float16,
+                       regenerate_mask=None):
         """The start of a run from a given clean panorama latent ``x0`` [1, 4, F, h, w] (SDEdit): ``init_noise``'s panorama noise
         draw at its place in the RNG order, the schedule entered at ``scheduler.timesteps_for_strength(strength)``, and ``x0`` noised
         to the first timestep that is run, the perspective start being the nearest-neighbour E2P resampling of the panorama start
-        (``kernels.noise_latents``, one launch).  Returns (pano_latent, pers_latent, steps)."""
+        (``kernels.noise_latents``, one launch).  Returns (pano_latent, pers_latent, steps); with ``regenerate_mask`` (float32
+        [F, h, w] on ``device``) a fourth value, the ``KeepRegion`` that holds on to the clean latent, this noise and the tables."""
         if tuple(x0.shape) != (1, 4, video_length, equi_h, equi_w):
             raise ValueError(f"the init latent must be [1, 4, {video_length}, {equi_h}, {equi_w}] (a clean panorama latent, multiplied by "
                              f"VAE_SCALE, such as pipe.last_latents[0]), got {tuple(x0.shape)}")
         noise, idx, ok = self.pano_noise_and_index(1, video_length, equi_h, equi_w, pers_h, pers_w, cameras, device)
         _, steps = self.scheduler.timesteps_for_strength(strength)
         sqrt_a, sqrt_b = self.scheduler.noise_coefficients(steps[0])
-        pano, pers = kernels.noise_latents(x0.to(device=device, dtype=latents_dtype).contiguous(), noise.squeeze(2), idx.to(torch.int32),
-                                           ok.to(torch.uint8), sqrt_a, sqrt_b)
+        x0, noise, idx, ok = x0.to(device=device, dtype=latents_dtype).contiguous(), noise.squeeze(2), idx.to(torch.int32), ok.to(torch.uint8)
+        pano, pers = kernels.noise_latents(x0, noise, idx, ok, sqrt_a, sqrt_b)
+        if regenerate_mask is not None:
+            return pano, pers, steps, KeepRegion(self.scheduler, steps, x0, noise, regenerate_mask, idx, ok)
         return pano, pers, steps
+
+    def prepare_regenerate_mask(self, mask, video_length, equi_h, equi_w, device):
+        """``regenerate_mask`` [1, F, 1, H', W'] (the layout and polarity of ``video_batch["pano_mask"]``: 1 regenerate, 0 keep) ->
+        float32 [F, h, w] on ``device``: nearest-resized to the panorama latent with the call of ``prepare_masked_latents_pano``,
+        clamped to [0, 1]."""
+        if mask.dim() != 5 or mask.shape[0] != 1 or mask.shape[2] != 1:
+            raise ValueError(f"regenerate_mask must be [1, F, 1, H, W] like video_batch['pano_mask'], got {tuple(mask.shape)}")
+        if mask.shape[1] != video_length:
+            raise ValueError(f"regenerate_mask has {mask.shape[1]} frames, the clip has video_length = {video_length}")
+        m = mask.to(device=device, dtype=torch.float32).transpose(2, 1)
+        m = F.interpolate(m, size=(m.shape[2], equi_h, equi_w))
+        return m.clamp(0.0, 1.0).reshape(video_length, equi_h, equi_w).contiguous()
 
     def _encode_chunks(self, x, chunk=8, keep_rows=None):
         """VAE-encode images [n, 3, H, W] in chunks of ``chunk`` and sample the posteriors (one randn per chunk, in order).
@@ -252,7 +295,7 @@ class AnimationPipeline:
                  video_batch=None, use_outpaint=False, use_ip_plus_cross_attention=False, use_fps_condition=False,
                  ip_plus_condition="image", prompt_embeds=None, sam_features=None, trace=None, frame_shard=None,
                  context_frames=None, context_overlap=4, context_weights="pyramid", guidance_rescale=0.0, context_loop=False,
-                 init_latents=None, init_video=None, strength=1.0, **kwargs):
+                 init_latents=None, init_video=None, strength=1.0, regenerate_mask=None, **kwargs):
         """``frame_shard`` (imagine360_amd.dist.FrameShard): this rank denoises a contiguous chunk of the frames (BASELINE
         configs 4 / 5); all ranks must be called with the same seeds and inputs.  Noise is drawn for the whole clip and
         cut, the VAE encodes / the loop runs / the VAE decodes only the local frames, the motion modules exchange tokens
@@ -279,7 +322,15 @@ class AnimationPipeline:
         ``init_noise`` makes, at the same place in the RNG order; both start latents come from one launch (``kernels.noise_latents``).
         Every loop variant runs the shortened schedule (graph replay, context windows, ``context_loop``, ``eta``,
         ``guidance_rescale``); not with ``frame_shard``.  Without an init, ``strength`` must be 1.0 and the call is the one without
-        these keywords."""
+        these keywords.
+        ``regenerate_mask`` (None: off; needs an init): [1, F, 1, H', W'] with values in [0, 1], the layout and polarity of
+        ``video_batch["pano_mask"]`` -- 1: regenerate, 0: keep the init clip, between: a blend.  Nearest-resized to the panorama latent
+        and clamped (``prepare_regenerate_mask``).  After the two step kernels of every step one launch (``kernels.keep_latents``)
+        blends both latents with the clean clip noised to the level the latents now have (``scheduler.keep_coefficients``: the next
+        timestep's, the clean clip after the last step), the perspective latent through the nearest-E2P tables of the start, so the
+        kept region of ``last_latents[0]`` is the init latent bit for bit; ``trace`` and ``callback`` see the blended latent.
+        ``regenerate_mask=video_batch["pano_mask"]`` pins the footage an outpainted panorama came from.  Independent of the model's
+        own mask channels; every loop variant; not with ``frame_shard``.  Without the keyword nothing of this runs."""
         device = self.device
         vb = video_batch
         plan = None
@@ -292,6 +343,11 @@ class AnimationPipeline:
         if init_latents is not None and init_video is not None:
             raise ValueError("give at most one of init_latents and init_video")
         has_init = init_latents is not None or init_video is not None
+        if regenerate_mask is not None and not has_init:
+            raise ValueError("regenerate_mask needs init_latents or init_video (the clip whose unmasked part is kept)")
+        if regenerate_mask is not None and frame_shard is not None:
+            raise ValueError("regenerate_mask cannot be combined with frame_shard (the cut of the kept clip, its noise and the mask to a "
+                             "rank's frames is not implemented)")
         strength = float(strength)
         if not has_init and strength != 1.0:
             raise ValueError(f"strength={strength} needs init_latents or init_video (a run from pure noise always runs the whole schedule)")
@@ -323,10 +379,13 @@ class AnimationPipeline:
         if has_init:
             # the encode draws nothing, so it may come first: the panorama noise is then drawn where init_noise draws it
             x0 = init_latents if init_latents is not None else self.encode_init_video(init_video.to(device))
-            pano_latent, pers_latent, steps_host = self.init_from_clip(x0, strength, f, H // 8, W // 8, ps // 8, ps // 8, cameras, device,
-                                                                       latents_dtype)
+            keep_mask = None if regenerate_mask is None else self.prepare_regenerate_mask(regenerate_mask, f, H // 8, W // 8, device)
+            pano_latent, pers_latent, steps_host, *region = self.init_from_clip(x0, strength, f, H // 8, W // 8, ps // 8, ps // 8, cameras,
+                                                                                device, latents_dtype, regenerate_mask=keep_mask)
+            region = region[0] if region else None             # (KeepRegion)
         else:
             pano_latent, pers_latent = self.init_noise(1, f, H // 8, W // 8, ps // 8, ps // 8, cameras, device, latents_dtype)
+            region = None
         sh = frame_shard
         if sh is not None:
             # every rank drew the whole clip's noise from the same seed: cut to the local frames
@@ -370,7 +429,7 @@ class AnimationPipeline:
                               reference_images_clip_feat_pers=feat_pers, relative_position_tensor=rel, pitchs_tensor=pitch)
                 pano_latent, pers_latent = self._windowed_loop(plan, inputs, cameras, pano_latent, pers_latent, steps_host, ts_dev,
                                                                guidance_scale_text, use_fps_condition, eta, generator, trace,
-                                                               callback, callback_steps, guidance_rescale)
+                                                               callback, callback_steps, guidance_rescale, region)
             graphed = None
             import torch.distributed as tdist
             capturable = sh is None or (tdist.is_initialized() and tdist.get_backend(sh.group) == "nccl")     # RCCL all-to-alls are stream ops
@@ -381,6 +440,8 @@ class AnimationPipeline:
                               fps_tensor_pano=fps_pano, fps_tensor_pers=fps_pers, reference_images_clip_feat_pano=feat_pano,
                               reference_images_clip_feat_pers=feat_pers, relative_position_tensor=rel, pitchs_tensor=pitch)
                 stoch = dict(eta=eta, generator=generator, frame_shard=sh) if eta > 0 else {}
+                if region is not None:
+                    stoch["keep"] = region
                 graphed = GraphedDenoiseStep(self.mv_base_model, self.scheduler, inputs, cameras, pano_latent, pers_latent,
                                              guidance_scale_text, use_fps=use_fps_condition, warmup=1, guidance_rescale=guidance_rescale, **stoch)       # one eager step fills every cache
             for i, t in enumerate(self.progress_bar(steps_host) if plan is None else ()):
@@ -397,6 +458,8 @@ class AnimationPipeline:
                     relative_position_tensor=rel, pitchs_tensor=pitch)
                 pano_latent = self._cfg_step(pred_pano, guidance_scale_text, t, pano_latent, eta, generator, sh, 2, guidance_rescale)
                 pers_latent = self._cfg_step(pred_pers, guidance_scale_text, t, pers_latent, eta, generator, sh, 3, guidance_rescale)
+                if region is not None:
+                    region.apply(pano_latent, pers_latent, i)
                 if trace is not None:
                     trace.append(pano_latent.clone())
                 if callback is not None and i % callback_steps == 0:
@@ -425,18 +488,20 @@ class AnimationPipeline:
         return self.scheduler.fused_cfg_step(u, c, g, t, latent, guidance_rescale=guidance_rescale)
 
     def _windowed_loop(self, plan, inputs, cameras, pano_latent, pers_latent, steps_host, ts_dev, g, use_fps, eta, generator,
-                       trace, callback, callback_steps, guidance_rescale=0.0):
+                       trace, callback, callback_steps, guidance_rescale=0.0, keep=None):
         """The denoising loop over sliding temporal context windows: per step one forward per window (slot order), then ONE
         blend + CFG + DDIM kernel per branch, panorama first.  RNG: as len(plan) successive calls of the model, then (eta > 0)
         the whole clip's panorama and perspective variance noise.  Captured in one hipGraph under the conditions of the
-        one-block loop (graph_step.GraphedWindowedStep), issued eagerly otherwise."""
+        one-block loop (graph_step.GraphedWindowedStep), issued eagerly otherwise.  ``keep`` (KeepRegion): its blend of the whole
+        clip after the two windows kernels of every step."""
         from .context import ip_cache_slots
         mv, sch = self.mv_base_model, self.scheduler
         with ip_cache_slots(mv, len(plan)):
             if self.use_graph and self.rng == "device" and pano_latent.is_cuda and trace is None and callback is None:
                 from .graph_step import GraphedWindowedStep
                 graphed = GraphedWindowedStep(mv, sch, inputs, cameras, pano_latent, pers_latent, g, plan, use_fps=use_fps, warmup=1,
-                                              eta=eta, generator=generator, guidance_rescale=guidance_rescale)
+                                              eta=eta, generator=generator, guidance_rescale=guidance_rescale,
+                                              **({} if keep is None else dict(keep=keep)))
                 for t in self.progress_bar(steps_host):
                     pano_latent, pers_latent = graphed.step(t)
                 return pano_latent, pers_latent
@@ -452,6 +517,8 @@ class AnimationPipeline:
                 pano_latent = sch.fused_cfg_step_windows(preds_pano, plan.starts_dev, plan.weights, g, t, pano_latent, noise=z, **kw)
                 z = variance_noise(sch, pers_latent, mdt, generator, self.rng, frame_dim=3) if eta > 0 else None
                 pers_latent = sch.fused_cfg_step_windows(preds_pers, plan.starts_dev, plan.weights, g, t, pers_latent, noise=z, **kw)
+                if keep is not None:
+                    keep.apply(pano_latent, pers_latent, i)
                 if trace is not None:
                     trace.append(pano_latent.clone())
                 if callback is not None and i % callback_steps == 0:

@@ -171,6 +171,15 @@ class DDIMScheduler:
         a_t = float(self.alphas_cumprod[int(timestep)])
         return _sqrt(a_t), _sqrt(1.0 - a_t)
 
+    def keep_coefficients(self, steps, i):
+        """(sqrt_a, sqrt_b) at which the kept region of a partly regenerated clip (pipeline ``regenerate_mask``) is noised AFTER step
+        ``i`` of the run's timestep list ``steps`` (arguments of ``kernels.keep_latents``): ``noise_coefficients(steps[i + 1])``, the
+        level of the latent that step has just produced, and (1.0, 0.0) -- the clean clip -- after the last step."""
+        i = int(i)
+        if not 0 <= i < len(steps):
+            raise ValueError(f"keep_coefficients: step {i} is not one of the {len(steps)} steps of the run")
+        return self.noise_coefficients(steps[i + 1]) if i + 1 < len(steps) else (1.0, 0.0)
+
     def timesteps_for_strength(self, strength):
         """Where a run that starts from a given clip enters the schedule of ``set_timesteps(N)`` (diffusers' img2img ``get_timesteps``):
         ``k = min(int(N * strength), N)`` steps are run, the last k of the schedule.  Returns ``(i0, steps)`` with ``i0 = N - k`` and

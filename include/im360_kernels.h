@@ -359,6 +359,28 @@ int im360_cfg_ddim_step_windows_ring_rescale(const void* pred, const void* x, co
 int im360_noise_latents(const void* x0, const float* noise, const int32_t* idx, const uint8_t* ok, void* out_pano, void* out_pers,
                         int64_t F, int64_t C, int64_t HW, int64_t M, int64_t Q, float sqrt_a, float sqrt_b, int dtype, void* stream);
 
+/* ---- regenerating part of a given clip (AnimationPipeline regenerate_mask): after every step of the loop both latents are blended,
+ * IN PLACE, with the clean clip noised to the level the latents now have; one launch after the two step launches:
+ *   known[c, f, p]   = T(sqrt_a * x0[c, f, p] + sqrt_b * noise[f, c, p])           the expression of im360_noise_latents, one rounding
+ *   pano[c, f, p]    = blend(pano[c, f, p], known[c, f, p], mask[f, p])
+ *   pers[m, c, f, q] = ok[m, q] ? blend(pers[m, c, f, q], known[c, f, idx[m, q]], mask[f, idx[m, q]]) : pers[m, c, f, q]
+ *   blend(x, k, w):  w >= 1 -> x, not stored;  w <= 0 -> k, bit for bit;  otherwise T(fma(w, x - k, k)) in fp32
+ * pano / x0: 16-bit [C, F, HW]; noise: fp32 [F, C, HW]; mask: fp32 [F, HW], 1 = regenerate, 0 = keep, one plane per frame shared by
+ * the channels; pers: 16-bit [M, C, F, Q]; idx int32 / ok uint8 [M, Q] as for im360_noise_latents.  sqrt_a, sqrt_b:
+ * DDIMScheduler.keep_coefficients; coef_dev: null, or device float[2] holding them, read by the kernel instead (graph replay).
+ * With mask 0 the latents are what im360_noise_latents writes for the same coefficients (pers: where ok), bit for bit.
+ * One workgroup per (c, f) plane; `known` is formed from x0 and noise (planes of up to 64 KiB are kept in LDS for the M * Q
+ * perspective elements, larger ones form them again) and never read back from pano, so the in-place update has no hazard between
+ * workgroups.  16-byte lanes when HW % 8 == 0, Q % 8 == 0 and every pointer is aligned for them, a scalar path otherwise.
+ * Refused: a null pointer (coef_dev excepted), a size <= 0, HW / C * F / M * Q >= 2^31, noise / mask / idx / coef_dev off 4 bytes,
+ * x0 == pano, an unknown dtype.  Precondition: 0 <= idx[m, q] < HW (clamped by the kernel).
+ * Replaces: the blend after scheduler.step of diffusers/pipelines/stable_diffusion/pipeline_stable_diffusion_inpaint_legacy.py:565-575
+ *   (`init_latents_proper = add_noise(init_latents_orig, noise, t); latents = init_latents_proper * mask + latents * (1 - mask)`, with
+ *   the opposite mask polarity), noised to the NEXT timestep as current diffusers does rather than to the step's own. */
+int im360_keep_latents(void* pano, void* pers, const void* x0, const float* noise, const float* mask, const int32_t* idx,
+                       const uint8_t* ok, int64_t F, int64_t C, int64_t HW, int64_t M, int64_t Q, float sqrt_a, float sqrt_b, int dtype,
+                       void* stream, const void* coef_dev);
+
 /* y[r] = LayerNorm(x[r] + pre[r % pre_period]) * gamma + beta + post[(r / post_div) % post_mod] on token rows
  * [rows, C]; pre / post are optional [*, C] tables (the WarpAttn spherical PE added before norm1, the motion
  * module's frame PE added after the norm).

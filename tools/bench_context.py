@@ -15,7 +15,11 @@ device events, with the bytes each has to move computed from the shapes.  Prints
                                                       # ends in a device synchronise) from pure noise and, with init_latents taken from a first call,
                                                       # at this strength, alternated --rounds times; over context windows when --frames > 16 (--loop:
                                                       # on a ring); and kernels.noise_latents at the size of that clip next to the torch-op composition
-                                                      # it replaces (device events, alternated), with the bytes the launch has to move"""
+                                                      # it replaces (device events, alternated), with the bytes the launch has to move
+    python tools/bench_context.py --strength 0.5 --regenerate-mask half [--frames 16]
+                                                      # part of the clip kept (pipeline regenerate_mask; even frames: the left half, odd frames: a
+                                                      # rectangle across the seam): the refinement call with the mask next to the same call without it,
+                                                      # alternated --rounds times, and kernels.keep_latents next to the torch ops it replaces"""
 import argparse
 import json
 import os
@@ -185,6 +189,70 @@ def time_noise_latents(sch, frames, dev, dt, iters, rounds=5):
     return res
 
 
+def half_mask(frames, H, W):
+    """[1, F, 1, H, W], 1 = regenerate: even frames keep the left half of the columns, odd frames a rectangle across the seam."""
+    m = torch.ones(1, frames, 1, H, W)
+    m[:, 0::2, :, :, :W // 2] = 0.0
+    m[:, 1::2, :, H // 4:3 * H // 4, 7 * W // 8:] = 0.0
+    m[:, 1::2, :, H // 4:3 * H // 4, :W // 8] = 0.0
+    return m
+
+
+def torch_keep_latents(pano, pers, x0, noise, mask, idx, ok, sqrt_a, sqrt_b):
+    """What ``kernels.keep_latents`` replaces, in torch ops: add_noise in fp32 and its rounding, the gather of it and of the mask by
+    the tables, and one lerp per branch (``idx`` int64, ``ok`` bool, ``mask`` [F, h, w]); results in fresh tensors."""
+    _, C, F, h, w = x0.shape
+    known = (sqrt_a * x0.float() + sqrt_b * noise.permute(0, 2, 1, 3, 4)).to(x0.dtype)
+    flat = idx.reshape(-1)
+    kg = known.reshape(C, F, h * w)[..., flat].reshape(C, F, *idx.shape).permute(2, 0, 1, 3, 4).unsqueeze(0)
+    wg = mask.reshape(F, h * w)[:, flat].reshape(F, *idx.shape).permute(1, 0, 2, 3)[None, :, None]
+    wg = torch.where(ok[None, :, None, None], wg, 1.0)
+    return torch.lerp(known, pano, mask[None, None].to(pano.dtype)), torch.lerp(kg, pers, wg.to(pers.dtype))
+
+
+def time_keep_latents(sch, frames, dev, dt, iters, rounds=5):
+    """Device-event time of ``kernels.keep_latents`` (in place) and of the torch-op composition on one clip under the half mask
+    (alternated round by round, ``iters`` back-to-back calls each), and the bytes the launch has to move: x0, noise and mask read, the
+    parts of the two latents the mask changes read (fractional values only) and written."""
+    from imagine360_amd import pano_geometry as G
+    cams = synthetic.icosahedron_cameras(90, PERS_PX)
+    idx64, okb = (t.to(dev) for t in G.nearest_e2p_index(*PANO_HW, *PERS_HW, cams))
+    idx32, ok8 = idx64.to(torch.int32), okb.to(torch.uint8)
+    x0, pano = (torch.randn(1, 4, frames, *PANO_HW, device=dev).to(dt) for _ in range(2))
+    pers = torch.randn(1, idx32.shape[0], 4, frames, *PERS_HW, device=dev).to(dt)
+    noise = torch.randn(1, frames, 4, *PANO_HW, device=dev)
+    mask = torch.nn.functional.interpolate(half_mask(frames, PANO_HW[0] * 8, PANO_HW[1] * 8).transpose(2, 1),
+                                           size=(frames, *PANO_HW))[0, 0].contiguous().to(dev)
+    sa, sb = sch.noise_coefficients(sch.timesteps_for_strength(0.5)[1][1])
+    fns = dict(kernel=lambda: kernels.keep_latents(pano, pers, x0, noise, mask, idx32, ok8, sa, sb),
+               torch_ops=lambda: torch_keep_latents(pano, pers, x0, noise, mask, idx64, okb, sa, sb))
+    b = fns["torch_ops"]()                                    # before the kernel blends in place
+    a = fns["kernel"]()
+    max_diff = max(float((a[0].float() - b[0].float()).abs().max()), float((a[1].float() - b[1].float()).abs().max()))
+    times = {k: [] for k in fns}
+    for r in range(rounds + 1):
+        for name, fn in fns.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            for _ in range(iters):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            if r:                                   # round 0 warms both up
+                times[name].append(e0.elapsed_time(e1) / iters * 1e3)
+    kept_pano = float((mask < 1).float().mean())
+    kept_pers = float(((mask.reshape(frames, -1)[:, idx64.reshape(-1)] < 1) & okb.reshape(-1)).float().mean())
+    nbytes = int(noise.numel() * 4 + x0.numel() * 2 + mask.numel() * 4 + kept_pano * pano.numel() * 2 + kept_pers * pers.numel() * 2)
+    res = {k: dict(us_min=min(v), us_median=statistics.median(v)) for k, v in times.items()}
+    res.update(bytes=nbytes, tables_bytes=idx32.numel() * 5, gb_per_s_kernel=nbytes / (res["kernel"]["us_min"] * 1e-6) / 1e9,
+               x0=list(x0.shape), pers=list(pers.shape), kept_fraction_pano=kept_pano, kept_fraction_pers=kept_pers,
+               max_abs_diff_from_torch_ops=max_diff,
+               note="event time over back-to-back calls on the same tensors (after the first call the kept region already holds the "
+                    "noised clip: the same loads and stores, the same values); the working set fits the Infinity Cache")
+    return res
+
+
 def strength_bench(args, sch, dev, dt):
     """--strength S: whole pipeline calls from pure noise and from the first call's latent at strength S."""
     import random
@@ -194,6 +262,9 @@ def strength_bench(args, sch, dev, dt):
     res = dict(tool="bench_context --strength", strength=args.strength, frames=frames, num_inference_steps=args.num_steps,
                pano_hw=PANO_HW, pers_hw=PERS_HW, dtype="bfloat16", device=torch.cuda.get_device_name(0))
     res["noise_latents"] = time_noise_latents(sch, frames, dev, dt, args.kernel_iters)
+    if args.regenerate_mask:
+        res["regenerate_mask"] = args.regenerate_mask
+        res["keep_latents"] = time_keep_latents(sch, frames, dev, dt, args.kernel_iters)
     if args.kernel_only:
         return res
     mv = configs.build_mv_model(1, device=dev, dtype=dt, xformers=True)
@@ -222,6 +293,8 @@ def strength_bench(args, sch, dev, dt):
     print("first call done", file=sys.stderr, flush=True)
     sch.set_timesteps(args.num_steps)
     steps = dict(from_noise=args.num_steps, refine=len(sch.timesteps_for_strength(args.strength)[1]))
+    if args.regenerate_mask:
+        return masked_refinement(args, res, call, x0, steps["refine"], half_mask(frames, PANO_HW[0] * 8, PANO_HW[1] * 8), fin)
     times = dict(from_noise=[], refine=[])
     for _ in range(args.rounds):
         for name, kw in (("from_noise", {}), ("refine", dict(init_latents=x0, strength=args.strength))):
@@ -232,6 +305,25 @@ def strength_bench(args, sch, dev, dt):
         res[k] = dict(call_ms=v, call_ms_min=min(v), steps=steps[k])
     res["ms_per_skipped_step"] = (res["from_noise"]["call_ms_min"] - res["refine"]["call_ms_min"]) / max(steps["from_noise"] - steps["refine"], 1)
     res["refine_over_from_noise"] = res["refine"]["call_ms_min"] / res["from_noise"]["call_ms_min"]
+    res["finite"] = fin
+    return res
+
+
+def masked_refinement(args, res, call, x0, steps, mask, fin):
+    """--regenerate-mask: the refinement call with the mask next to the same call without it, alternated."""
+    times = dict(refine=[], refine_masked=[])
+    init = dict(init_latents=x0, strength=args.strength)
+    for _ in range(args.rounds + 1):                       # (round 0 warms the masked call's shapes up)
+        for name, kw in (("refine", init), ("refine_masked", dict(regenerate_mask=mask, **init))):
+            ms, ok = call(**kw)
+            times[name].append(ms)
+            fin = fin and ok
+    for k, v in times.items():
+        res[k] = dict(call_ms=v[1:], call_ms_min=min(v[1:]), call_ms_median=statistics.median(v[1:]), steps=steps)
+    res["masked_minus_plain_ms_per_step"] = (res["refine_masked"]["call_ms_min"] - res["refine"]["call_ms_min"]) / steps
+    res["masked_over_plain"] = res["refine_masked"]["call_ms_min"] / res["refine"]["call_ms_min"]
+    # (an upper bound of the share of a step: the call time per step also holds the encode, the graph capture and the decode)
+    res["keep_latents_share_of_call_time_per_step"] = res["keep_latents"]["kernel"]["us_min"] * 1e-3 / (res["refine"]["call_ms_min"] / steps)
     res["finite"] = fin
     return res
 
@@ -247,6 +339,8 @@ def main():
     ap.add_argument("--strength", type=float, default=None, help="the refinement pass: pipeline calls with init_latents at this strength next to calls from pure noise")
     ap.add_argument("--frames", type=int, default=FRAMES, help="--strength: frames of the clip (context windows above 16)")
     ap.add_argument("--num-steps", type=int, default=6, help="--strength: num_inference_steps of every call")
+    ap.add_argument("--regenerate-mask", choices=["half"], default=None,
+                    help="--strength: keep part of the clip (pipeline regenerate_mask) and time that call next to the call without the mask")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_context.py measures on the MI355X; there is nothing to time without one"
