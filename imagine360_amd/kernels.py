@@ -66,6 +66,7 @@ _SIGNATURES = {
                                                                                                        _PTR, _PTR]),
     "im360_noise_latents": (_INT, [_PTR] * 6 + [_I64] * 5 + [_F32, _F32, _INT, _PTR]),
     "im360_keep_latents": (_INT, [_PTR] * 7 + [_I64] * 5 + [_F32, _F32, _INT, _PTR, _PTR]),
+    "im360_resize_pano_latent": (_INT, [_PTR] * 2 + [_I64] * 6 + [_INT, _INT, _PTR]),
     "im360_layernorm": (_INT, [_PTR] * 6 + [_I64] * 5 + [_F32, _INT, _PTR]),
     "im360_geglu": (_INT, [_PTR] * 2 + [_I64] * 2 + [_INT, _PTR]),
     "im360_linear_geglu": (_INT, [_PTR] * 4 + [_I64] * 3 + [_INT, _PTR]),
@@ -1061,6 +1062,36 @@ def keep_latents(pano, pers, x0, noise, mask, idx, ok, sqrt_a, sqrt_b, coef_dev=
                                   float(sqrt_a), float(sqrt_b), dt, _stream(), _p(coef_dev))
     _check(rc, "im360_keep_latents")
     return pano, pers
+
+
+RESIZE_MODES = {"bilinear": 0, "bicubic": 1}
+
+
+def resize_pano_latent(x, H, W, mode="bicubic"):
+    """A clean panorama latent upscaled as the equirectangular image it is, one launch: ``x`` 16-bit [1, C, F, h, w] -> [1, C, F, H, W]
+    with ``H >= h`` and ``W >= w`` (no antialiasing filter: shrinking is refused).  Half-pixel centres (``align_corners=False``) from
+    integer coordinates, ``mode`` "bilinear" or "bicubic" (Keys, A = -0.75: torch's), column taps wrap around the +-180 degree seam,
+    row taps clamp at the poles; fp32, horizontal pass then vertical, one rounding.  The definition is
+    ``pano_geometry.resize_pano_latent``; equal sizes return the input's bits."""
+    _dev(x)
+    dt = _dt(x)
+    if mode not in RESIZE_MODES:
+        raise ValueError(f"resize_pano_latent: mode must be one of {sorted(RESIZE_MODES)}, got {mode!r}")
+    if x.dim() != 5 or x.shape[0] != 1:
+        raise ValueError(f"resize_pano_latent: x must be [1, C, F, h, w], got {list(x.shape)}")
+    _, C, F, h, w = x.shape
+    if not (isinstance(H, int) and isinstance(W, int)) or isinstance(H, bool) or isinstance(W, bool):
+        raise TypeError(f"resize_pano_latent: H and W must be ints, got {H!r} and {W!r}")
+    if min(C, F, h, w) < 1:
+        raise ValueError(f"resize_pano_latent: x must not be empty, got {list(x.shape)}")
+    if H < h or W < w:
+        raise ValueError(f"resize_pano_latent: {h} x {w} -> {H} x {W} shrinks (there is no antialiasing filter; H >= h and W >= w)")
+    if not x.is_contiguous():
+        raise ValueError("resize_pano_latent: x must be contiguous")
+    out = torch.empty((1, C, F, H, W), dtype=x.dtype, device=x.device)
+    rc = lib().im360_resize_pano_latent(_p(x), _p(out), C, F, h, w, H, W, RESIZE_MODES[mode], dt, _stream())
+    _check(rc, "im360_resize_pano_latent")
+    return out
 
 
 # ------------------------------------------------------------------------------------------ tuning knobs

@@ -210,3 +210,51 @@ def nearest_e2p_index(eh, ew, ph, pw, cameras):
         idx.append(F.grid_sample(idx_img, grid, mode="nearest", padding_mode="zeros", align_corners=True)[0, 0].long())
         ok.append(F.grid_sample(one_img, grid, mode="nearest", padding_mode="zeros", align_corners=True)[0, 0] > 0.5)
     return torch.stack(idx), torch.stack(ok)
+
+
+# ------------------------------------------------------------------------------- resampling a panorama latent
+RESIZE_MODES = ("bilinear", "bicubic")
+
+
+def _resize_taps(n_in, n_out, mode, dtype, device):
+    """Taps of the ``n_out`` samples of an axis of ``n_in``: (first tap [n_out] int64, unwrapped and unclamped; weights [taps, n_out]).
+    Half-pixel centres from integers: sample ``o`` sits at ((2 o + 1) n_in - n_out) / (2 n_out) = i0 + t, 0 <= t < 1; no float
+    coordinate accumulates, and t is periodic in ``o`` for every integer scale."""
+    o = torch.arange(n_out, dtype=torch.int64, device=device)
+    num = (2 * o + 1) * n_in - n_out
+    i0 = torch.div(num, 2 * n_out, rounding_mode="floor")
+    t = (num - i0 * 2 * n_out).to(dtype) / (2 * n_out)
+    if mode == "bilinear":
+        return i0, torch.stack([1 - t, t])
+    A = -0.75                                            # torch's upsample_bicubic2d: cubic_convolution1 / cubic_convolution2
+    near = lambda x: ((A + 2) * x - (A + 3)) * x * x + 1
+    far = lambda x: ((A * x - 5 * A) * x + 8 * A) * x - 4 * A
+    return i0 - 1, torch.stack([far(t + 1), near(t), near(1 - t), far(2 - t)])
+
+
+def resize_pano_latent(x, H, W, mode="bicubic"):
+    """``x`` [..., h, w] -> [..., H, W], ``H >= h`` and ``W >= w``: a panorama latent upscaled as the equirectangular image it is.  The
+    eager definition of ``kernels.resize_pano_latent``, in torch ops on any device, blending in ``x``'s dtype (the weights are
+    formed in float32 for a 16-bit ``x``).  Half-pixel centres (``align_corners=False``) from integer coordinates; "bilinear": taps
+    i0, i0 + 1 with weights (1 - t, t); "bicubic": taps i0 - 1 .. i0 + 2, Keys kernel with A = -0.75.  Longitude wraps (column taps
+    mod w: no seam at +-180 degrees), latitude clamps (row taps in [0, h - 1]).  Horizontal pass, then vertical; a sum is
+    w0 a0 + w1 a1 + ... in this order.  Equal sizes return the input's values: t = 0, weights exactly (0, 1, 0, 0)."""
+    if mode not in RESIZE_MODES:
+        raise ValueError(f"resize_pano_latent: mode must be one of {sorted(RESIZE_MODES)}, got {mode!r}")
+    h, w = x.shape[-2:]
+    if H < h or W < w:
+        raise ValueError(f"resize_pano_latent: {h} x {w} -> {H} x {W} shrinks (there is no antialiasing filter; H >= h and W >= w)")
+    wdt = x.dtype if x.dtype in (torch.float32, torch.float64) else torch.float32
+
+    def blend(taps, weights):
+        acc = weights[0] * taps[0]
+        for wk, a in zip(weights[1:], taps[1:]):
+            acc = acc + wk * a
+        return acc
+
+    c0, wx = _resize_taps(w, W, mode, wdt, x.device)
+    wx = wx.to(x.dtype)
+    x = blend([x[..., (c0 + j) % w] for j in range(wx.shape[0])], wx)                                     # [..., h, W]
+    r0, wy = _resize_taps(h, H, mode, wdt, x.device)
+    wy = wy.to(x.dtype)[:, :, None]
+    return blend([x[..., (r0 + k).clamp(0, h - 1), :] for k in range(wy.shape[0])], wy)                    # [..., H, W]

@@ -21,6 +21,9 @@ surface, rebuilt for the MI355X:
   * regenerating part of such a clip (``regenerate_mask``): after the two step kernels of every step ONE more kernel
     (``kernels.keep_latents``) blends both latents with the clean clip noised to the level they now have, so the kept region ends as
     the input, bit for bit.
+  * a hi-res pass (``init_latents`` / ``init_video`` SMALLER than the run, ``init_resize``): the clean latent of a clip generated at the
+    trained size is upscaled once, as the equirectangular image it is (longitude wraps, latitude clamps), in ONE kernel
+    (``kernels.resize_pano_latent``) in front of everything above, which then sees a clean latent of the run's size.
 
 CLIP text encoding and SAM feature extraction are outside the hot path: the
 pipeline uses ``text_encoder``/``tokenizer``/``image_encoder`` when given, and also accepts precomputed
@@ -189,6 +192,19 @@ class AnimationPipeline:
         lat = torch.cat([self.vae.encode(x[i:i + chunk], min(chunk, b * f - i)).latent_dist.mode() for i in range(0, b * f, chunk)])
         return lat.reshape(b, f, *lat.shape[1:]).permute(0, 2, 1, 3, 4) * VAE_SCALE
 
+    def resize_init(self, x0, video_length, equi_h, equi_w, device, latents_dtype=torch.float16, init_resize="bicubic"):
+        """The clean init latent ``x0`` [1, 4, F, h, w] at the size of the run: itself when ``(h, w) == (equi_h, equi_w)`` -- no launch,
+        no copy -- and otherwise upscaled once (``kernels.resize_pano_latent``: half-pixel centres, ``init_resize`` "bicubic" or
+        "bilinear", columns wrap, rows clamp) in ``latents_dtype`` on ``device``.  ``ValueError``: another frame count, or an init that
+        is larger than the run in either dimension (there is no antialiasing filter)."""
+        if x0.dim() != 5 or tuple(x0.shape[:3]) != (1, 4, video_length) or x0.shape[3] > equi_h or x0.shape[4] > equi_w:
+            raise ValueError(f"the init latent must be [1, 4, {video_length}, {equi_h}, {equi_w}] or smaller in its last two dimensions "
+                             f"(a clean panorama latent, multiplied by VAE_SCALE, such as pipe.last_latents[0]; a smaller one is "
+                             f"upscaled, init_resize), got {tuple(x0.shape)}")
+        if tuple(x0.shape[3:]) == (equi_h, equi_w):
+            return x0
+        return kernels.resize_pano_latent(x0.to(device=device, dtype=latents_dtype).contiguous(), equi_h, equi_w, init_resize)
+
     def init_from_clip(self, x0, strength, video_length, equi_h, equi_w, pers_h, pers_w, cameras, device, latents_dtype=torch.float16,
                        regenerate_mask=None):
         """The start of a run from a given clean panorama latent ``x0`` [1, 4, F, h, w] (SDEdit): ``init_noise``'s panorama noise
@@ -295,7 +311,7 @@ class AnimationPipeline:
                  video_batch=None, use_outpaint=False, use_ip_plus_cross_attention=False, use_fps_condition=False,
                  ip_plus_condition="image", prompt_embeds=None, sam_features=None, trace=None, frame_shard=None,
                  context_frames=None, context_overlap=4, context_weights="pyramid", guidance_rescale=0.0, context_loop=False,
-                 init_latents=None, init_video=None, strength=1.0, regenerate_mask=None, **kwargs):
+                 init_latents=None, init_video=None, strength=1.0, regenerate_mask=None, init_resize="bicubic", **kwargs):
         """``frame_shard`` (imagine360_amd.dist.FrameShard): this rank denoises a contiguous chunk of the frames (BASELINE
         configs 4 / 5); all ranks must be called with the same seeds and inputs.  Noise is drawn for the whole clip and
         cut, the VAE encodes / the loop runs / the VAE decodes only the local frames, the motion modules exchange tokens
@@ -330,7 +346,15 @@ class AnimationPipeline:
         timestep's, the clean clip after the last step), the perspective latent through the nearest-E2P tables of the start, so the
         kept region of ``last_latents[0]`` is the init latent bit for bit; ``trace`` and ``callback`` see the blended latent.
         ``regenerate_mask=video_batch["pano_mask"]`` pins the footage an outpainted panorama came from.  Independent of the model's
-        own mask channels; every loop variant; not with ``frame_shard``.  Without the keyword nothing of this runs."""
+        own mask channels; every loop variant; not with ``frame_shard``.  Without the keyword nothing of this runs.
+        ``init_resize`` ("bicubic", or "bilinear"): the hi-res pass.  ``init_latents`` may be [1, 4, F, h, w] with ``h <= H/8`` and
+        ``w <= W/8`` and ``init_video`` [1, F, 3, 8h, 8w] (encoded at its own size, no RNG draw): a smaller clean latent is upscaled once
+        to the run's size before anything else sees it (``kernels.resize_pano_latent``, one launch: half-pixel centres, columns wrap
+        around the +-180 degree seam, rows clamp at the poles), so the noising, ``regenerate_mask`` (the kept region of
+        ``last_latents[0]`` is the UPSCALED clean latent bit for bit), both graphed steps, context windows, ``context_loop``, ``eta`` and
+        ``guidance_rescale`` run as for an init of the run's size and the RNG order is unchanged.  Generate at the trained size, then
+        call again with a ``video_batch`` of twice the size, ``init_latents=pipe.last_latents[0]`` and ``strength`` around 0.5.  An init
+        of the run's size never reaches the new code; a larger one, or another frame count, raises ``ValueError``."""
         device = self.device
         vb = video_batch
         plan = None
@@ -342,6 +366,8 @@ class AnimationPipeline:
             raise ValueError("context_loop cannot be combined with frame_shard (windows under frame sharding are not implemented)")
         if init_latents is not None and init_video is not None:
             raise ValueError("give at most one of init_latents and init_video")
+        if init_resize not in G.RESIZE_MODES:
+            raise ValueError(f"init_resize must be one of {sorted(G.RESIZE_MODES)}, got {init_resize!r}")
         has_init = init_latents is not None or init_video is not None
         if regenerate_mask is not None and not has_init:
             raise ValueError("regenerate_mask needs init_latents or init_video (the clip whose unmasked part is kept)")
@@ -379,6 +405,7 @@ class AnimationPipeline:
         if has_init:
             # the encode draws nothing, so it may come first: the panorama noise is then drawn where init_noise draws it
             x0 = init_latents if init_latents is not None else self.encode_init_video(init_video.to(device))
+            x0 = self.resize_init(x0, f, H // 8, W // 8, device, latents_dtype, init_resize)     # (itself at the run's size)
             keep_mask = None if regenerate_mask is None else self.prepare_regenerate_mask(regenerate_mask, f, H // 8, W // 8, device)
             pano_latent, pers_latent, steps_host, *region = self.init_from_clip(x0, strength, f, H // 8, W // 8, ps // 8, ps // 8, cameras,
                                                                                 device, latents_dtype, regenerate_mask=keep_mask)

@@ -381,6 +381,22 @@ int im360_keep_latents(void* pano, void* pers, const void* x0, const float* nois
                        const uint8_t* ok, int64_t F, int64_t C, int64_t HW, int64_t M, int64_t Q, float sqrt_a, float sqrt_b, int dtype,
                        void* stream, const void* coef_dev);
 
+/* ---- upscaling a clean panorama latent (AnimationPipeline init_latents / init_video at a lower resolution than the run, init_resize),
+ * one launch: x [C, F, h, w] -> out [C, F, H, W], H >= h, W >= w, one 16-bit dtype; mode 0 bilinear, 1 bicubic.
+ *   out[c, f, Y, X] = T(sum_r wy[Y][r] * (sum_j wx[X][j] * x[c, f, row(Y, r), col(X, j)]))     fp32, horizontal pass then vertical, one rounding
+ * Half-pixel centres (align_corners=False) from integers: num = (2 X + 1) w - W, i0 = floor(num / 2 W), t = float(num - i0 * 2 W) /
+ * float(2 W) (one rounding; exactly periodic in X for every integer scale), rows alike.  Bilinear: taps i0, i0 + 1, weights (1 - t, t);
+ * bicubic: taps i0 - 1 .. i0 + 2, Keys kernel, A = -0.75 (the polynomials of torch's upsample_bicubic2d).  The image is
+ * equirectangular: column taps wrap (mod w), row taps clamp to [0, h - 1].  Equal sizes return the input's bits (t = 0).
+ * One workgroup per (plane, 8 output rows); eight columns per lane and one 16-byte store when W % 8 == 0 and both pointers are
+ * 16-byte aligned, a scalar path otherwise, the same bits on both; source rows are read from global memory (cache-resident planes).
+ * Refused: a null pointer, a size <= 0, h / w / H / C * F / 8 W >= 2^31 (32-bit rows and columns; coordinates and element offsets
+ * are 64-bit), C * F * ceil(H / 8) >= 2^24 workgroups (a launch holds fewer than 2^32 threads), a pointer off 2 bytes, x == out, H < h or W < w (no antialiasing filter), an unknown mode or dtype.
+ * Replaces: nothing in the reference (it upscales the decoded video with an external super-resolution stage); the latent-upscale
+ *   pass of diffusers (F.interpolate on the latent), made aware of the +-180 degree seam. */
+int im360_resize_pano_latent(const void* x, void* out, int64_t C, int64_t F, int64_t h, int64_t w, int64_t H, int64_t W, int mode,
+                             int dtype, void* stream);
+
 /* y[r] = LayerNorm(x[r] + pre[r % pre_period]) * gamma + beta + post[(r / post_div) % post_mod] on token rows
  * [rows, C]; pre / post are optional [*, C] tables (the WarpAttn spherical PE added before norm1, the motion
  * module's frame PE added after the norm).

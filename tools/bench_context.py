@@ -19,7 +19,14 @@ device events, with the bytes each has to move computed from the shapes.  Prints
     python tools/bench_context.py --strength 0.5 --regenerate-mask half [--frames 16]
                                                       # part of the clip kept (pipeline regenerate_mask; even frames: the left half, odd frames: a
                                                       # rectangle across the seam): the refinement call with the mask next to the same call without it,
-                                                      # alternated --rounds times, and kernels.keep_latents next to the torch ops it replaces"""
+                                                      # alternated --rounds times, and kernels.keep_latents next to the torch ops it replaces
+    python tools/bench_context.py --init-scale 2 --strength 0.5 [--pano-hw 128 256] [--frames 16] [--num-steps 20]
+                                                      # the hi-res pass: a first pipeline call from pure noise at 1/N of the size plus a second call
+                                                      # at the full size from its latent (init_latents smaller than the run: kernels.resize_pano_latent)
+                                                      # at this strength, next to ONE call from pure noise at the full size, alternated --rounds times
+                                                      # after one warm-up of every shape; and kernels.resize_pano_latent at these sizes, both modes, next
+                                                      # to the eager definition pano_geometry.resize_pano_latent on the GPU.  --pano-hw: the latent size
+                                                      # of the full-size run (default 128 256: BASELINE cfg5, 1024 x 2048 pixels)"""
 import argparse
 import json
 import os
@@ -253,6 +260,98 @@ def time_keep_latents(sch, frames, dev, dt, iters, rounds=5):
     return res
 
 
+def time_resize(small_hw, big_hw, frames, dev, dt, iters, rounds=5):
+    """Device-event time of ``kernels.resize_pano_latent`` and of the eager definition ``pano_geometry.resize_pano_latent`` on the GPU,
+    both modes (alternated round by round, ``iters`` back-to-back calls each, allocation of the result included), the spread over the
+    rounds, and the bytes the launch has to move."""
+    from imagine360_amd import pano_geometry as G
+    x = (1.5 * torch.randn(1, 4, frames, *small_hw, device=dev)).to(dt)
+    res = dict(x=list(x.shape), out=[1, 4, frames, *big_hw], bytes=x.numel() * 2 + 4 * frames * big_hw[0] * big_hw[1] * 2, iters=iters, rounds=rounds)
+    for mode in G.RESIZE_MODES:
+        fns = dict(kernel=lambda: kernels.resize_pano_latent(x, *big_hw, mode), eager=lambda: G.resize_pano_latent(x, *big_hw, mode))
+        ref = G.resize_pano_latent(x.double(), *big_hw, mode)
+        diff = {k: float((fn().double() - ref).abs().max()) for k, fn in fns.items()}
+        times = {k: [] for k in fns}
+        for r in range(rounds + 1):
+            for name, fn in fns.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                for _ in range(iters):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                if r:                                   # round 0 warms both up
+                    times[name].append(e0.elapsed_time(e1) / iters * 1e3)
+        res[mode] = {k: dict(us_min=min(v), us_median=statistics.median(v), us_max=max(v), max_abs_diff_from_fp64=diff[k]) for k, v in times.items()}
+        res[mode]["eager_over_kernel"] = res[mode]["eager"]["us_min"] / res[mode]["kernel"]["us_min"]
+    res["note"] = ("event time over back-to-back calls; the eager definition blends in bf16 (several roundings), the kernel in fp32 (one); "
+                   "the working set fits the Infinity Cache")
+    return res
+
+
+def hires_bench(args, sch, dev, dt):
+    """--init-scale N: the two-pass run (1 / N of the size from pure noise, then the full size from its latent at --strength) next to one
+    run from pure noise at the full size; whole pipeline calls (encode, loop, decode), host clock around a call that ends in a device
+    synchronise."""
+    import random
+
+    from imagine360_amd.pipeline import AnimationPipeline
+    n, frames, big = args.init_scale, args.frames, tuple(args.pano_hw)
+    assert big[0] % n == 0 and big[1] % n == 0, f"--pano-hw {big} is not a multiple of --init-scale {n}"
+    small = (big[0] // n, big[1] // n)
+    res = dict(tool="bench_context --init-scale", init_scale=n, strength=args.strength, frames=frames, num_inference_steps=args.num_steps,
+               pano_hw=list(big), first_pass_pano_hw=list(small), dtype="bfloat16", device=torch.cuda.get_device_name(0))
+    res["resize_pano_latent"] = time_resize(small, big, frames, dev, dt, args.kernel_iters)
+    if args.kernel_only:
+        return res
+    mv = configs.build_mv_model(1, device=dev, dtype=dt, xformers=True)
+    mv.dual_stream, mv.warp_streams = True, True
+    vae = configs.build_vae(1, device=dev, dtype=dt)
+    pipe = AnimationPipeline(vae, None, None, mv.unet, mv.pano_unet, mv, DDIMScheduler(**configs.NOISE_SCHEDULER_KWARGS), None, "SAM").to(dev)
+    pipe._no_progress = True
+    vbs = {hw: synthetic.video_batch(frames=frames, pano_hw=(hw[0] * 8, hw[1] * 8), seed=1) for hw in (small, big)}
+    cond = synthetic.conditioning(frames=max(frames, 16), seed=1)
+    windows = dict(context_frames=LENGTH, context_overlap=OVERLAP, context_loop=args.loop) if frames > LENGTH else {}
+    res["windows"] = windows
+
+    def call(hw, **kw):
+        torch.manual_seed(21)
+        random.seed(21)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        vid = pipe("synthetic", num_inference_steps=args.num_steps, guidance_scale_text=7.5, negative_prompt="", latents_dtype=dt,
+                   video_batch=vbs[hw], use_outpaint=True, use_ip_plus_cross_attention=True, use_fps_condition=True, ip_plus_condition="video",
+                   prompt_embeds=(cond["text_pano"], cond["text_pers"]), sam_features=(cond["sam_pano"], cond["sam_pers"]), **windows, **kw).videos
+        torch.cuda.synchronize()
+        assert tuple(vid.shape[-2:]) == (hw[0] * 8, hw[1] * 8)
+        return (time.perf_counter() - t0) * 1e3, bool(torch.isfinite(vid).all())
+
+    def two_pass():
+        a, ok_a = call(small)
+        b, ok_b = call(big, init_latents=pipe.last_latents[0], strength=args.strength)
+        return dict(first_pass_ms=a, second_pass_ms=b, total_ms=a + b), ok_a and ok_b
+
+    sch.set_timesteps(args.num_steps)
+    res["steps"] = dict(first_pass=args.num_steps, second_pass=len(sch.timesteps_for_strength(args.strength)[1]), direct=args.num_steps)
+    warm, fin = two_pass()                                  # warms every shape of both sizes up
+    res["warm_up"] = dict(two_pass=warm, direct_ms=call(big)[0])
+    print("warm-up done", file=sys.stderr, flush=True)
+    runs = dict(two_pass=[], direct=[])
+    for _ in range(args.rounds):
+        t, ok = two_pass()
+        runs["two_pass"].append(t)
+        ms, ok2 = call(big)
+        runs["direct"].append(ms)
+        fin = fin and ok and ok2
+    res["two_pass"] = dict(calls=runs["two_pass"], total_ms_min=min(r["total_ms"] for r in runs["two_pass"]),
+                           total_ms_max=max(r["total_ms"] for r in runs["two_pass"]))
+    res["direct"] = dict(call_ms=runs["direct"], call_ms_min=min(runs["direct"]), call_ms_max=max(runs["direct"]))
+    res["two_pass_over_direct"] = res["two_pass"]["total_ms_min"] / res["direct"]["call_ms_min"]
+    res["finite"] = fin
+    return res
+
+
 def strength_bench(args, sch, dev, dt):
     """--strength S: whole pipeline calls from pure noise and from the first call's latent at strength S."""
     import random
@@ -341,6 +440,9 @@ def main():
     ap.add_argument("--num-steps", type=int, default=6, help="--strength: num_inference_steps of every call")
     ap.add_argument("--regenerate-mask", choices=["half"], default=None,
                     help="--strength: keep part of the clip (pipeline regenerate_mask) and time that call next to the call without the mask")
+    ap.add_argument("--init-scale", type=int, default=None,
+                    help="with --strength: the hi-res pass -- a first call at 1/N of --pano-hw, a second call at --pano-hw from its latent -- next to one call from pure noise at --pano-hw")
+    ap.add_argument("--pano-hw", type=int, nargs=2, default=[128, 256], metavar=("H", "W"), help="--init-scale: latent size of the full-size run (default: cfg5)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_context.py measures on the MI355X; there is nothing to time without one"
@@ -350,6 +452,9 @@ def main():
     sch = DDIMScheduler(**configs.NOISE_SCHEDULER_KWARGS)
     sch.set_timesteps(25)
     ts_host = [int(t) for t in sch._timesteps_host]
+    if args.init_scale is not None:
+        assert args.strength is not None and args.init_scale >= 1, "--init-scale N (>= 1) goes with --strength"
+        return emit(hires_bench(args, sch, dev, dt), args.out)
     if args.strength is not None:
         return emit(strength_bench(args, sch, dev, dt), args.out)
     if args.loop:
