@@ -234,6 +234,11 @@ extern "C" __attribute__((visibility("hidden"))) void im360_set_error(const char
             return IM360_ERR_LAUNCH;                                  \
         }                                                             \
     } while (0)
+// what a launcher returns behind its launch
+static inline int im360_launch_status() {
+    IM360_CHECK_LAUNCH();
+    return IM360_OK;
+}
 
 // ---- value -> template argument (host-side launchers): a run-time dtype / flag / small integer picks an instantiation
 namespace im360 {

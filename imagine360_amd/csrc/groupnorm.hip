@@ -591,361 +591,6 @@ __global__ void circular_pad_hw_kernel(const U* __restrict__ x, U* __restrict__ 
     }
 }
 
-// ---- CFG combine + DDIM v-prediction update (eta = 0), one elementwise pass
-//      (pipeline_animation_inference_dual.py:791-800; diffusers/schedulers/scheduling_ddim.py:300-350):
-//      v = u + g (c - u);  x_prev = cx * x + cv * v   with cx, cv precomputed on the host in fp64
-template <typename T>
-__global__ void cfg_ddim_kernel(const T* __restrict__ uncond, const T* __restrict__ cond, const T* __restrict__ x,
-                                T* __restrict__ out, long n8, float g, float cx, float cv, const float* __restrict__ coef) {
-    if (coef != nullptr) {          // (guidance, cx, cv) read on the device: the launch can be replayed from a hipGraph
-        g = coef[0];
-        cx = coef[1];
-        cv = coef[2];
-    }
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
-        float u[8], c[8], s[8];
-        unpack8<T>(((const uint4*)uncond)[i], u);
-        unpack8<T>(((const uint4*)cond)[i], c);
-        unpack8<T>(((const uint4*)x)[i], s);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) s[e] = cx * s[e] + cv * (u[e] + g * (c[e] - u[e]));
-        ((uint4*)out)[i] = pack8<T>(s);
-    }
-}
-
-// ---- CFG combine + the full DDIMScheduler.step (diffusers/schedulers/scheduling_ddim.py:251-373), one elementwise pass:
-//      m = u + g (c - u);  x0 / e from the prediction type (mode bits 0-1: 0 epsilon, 1 v, 2 sample);  x0 clamped to [-1, 1]
-//      (bit 2);  e re-derived from the clamped x0 (bit 3);  out = sa_prev x0 + dir e + sigma z.  sa, sb = sqrt(a_t), sqrt(1 - a_t);
-//      dir = sqrt(1 - a_prev - sigma^2), sigma = eta sqrt(var) come from fp64 host math.  noise == nullptr: z = 0.
-// The step arithmetic of one element, shared by cfg_ddim_step_kernel and cfg_ddim_step_windows_kernel: m is the guided model output,
-// s the sample, z the variance noise (0 without one); isa = 1 / sa, isb = 1 / sb.
-struct DdimCoefs {
-    float g, sa, sb, sap, dir, sigma, isa, isb;
-    int pred;
-    bool clip, clipped_out;
-};
-
-__device__ __forceinline__ DdimCoefs ddim_coefs(float g, float sa, float sb, float sap, float dir, float sigma, int mode,
-                                                const float* __restrict__ coef) {
-    if (coef != nullptr) {          // (guidance, sa, sb, sa_prev, dir, sigma) read on the device: hipGraph replay
-        g = coef[0];
-        sa = coef[1];
-        sb = coef[2];
-        sap = coef[3];
-        dir = coef[4];
-        sigma = coef[5];
-    }
-    DdimCoefs k;
-    k.g = g, k.sa = sa, k.sb = sb, k.sap = sap, k.dir = dir, k.sigma = sigma;
-    k.isa = 1.0f / sa, k.isb = 1.0f / sb;
-    k.pred = mode & 3;
-    k.clip = (mode & 4) != 0, k.clipped_out = (mode & 8) != 0;
-    return k;
-}
-
-__device__ __forceinline__ float cfg_combine(float u, float c, float g) { return u + g * (c - u); }
-
-__device__ __forceinline__ float ddim_step_elem(float m, float s, float z, const DdimCoefs& k) {
-    float x0, eps;
-    if (k.pred == 0) {
-        x0 = (s - k.sb * m) * k.isa;
-        eps = m;
-    } else if (k.pred == 1) {
-        x0 = k.sa * s - k.sb * m;
-        eps = k.sa * m + k.sb * s;
-    } else {
-        x0 = m;
-        eps = m;                     // the reference's direction term multiplies the model output, i.e. x0 itself
-    }
-    if (k.clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-    if (k.clipped_out) eps = (s - k.sa * x0) * k.isb;
-    return k.sap * x0 + k.dir * eps + k.sigma * z;
-}
-
-// ---- guidance rescale (arXiv 2305.08891, section 3.4): m' = r m with r = phi std(c) / std(m) + (1 - phi), the standard deviations
-//      (correction 1) over the whole tensor.  Two launches: a statistics pass writes one record of partial moments per workgroup,
-//      and every workgroup of the step kernel merges ALL records itself, in one fixed order, so that all of them multiply by the
-//      same bits -- no atomics, no counter, no workgroup waits for another one, nothing read back by the host.
-//      Moments are carried as (count, mean, M2 = sum (x - mean)^2) and merged with Chan's formula, never as sum x, sum x^2: the
-//      variance of a prediction whose mean is far from zero would cancel in fp32.  c and m share the count.  Counts are fp32
-//      (exact below 2^24 elements, 6e-8 relative above).
-struct CfgMoments {
-    float n, mc, qc, mm, qm;         // count;  mean, M2 of the text prediction c;  mean, M2 of the guided prediction m
-};
-
-constexpr int kRescaleMaxRecords = 256;      // grid cap of the statistics pass (about one workgroup per CU) = threads of a consumer
-constexpr int kRescaleRecord = 8;            // floats per record (five used)
-
-// a <- a (+) b, Chan et al.; an empty side leaves the other one untouched
-__device__ __forceinline__ void moments_merge(CfgMoments& a, const CfgMoments& b) {
-    if (b.n == 0.0f) return;
-    if (a.n == 0.0f) {
-        a = b;
-        return;
-    }
-    const float n = a.n + b.n, f = b.n / n, w = a.n * f;
-    const float dc = b.mc - a.mc, dm = b.mm - a.mm;
-    a.mc = __fmaf_rn(dc, f, a.mc);
-    a.qc = __fmaf_rn(dc * dc, w, a.qc + b.qc);
-    a.mm = __fmaf_rn(dm, f, a.mm);
-    a.qm = __fmaf_rn(dm * dm, w, a.qm + b.qm);
-    a.n = n;
-}
-
-// a <- a (+) the cnt (1 .. 8) leading values of c[] / m[]: their own mean first, then the squared distances to it
-__device__ __forceinline__ void moments_add(CfgMoments& a, const float* c, const float* m, int cnt) {
-    float sc = 0.0f, sm = 0.0f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        if (e < cnt) {
-            sc += c[e];
-            sm += m[e];
-        }
-    }
-    CfgMoments b;
-    b.n = (float)cnt;
-    b.mc = sc / b.n, b.mm = sm / b.n;
-    b.qc = 0.0f, b.qm = 0.0f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        if (e < cnt) {
-            const float dc = c[e] - b.mc, dm = m[e] - b.mm;
-            b.qc = __fmaf_rn(dc, dc, b.qc);
-            b.qm = __fmaf_rn(dm, dm, b.qm);
-        }
-    }
-    moments_merge(a, b);
-}
-
-// The moments of a workgroup of exactly 256 threads (four waves; every kernel that calls this is launched so and carries
-// __launch_bounds__(256)), valid in thread 0: lane l takes lane l + 1, + 2, ... + 32 of its wave (lane 0 ends with
-// lanes 0 .. 63 in ascending order), then thread 0 takes the four waves in ascending order.  `lds`: 4 records.
-__device__ __forceinline__ CfgMoments moments_block_reduce(CfgMoments a, CfgMoments* lds) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        CfgMoments b;
-        b.n = __shfl_down(a.n, o), b.mc = __shfl_down(a.mc, o), b.qc = __shfl_down(a.qc, o);
-        b.mm = __shfl_down(a.mm, o), b.qm = __shfl_down(a.qm, o);
-        moments_merge(a, b);          // (lanes past 63 - o read their own value: never part of what lane 0 collects)
-    }
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = a;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        a = lds[0];
-        for (int w = 1; w < (int)(blockDim.x >> 6); ++w) moments_merge(a, lds[w]);
-    }
-    return a;
-}
-
-__device__ __forceinline__ void moments_store(float* __restrict__ ws, const CfgMoments& a) {
-    float* rec = ws + (long)blockIdx.x * kRescaleRecord;
-    rec[0] = a.n, rec[1] = a.mc, rec[2] = a.qc, rec[3] = a.mm, rec[4] = a.qm;
-}
-
-// r from the nrec records of a statistics pass, the same bits in every thread of every workgroup that calls it.  One record per
-// thread: nrec <= kRescaleMaxRecords = 256 = blockDim.x (im360_cfg_rescale_records caps the statistics grid there).
-__device__ __forceinline__ float rescale_factor(const float* ws, int nrec, float phi) {
-    __shared__ CfgMoments lds[4];
-    __shared__ float r_lds;
-    CfgMoments a;
-    a.n = a.mc = a.qc = a.mm = a.qm = 0.0f;
-    if ((int)threadIdx.x < nrec) {
-        const float* rec = ws + (long)threadIdx.x * kRescaleRecord;
-        a.n = rec[0], a.mc = rec[1], a.qc = rec[2], a.mm = rec[3], a.qm = rec[4];
-    }
-    a = moments_block_reduce(a, lds);
-    if (threadIdx.x == 0) {
-        const float std_c = sqrtf(a.qc / (a.n - 1.0f)), std_m = sqrtf(a.qm / (a.n - 1.0f));
-        r_lds = phi * std_c / std_m + (1.0f - phi);          // std_m = 0 or n = 1: inf / NaN, as the formula gives
-    }
-    __syncthreads();
-    return r_lds;
-}
-
-// statistics pass over (u, c): n8 16-byte lanes, grid <= kRescaleMaxRecords, one record per workgroup
-template <typename T>
-__global__ __launch_bounds__(256) void cfg_rescale_stats_kernel(const T* __restrict__ uncond, const T* __restrict__ cond, long n8,
-                                                                 float g, const float* __restrict__ coef, float* __restrict__ ws) {
-    __shared__ CfgMoments lds[4];
-    if (coef != nullptr) g = coef[0];
-    CfgMoments a;
-    a.n = a.mc = a.qc = a.mm = a.qm = 0.0f;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
-        float u[8], c[8], m[8];
-        unpack8<T>(((const uint4*)uncond)[i], u);
-        unpack8<T>(((const uint4*)cond)[i], c);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) m[e] = cfg_combine(u[e], c[e], g);
-        moments_add(a, c, m, 8);
-    }
-    a = moments_block_reduce(a, lds);
-    if (threadIdx.x == 0) moments_store(ws, a);
-}
-
-// r alone, for tests and tools: one workgroup, the reduction every step workgroup makes
-__global__ __launch_bounds__(256) void cfg_rescale_factor_kernel(const float* __restrict__ ws, int nrec, float phi, float* __restrict__ out) {
-    const float r = rescale_factor(ws, nrec, phi);
-    if (threadIdx.x == 0) out[0] = r;
-}
-
-// r * m as ONE fp32 multiplication of exactly these two values.  This file is built with -ffast-math: without the two value barriers
-// hipcc folds r into the step's coefficients in one kernel and into the blend's division in another, and the windows kernel would
-// no longer give the plain kernel's bits for one uniform window.
-__device__ __forceinline__ float rescale_mul(float r, float m) {
-    asm volatile("" : "+v"(m));
-    float p = r * m;
-    asm volatile("" : "+v"(p));
-    return p;
-}
-
-// RS: the guided prediction is multiplied by rescale_factor(ws, nrec, phi) before the step; those instantiations need workgroups of
-// 256 threads and say so in their launch bounds (1024 is the default, i.e. what the kernel without the factor always had)
-template <typename T, bool RS>
-__global__ __launch_bounds__(RS ? 256 : 1024) void cfg_ddim_step_kernel(const T* __restrict__ uncond, const T* __restrict__ cond, const T* __restrict__ x,
-                                     const T* __restrict__ noise, T* __restrict__ out, long n8, float g, float sa, float sb,
-                                     float sap, float dir, float sigma, int mode, const float* __restrict__ coef,
-                                     const float* __restrict__ ws, int nrec, float phi) {
-    const DdimCoefs k = ddim_coefs(g, sa, sb, sap, dir, sigma, mode, coef);
-    float r = 1.0f;
-    if (RS) r = rescale_factor(ws, nrec, phi);
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
-        float u[8], c[8], s[8], z[8];
-        unpack8<T>(((const uint4*)uncond)[i], u);
-        unpack8<T>(((const uint4*)cond)[i], c);
-        unpack8<T>(((const uint4*)x)[i], s);
-        if (noise != nullptr) unpack8<T>(((const uint4*)noise)[i], z);
-        else {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) z[e] = 0.0f;
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float m = cfg_combine(u[e], c[e], k.g);
-            s[e] = ddim_step_elem(RS ? rescale_mul(r, m) : m, s[e], z[e], k);
-        }
-        ((uint4*)out)[i] = pack8<T>(s);
-    }
-}
-
-// ---- the same step on the per-frame blend of sliding temporal context windows.  x / noise / out are [outer, F, inner]; the
-//      predictions of all windows sit in one buffer pred[nW, 2, outer, L, inner] (window, CFG half, the model's own layout);
-//      start[nW] ascending window start frames, weight[L] the blend weight of each position inside a window.  Per element at frame f:
-//          m = (sum_k w[f - s_k] (u_k + g (c_k - u_k))) / (sum_k w[f - s_k])   over the windows with s_k <= f < s_k + L, k ascending
-//      (a fixed summation order: deterministic), then ddim_step_elem; one rounding, at the store.  V = 8: 16-byte lanes (inner % 8
-//      == 0, so a lane never straddles a frame); V = 1: the scalar path for any inner.  The first covering window initialises the
-//      sums, so one window with weight 1 gives m = 1 * m_0 / 1 = m_0 exactly: bit-identical to cfg_ddim_step_kernel.
-//      wrap = 0: the windows lie on a line (above).  wrap = F: they lie on a ring of F frames, window k covers the frames
-//      (s_k + j) mod F, j = 0 .. L - 1, and a frame in front of s_k is at position f - s_k + F.  One integer compare-and-add per
-//      window and lane; slot order and float arithmetic are those of the line.  j indexes pred / weight only when 0 <= j < L,
-//      whatever the table holds.
-// The blend of the V elements from element e0 on (V = 8: one 16-byte lane inside one frame): mb[] = the guided prediction m above;
-// cb[] (CB only) = the same blend of the text half c_k alone, what the guidance rescale takes std(c) of.
-template <typename T, int V, bool CB>
-__device__ __forceinline__ void windows_blend(const T* __restrict__ pred, const int* __restrict__ start, const float* __restrict__ weight,
-                                              int nW, int F, int L, int wrap, long inner, long half, long e0, float g, float* mb, float* cb) {
-    const long r = e0 % inner, of = e0 / inner;
-    const int f = (int)(of % F);
-    const long o = of / F;
-    float acc[V], cacc[V];
-#pragma unroll
-    for (int e = 0; e < V; ++e) acc[e] = cacc[e] = 0.0f;
-    float wsum = 0.0f;
-    bool first = true;
-    for (int w = 0; w < nW; ++w) {
-        int j = f - start[w];
-        if (j < 0) j += wrap;
-        if (j < 0 || j >= L) continue;
-        const float wt = weight[j];
-        const long at = (long)w * 2 * half + (o * L + j) * inner + r;
-        float u[V], c[V];
-        if (V == 8) {
-            unpack8<T>(*(const uint4*)(pred + at), u);
-            unpack8<T>(*(const uint4*)(pred + at + half), c);
-        } else {
-            u[0] = to_f32<T>(pred[at]);
-            c[0] = to_f32<T>(pred[at + half]);
-        }
-#pragma unroll
-        for (int e = 0; e < V; ++e) {
-            const float m = wt * cfg_combine(u[e], c[e], g);
-            acc[e] = first ? m : acc[e] + m;
-            if (CB) {
-                const float t = wt * c[e];
-                cacc[e] = first ? t : cacc[e] + t;
-            }
-        }
-        wsum = first ? wt : wsum + wt;
-        first = false;
-    }
-#pragma unroll
-    for (int e = 0; e < V; ++e) {
-        mb[e] = acc[e] / wsum;
-        if (CB) cb[e] = cacc[e] / wsum;
-    }
-}
-
-// statistics pass of the guidance rescale over the blends (windows_blend: the step kernel's own m, and c blended the same way), the
-// moments over the whole clip [outer, F, inner].  A thread takes the elements in the groups of 8 of cfg_rescale_stats_kernel for
-// either V (V = 1: eight scalar blends, the last group may be short), so one uniform window with L = F writes that kernel's records.
-template <typename T, int V>
-__global__ __launch_bounds__(256) void cfg_rescale_stats_windows_kernel(const T* __restrict__ pred, const int* __restrict__ start,
-                                                                         const float* __restrict__ weight, int nW, long outer, int F, int L,
-                                                                         int wrap, long inner, float g, const float* __restrict__ coef,
-                                                                         float* __restrict__ ws) {
-    __shared__ CfgMoments lds[4];
-    if (coef != nullptr) g = coef[0];
-    const long n = outer * F * inner, n8 = (n + 7) / 8;
-    const long half = outer * L * inner;
-    CfgMoments a;
-    a.n = a.mc = a.qc = a.mm = a.qm = 0.0f;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
-        float c[8], m[8];
-        int cnt = 8;
-        if (V == 8) windows_blend<T, 8, true>(pred, start, weight, nW, F, L, wrap, inner, half, i * 8, g, m, c);
-        else {
-            cnt = (int)(n - i * 8 < 8 ? n - i * 8 : 8);
-#pragma unroll
-            for (int e = 0; e < 8; ++e)
-                if (e < cnt) windows_blend<T, 1, true>(pred, start, weight, nW, F, L, wrap, inner, half, i * 8 + e, g, &m[e], &c[e]);
-        }
-        moments_add(a, c, m, cnt);
-    }
-    a = moments_block_reduce(a, lds);
-    if (threadIdx.x == 0) moments_store(ws, a);
-}
-
-template <typename T, int V, bool RS>
-__global__ __launch_bounds__(RS ? 256 : 1024) void cfg_ddim_step_windows_kernel(const T* __restrict__ pred, const T* __restrict__ x, const T* __restrict__ noise,
-                                             T* __restrict__ out, const int* __restrict__ start, const float* __restrict__ weight,
-                                             int nW, long outer, int F, int L, int wrap, long inner, float g, float sa, float sb, float sap,
-                                             float dir, float sigma, int mode, const float* __restrict__ coef,
-                                             const float* __restrict__ ws, int nrec, float phi) {
-    const DdimCoefs k = ddim_coefs(g, sa, sb, sap, dir, sigma, mode, coef);
-    float r = 1.0f;
-    if (RS) r = rescale_factor(ws, nrec, phi);
-    const long nv = outer * F * inner / V;
-    const long half = outer * L * inner;              // one CFG half of one window
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
-        float m[V], s[V], z[V];
-        windows_blend<T, V, false>(pred, start, weight, nW, F, L, wrap, inner, half, i * V, k.g, m, nullptr);
-        if (V == 8) {
-            unpack8<T>(((const uint4*)x)[i], s);
-            if (noise != nullptr) unpack8<T>(((const uint4*)noise)[i], z);
-        } else {
-            s[0] = to_f32<T>(x[i]);
-            if (noise != nullptr) z[0] = to_f32<T>(noise[i]);
-        }
-        if (noise == nullptr) {
-#pragma unroll
-            for (int e = 0; e < V; ++e) z[e] = 0.0f;
-        }
-#pragma unroll
-        for (int e = 0; e < V; ++e) s[e] = ddim_step_elem(RS ? rescale_mul(r, m[e]) : m[e], s[e], z[e], k);
-        if (V == 8) ((uint4*)out)[i] = pack8<T>(s);
-        else out[i] = from_f32<T>(s[0]);
-    }
-}
-
 static inline int pick_slabs(long N, long HW) {
     long s = (2048 + N - 1) / N;
     const long maxs = HW / 64 > 0 ? HW / 64 : 1;
@@ -1003,8 +648,7 @@ extern "C" __attribute__((visibility("default"))) int im360_groupnorm_stats(cons
     ProfScope prof(PROF_GN_STATS, stream);
     if (dtype == 0) launch_gn_stats<__bf16>(x, nullptr, C, 0, gamma, beta, partial, scale, shift, N, H, W, G, pad, eps, (hipStream_t)stream);
     else launch_gn_stats<_Float16>(x, nullptr, C, 0, gamma, beta, partial, scale, shift, N, H, W, G, pad, eps, (hipStream_t)stream);
-    IM360_CHECK_LAUNCH();
-    return IM360_OK;
+    return im360_launch_status();
 }
 
 // Per-slab partial sums only (no finalize, no pad weighting): partial fp32 [N][S][2][C], S = im360_gn_num_slabs(N, H, W).
@@ -1018,8 +662,7 @@ extern "C" __attribute__((visibility("default"))) int im360_groupnorm_partial(co
     const int S = pick_slabs(N, H * W);
     if (dtype == 0) hipLaunchKernelGGL((gn_partial_kernel<__bf16>), dim3(S, (unsigned)N), dim3(256), 0, (hipStream_t)stream, (const __bf16*)x, (float*)partial, (int)(H * W), (int)W, (int)C, 0, S, (int)C, 0);
     else hipLaunchKernelGGL((gn_partial_kernel<_Float16>), dim3(S, (unsigned)N), dim3(256), 0, (hipStream_t)stream, (const _Float16*)x, (float*)partial, (int)(H * W), (int)W, (int)C, 0, S, (int)C, 0);
-    IM360_CHECK_LAUNCH();
-    return IM360_OK;
+    return im360_launch_status();
 }
 
 // scale / shift [N, C1 + C2] from partial sums: channels [0, C1) from pa ([N][Sa][2][C1]), [C1, C1 + C2) from pb ([N][Sb][2][C2];
@@ -1040,8 +683,7 @@ extern "C" __attribute__((visibility("default"))) int im360_groupnorm_finalize(c
                                        (const __bf16*)gamma, (const __bf16*)beta, (float*)scale, (float*)shift, (int)G, count, eps);
     else hipLaunchKernelGGL((gn_finalize2_kernel<_Float16>), dim3((unsigned)N), dim3(256), dyn, (hipStream_t)stream, (const float*)pa, (int)Sa, (int)C1, (const float*)pb, (int)Sb, (int)C2,
                             (const _Float16*)gamma, (const _Float16*)beta, (float*)scale, (float*)shift, (int)G, count, eps);
-    IM360_CHECK_LAUNCH();
-    return IM360_OK;
+    return im360_launch_status();
 }
 
 // GroupNorm statistics of the channel concatenation [xa | xb] without materialising it (xa [N,H,W,C1], xb [N,H,W,C2];
@@ -1061,8 +703,7 @@ extern "C" __attribute__((visibility("default"))) int im360_groupnorm_stats_cat(
     ProfScope prof(PROF_GN_STATS, stream);
     if (dtype == 0) launch_gn_stats<__bf16>(xa, xb, C1, C2, gamma, beta, partial, scale, shift, N, H, W, G, pad, eps, (hipStream_t)stream);
     else launch_gn_stats<_Float16>(xa, xb, C1, C2, gamma, beta, partial, scale, shift, N, H, W, G, pad, eps, (hipStream_t)stream);
-    IM360_CHECK_LAUNCH();
-    return IM360_OK;
+    return im360_launch_status();
 }
 
 // y [N, H, W + 2 pad, C] = act(x * scale + shift) with circular W addressing; act: 0 none, 1 SiLU
@@ -1079,8 +720,7 @@ extern "C" __attribute__((visibility("default"))) int im360_groupnorm_apply(cons
     ProfScope prof(PROF_GN_APPLY, stream);
     if (dtype == 0) launch_gn_apply<__bf16>(x, nullptr, C, 0, scale, shift, y, N, H, W, pad, act, (hipStream_t)stream);
     else launch_gn_apply<_Float16>(x, nullptr, C, 0, scale, shift, y, N, H, W, pad, act, (hipStream_t)stream);
-    IM360_CHECK_LAUNCH();
-    return IM360_OK;
+    return im360_launch_status();
 }
 
 // y [N, H, W + 2 pad, C1 + C2] = act([xa | xb] * scale + shift): the normalised concatenation is written directly, the
@@ -1098,8 +738,7 @@ extern "C" __attribute__((visibility("default"))) int im360_groupnorm_apply_cat(
     ProfScope prof(PROF_GN_APPLY, stream);
     if (dtype == 0) launch_gn_apply<__bf16>(xa, xb, C1, C2, scale, shift, y, N, H, W, pad, act, (hipStream_t)stream);
     else launch_gn_apply<_Float16>(xa, xb, C1, C2, scale, shift, y, N, H, W, pad, act, (hipStream_t)stream);
-    IM360_CHECK_LAUNCH();
-    return IM360_OK;
+    return im360_launch_status();
 }
 
 // Per-slab partial sums with the circular-pad weighting of im360_groupnorm_stats (the `pad` wrapped columns count twice):
@@ -1116,8 +755,7 @@ extern "C" __attribute__((visibility("default"))) int im360_groupnorm_partial_pa
     const int S = pick_slabs(N, H * W);
     if (dtype == 0) hipLaunchKernelGGL((gn_partial_kernel<__bf16>), dim3(S, (unsigned)N), dim3(256), 0, (hipStream_t)stream, (const __bf16*)x, (float*)partial, (int)(H * W), (int)W, (int)C, (int)pad, S, (int)C, 0);
     else hipLaunchKernelGGL((gn_partial_kernel<_Float16>), dim3(S, (unsigned)N), dim3(256), 0, (hipStream_t)stream, (const _Float16*)x, (float*)partial, (int)(H * W), (int)W, (int)C, (int)pad, S, (int)C, 0);
-    IM360_CHECK_LAUNCH();
-    return IM360_OK;
+    return im360_launch_status();
 }
 
 // y [N, H, W + 2 pad, C1 + C2] = act(GroupNorm([xa | xb])) straight from PARTIAL SUMS: channels [0, C1) of the statistics from pa
@@ -1169,8 +807,7 @@ extern "C" __attribute__((visibility("default"))) int im360_groupnorm_apply_part
             case 6: launch(t, I4{}, std::true_type{}, std::true_type{}); break;
             default: launch(t, I4{}, std::true_type{}, std::false_type{}); break;
         }
-        IM360_CHECK_LAUNCH();
-        return IM360_OK;
+        return im360_launch_status();
     });
 }
 
@@ -1208,8 +845,7 @@ extern "C" __attribute__((visibility("default"))) int im360_groupnorm_fused(cons
         hipLaunchKernelGGL((gn_fused_kernel<_Float16>), dim3((unsigned)(N * S)), dim3(256), dyn, s, (const _Float16*)xa, (const _Float16*)xb, (int)C1, (int)C2,
                            (float*)partial, (int*)counter, (const _Float16*)gamma, (const _Float16*)beta, (_Float16*)y, (int)H, (int)W, (int)G,
                            (int)pad, act, S, eps, C);
-    IM360_CHECK_LAUNCH();
-    return IM360_OK;
+    return im360_launch_status();
 }
 
 // x [rows, W, C] -> y [rows, W + 2 pad, C], circular along W (16-bit elements, C % 8 == 0)
@@ -1225,8 +861,7 @@ extern "C" __attribute__((visibility("default"))) int im360_circular_pad_w(const
     // a byte copy of 16-bit elements: one instantiation serves both dtypes
     hipLaunchKernelGGL((circular_pad_w_kernel<uint16_t>), dim3(blocks), dim3(256), 0, (hipStream_t)stream,
                        (const uint16_t*)x, (uint16_t*)y, (long)rows, (int)W, (int)(C / 8), (int)pad);
-    IM360_CHECK_LAUNCH();
-    return IM360_OK;
+    return im360_launch_status();
 }
 
 // x [N, H, W] -> y [N, H + top + bottom, W + left + right], circular in both axes; elements of `esize` bytes (1, 2, 4, 8).
@@ -1255,257 +890,5 @@ extern "C" __attribute__((visibility("default"))) int im360_circular_pad_hw(cons
     else if (u == 2) IM360_PAD(uint16_t);
     else IM360_PAD(uint8_t);
 #undef IM360_PAD
-    IM360_CHECK_LAUNCH();
-    return IM360_OK;
-}
-
-// out = cx * x + cv * (uncond + g (cond - uncond)), n elements (n % 8 == 0), all same dtype
-extern "C" __attribute__((visibility("default"))) int im360_cfg_ddim_update(const void* uncond, const void* cond, const void* x, void* out, int64_t n,
-                                     float guidance, float cx, float cv, int dtype, void* stream, const void* coef_dev) {
-    using namespace im360;
-    IM360_CHECK_ARG(uncond && cond && x && out, "cfg_ddim_update: null pointer");
-    IM360_CHECK_ARG(n > 0 && (n % 8) == 0, "cfg_ddim_update: n=%ld must be a positive multiple of 8", (long)n);
-    IM360_CHECK_ARG(((uintptr_t)uncond % 16) == 0 && ((uintptr_t)cond % 16) == 0 && ((uintptr_t)x % 16) == 0 &&
-                    ((uintptr_t)out % 16) == 0, "cfg_ddim_update: misaligned pointer");
-    const long n8 = n / 8;
-    const unsigned blocks = (unsigned)((n8 + 255) / 256 > 4096 ? 4096 : (n8 + 255) / 256);
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == 0)
-        hipLaunchKernelGGL((cfg_ddim_kernel<__bf16>), dim3(blocks), dim3(256), 0, s, (const __bf16*)uncond,
-                           (const __bf16*)cond, (const __bf16*)x, (__bf16*)out, n8, guidance, cx, cv, (const float*)coef_dev);
-    else if (dtype == 1)
-        hipLaunchKernelGGL((cfg_ddim_kernel<_Float16>), dim3(blocks), dim3(256), 0, s, (const _Float16*)uncond,
-                           (const _Float16*)cond, (const _Float16*)x, (_Float16*)out, n8, guidance, cx, cv, (const float*)coef_dev);
-    else {
-        im360_set_error("cfg_ddim_update: dtype %d unsupported", dtype);
-        return IM360_ERR_UNSUPPORTED;
-    }
-    IM360_CHECK_LAUNCH();
-    return IM360_OK;
-}
-
-// Records a statistics pass of the guidance rescale writes for n elements = its grid: one workgroup per 256 groups of 8 elements,
-// at most kRescaleMaxRecords (every consumer thread reads one record).
-extern "C" __attribute__((visibility("default"))) int64_t im360_cfg_rescale_records(int64_t n) {
-    const int64_t blocks = ((n + 7) / 8 + 255) / 256;
-    return blocks < 1 ? 1 : blocks > im360::kRescaleMaxRecords ? im360::kRescaleMaxRecords : blocks;
-}
-
-// the workspace of n elements: present, 4-byte aligned, large enough for the grid
-#define IM360_CHECK_RESCALE_WS(name, n)                                                                                             \
-    IM360_CHECK_ARG(ws && ((uintptr_t)ws % 4) == 0, name ": null or misaligned workspace");                                          \
-    IM360_CHECK_ARG(ws_floats >= im360_cfg_rescale_records(n) * im360::kRescaleRecord, name ": workspace of %ld floats, %ld needed", \
-                    (long)ws_floats, (long)(im360_cfg_rescale_records(n) * im360::kRescaleRecord))
-
-// partial moments of cond and of uncond + g (cond - uncond) over n elements (n % 8 == 0) -> ws
-extern "C" __attribute__((visibility("default"))) int im360_cfg_rescale_stats(const void* uncond, const void* cond, int64_t n, float guidance,
-                                   void* ws, int64_t ws_floats, int dtype, void* stream, const void* coef_dev) {
-    using namespace im360;
-    IM360_CHECK_ARG(uncond && cond, "cfg_rescale_stats: null pointer");
-    IM360_CHECK_ARG(n > 0 && (n % 8) == 0, "cfg_rescale_stats: n=%ld must be a positive multiple of 8", (long)n);
-    IM360_CHECK_ARG(((uintptr_t)uncond % 16) == 0 && ((uintptr_t)cond % 16) == 0, "cfg_rescale_stats: misaligned pointer");
-    IM360_CHECK_RESCALE_WS("cfg_rescale_stats", n);
-    const unsigned blocks = (unsigned)im360_cfg_rescale_records(n);
-    hipStream_t s = (hipStream_t)stream;
-    return with_dtype(dtype, "cfg_rescale_stats", [&](auto t) {
-        using T = typename decltype(t)::type;
-        hipLaunchKernelGGL((cfg_rescale_stats_kernel<T>), dim3(blocks), dim3(256), 0, s, (const T*)uncond, (const T*)cond, (long)(n / 8),
-                           guidance, (const float*)coef_dev, (float*)ws);
-        IM360_CHECK_LAUNCH();
-        return IM360_OK;
-    });
-}
-
-namespace im360 {
-// im360_cfg_rescale_stats_windows (wrap = 0) and im360_cfg_rescale_stats_windows_ring (wrap = F) behind their argument checks
-static int launch_cfg_rescale_stats_windows(const char* name, const void* pred, const void* start, const void* weight, int nW, int64_t outer,
-                                            int64_t F, int64_t L, int wrap, int64_t inner, float guidance, void* ws, int dtype, void* stream,
-                                            const void* coef_dev) {
-    const bool vec = (inner % 8) == 0 && ((uintptr_t)pred % 16) == 0;
-    const unsigned blocks = (unsigned)im360_cfg_rescale_records(outer * F * inner);
-    hipStream_t s = (hipStream_t)stream;
-    return with_dtype(dtype, name, [&](auto t) {
-        using T = typename decltype(t)::type;
-        with_const<1, 8>(vec ? 8 : 1, [&](auto v) {
-            hipLaunchKernelGGL((cfg_rescale_stats_windows_kernel<T, decltype(v)::value>), dim3(blocks), dim3(256), 0, s, (const T*)pred,
-                               (const int*)start, (const float*)weight, nW, (long)outer, (int)F, (int)L, wrap, (long)inner, guidance,
-                               (const float*)coef_dev, (float*)ws);
-        });
-        IM360_CHECK_LAUNCH();
-        return IM360_OK;
-    });
-}
-}  // namespace im360
-
-#define IM360_CHECK_CFG_RESCALE_STATS_WINDOWS(name)                                                                                  \
-    IM360_CHECK_ARG(pred && start && weight, name ": null pointer");                                                                 \
-    IM360_CHECK_ARG(nW > 0 && outer > 0 && inner > 0 && L > 0 && L <= F && F < (1 << 30),                                            \
-                    name ": nW=%d outer=%ld F=%ld L=%ld inner=%ld out of range", nW, (long)outer, (long)F, (long)L, (long)inner);    \
-    IM360_CHECK_ARG(((uintptr_t)start % 4) == 0 && ((uintptr_t)weight % 4) == 0, name ": misaligned table");                         \
-    IM360_CHECK_RESCALE_WS(name, outer * F * inner)
-
-// the same over the per-frame blends of nW sliding-window predictions (layout and tables of im360_cfg_ddim_step_windows)
-extern "C" __attribute__((visibility("default"))) int im360_cfg_rescale_stats_windows(const void* pred, const void* start, const void* weight, int nW,
-                                   int64_t outer, int64_t F, int64_t L, int64_t inner, float guidance, void* ws, int64_t ws_floats,
-                                   int dtype, void* stream, const void* coef_dev) {
-    IM360_CHECK_CFG_RESCALE_STATS_WINDOWS("cfg_rescale_stats_windows");
-    return im360::launch_cfg_rescale_stats_windows("cfg_rescale_stats_windows", pred, start, weight, nW, outer, F, L, 0, inner, guidance, ws,
-                                                   dtype, stream, coef_dev);
-}
-
-// the same with the windows on a ring of F frames (tables of im360_cfg_ddim_step_windows_ring).  The host cannot see the tables:
-// the caller guarantees 0 <= start[k] < F, every frame covered, L <= F.
-extern "C" __attribute__((visibility("default"))) int im360_cfg_rescale_stats_windows_ring(const void* pred, const void* start, const void* weight,
-                                   int nW, int64_t outer, int64_t F, int64_t L, int64_t inner, float guidance, void* ws,
-                                   int64_t ws_floats, int dtype, void* stream, const void* coef_dev) {
-    IM360_CHECK_CFG_RESCALE_STATS_WINDOWS("cfg_rescale_stats_windows_ring");
-    return im360::launch_cfg_rescale_stats_windows("cfg_rescale_stats_windows_ring", pred, start, weight, nW, outer, F, L, (int)F, inner,
-                                                   guidance, ws, dtype, stream, coef_dev);
-}
-
-// out[0] = r = phi std(c) / std(m) + (1 - phi) from the records a statistics pass over n elements left in ws
-extern "C" __attribute__((visibility("default"))) int im360_cfg_rescale_factor(const void* ws, int64_t ws_floats, int64_t n, float phi, void* out,
-                                   void* stream) {
-    using namespace im360;
-    IM360_CHECK_ARG(out && ((uintptr_t)out % 4) == 0 && n > 0, "cfg_rescale_factor: null or misaligned output / empty problem");
-    IM360_CHECK_ARG(std::isfinite(phi), "cfg_rescale_factor: rescale=%g must be finite", (double)phi);
-    IM360_CHECK_RESCALE_WS("cfg_rescale_factor", n);
-    hipLaunchKernelGGL(cfg_rescale_factor_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)ws,
-                       (int)im360_cfg_rescale_records(n), phi, (float*)out);
-    IM360_CHECK_LAUNCH();
-    return IM360_OK;
-}
-
-namespace im360 {
-// im360_cfg_ddim_step (ws == nullptr) and im360_cfg_ddim_step_rescale behind their argument checks
-static int launch_cfg_ddim_step(const char* name, const void* uncond, const void* cond, const void* x, const void* noise, void* out,
-                                int64_t n, float guidance, float sqrt_a, float sqrt_b, float sqrt_a_prev, float dir, float sigma,
-                                int mode, int dtype, void* stream, const void* coef_dev, const void* ws, float phi) {
-    const long n8 = n / 8;
-    const unsigned blocks = (unsigned)((n8 + 255) / 256 > 4096 ? 4096 : (n8 + 255) / 256);
-    const int nrec = ws ? (int)im360_cfg_rescale_records(n) : 0;
-    hipStream_t s = (hipStream_t)stream;
-    return with_dtype(dtype, name, [&](auto t) {
-        using T = typename decltype(t)::type;
-        with_bool(ws != nullptr, [&](auto rs) {
-            hipLaunchKernelGGL((cfg_ddim_step_kernel<T, decltype(rs)::value>), dim3(blocks), dim3(256), 0, s, (const T*)uncond,
-                               (const T*)cond, (const T*)x, (const T*)noise, (T*)out, n8, guidance, sqrt_a, sqrt_b, sqrt_a_prev, dir,
-                               sigma, mode, (const float*)coef_dev, (const float*)ws, nrec, phi);
-        });
-        IM360_CHECK_LAUNCH();
-        return IM360_OK;
-    });
-}
-
-static int launch_cfg_ddim_step_windows(const char* name, const void* pred, const void* x, const void* noise, void* out, const void* start,
-                                        const void* weight, int nW, int64_t outer, int64_t F, int64_t L, int wrap, int64_t inner, float guidance,
-                                        float sqrt_a, float sqrt_b, float sqrt_a_prev, float dir, float sigma, int mode, int dtype,
-                                        void* stream, const void* coef_dev, const void* ws, float phi) {
-    const bool vec = (inner % 8) == 0 && ((uintptr_t)pred % 16) == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)noise % 16) == 0 &&
-                     ((uintptr_t)out % 16) == 0;
-    const long nv = (long)(outer * F * inner) / (vec ? 8 : 1);
-    const unsigned blocks = (unsigned)((nv + 255) / 256 > 4096 ? 4096 : (nv + 255) / 256);
-    const int nrec = ws ? (int)im360_cfg_rescale_records(outer * F * inner) : 0;
-    hipStream_t s = (hipStream_t)stream;
-    return with_dtype(dtype, name, [&](auto t) {
-        using T = typename decltype(t)::type;
-        with_const<1, 8>(vec ? 8 : 1, [&](auto v) { with_bool(ws != nullptr, [&](auto rs) {
-            hipLaunchKernelGGL((cfg_ddim_step_windows_kernel<T, decltype(v)::value, decltype(rs)::value>), dim3(blocks), dim3(256), 0, s,
-                               (const T*)pred, (const T*)x, (const T*)noise, (T*)out, (const int*)start, (const float*)weight, nW,
-                               (long)outer, (int)F, (int)L, wrap, (long)inner, guidance, sqrt_a, sqrt_b, sqrt_a_prev, dir, sigma, mode,
-                               (const float*)coef_dev, (const float*)ws, nrec, phi);
-        }); });
-        IM360_CHECK_LAUNCH();
-        return IM360_OK;
-    });
-}
-}  // namespace im360
-
-#define IM360_CHECK_CFG_DDIM_STEP(name)                                                                                              \
-    IM360_CHECK_ARG(uncond && cond && x && out, name ": null pointer");                                                              \
-    IM360_CHECK_ARG(n > 0 && (n % 8) == 0, name ": n=%ld must be a positive multiple of 8", (long)n);                                \
-    IM360_CHECK_ARG(((uintptr_t)uncond % 16) == 0 && ((uintptr_t)cond % 16) == 0 && ((uintptr_t)x % 16) == 0 &&                      \
-                    ((uintptr_t)noise % 16) == 0 && ((uintptr_t)out % 16) == 0, name ": misaligned pointer");                        \
-    IM360_CHECK_ARG(mode >= 0 && mode < 16 && (mode & 3) != 3, name ": mode %d unsupported", mode);                                  \
-    IM360_CHECK_ARG(noise || coef_dev || sigma == 0.0f, name ": sigma=%g needs a noise tensor", (double)sigma)
-
-#define IM360_CHECK_CFG_DDIM_STEP_WINDOWS(name)                                                                                      \
-    IM360_CHECK_ARG(pred && x && out && start && weight, name ": null pointer");                                                     \
-    IM360_CHECK_ARG(nW > 0 && outer > 0 && inner > 0 && L > 0 && L <= F && F < (1 << 30),                                            \
-                    name ": nW=%d outer=%ld F=%ld L=%ld inner=%ld out of range", nW, (long)outer, (long)F, (long)L, (long)inner);    \
-    IM360_CHECK_ARG(mode >= 0 && mode < 16 && (mode & 3) != 3, name ": mode %d unsupported", mode);                                  \
-    IM360_CHECK_ARG(noise || coef_dev || sigma == 0.0f, name ": sigma=%g needs a noise tensor", (double)sigma);                      \
-    IM360_CHECK_ARG(((uintptr_t)start % 4) == 0 && ((uintptr_t)weight % 4) == 0, name ": misaligned table")
-
-// out = DDIMScheduler.step(uncond + g (cond - uncond), x, noise) for any prediction type / clip / eta, n elements (n % 8 == 0),
-// all same dtype; noise may be null (zero noise)
-extern "C" __attribute__((visibility("default"))) int im360_cfg_ddim_step(const void* uncond, const void* cond, const void* x, const void* noise,
-                                   void* out, int64_t n, float guidance, float sqrt_a, float sqrt_b, float sqrt_a_prev,
-                                   float dir, float sigma, int mode, int dtype, void* stream, const void* coef_dev) {
-    IM360_CHECK_CFG_DDIM_STEP("cfg_ddim_step");
-    return im360::launch_cfg_ddim_step("cfg_ddim_step", uncond, cond, x, noise, out, n, guidance, sqrt_a, sqrt_b, sqrt_a_prev, dir, sigma,
-                                       mode, dtype, stream, coef_dev, nullptr, 0.0f);
-}
-
-// the same step on r (uncond + g (cond - uncond)), r from the records im360_cfg_rescale_stats left in ws for the same n
-extern "C" __attribute__((visibility("default"))) int im360_cfg_ddim_step_rescale(const void* uncond, const void* cond, const void* x, const void* noise,
-                                   void* out, int64_t n, float guidance, float sqrt_a, float sqrt_b, float sqrt_a_prev,
-                                   float dir, float sigma, int mode, float phi, const void* ws, int64_t ws_floats, int dtype,
-                                   void* stream, const void* coef_dev) {
-    IM360_CHECK_CFG_DDIM_STEP("cfg_ddim_step_rescale");
-    IM360_CHECK_ARG(std::isfinite(phi), "cfg_ddim_step_rescale: rescale=%g must be finite", (double)phi);
-    IM360_CHECK_RESCALE_WS("cfg_ddim_step_rescale", n);
-    return im360::launch_cfg_ddim_step("cfg_ddim_step_rescale", uncond, cond, x, noise, out, n, guidance, sqrt_a, sqrt_b, sqrt_a_prev, dir,
-                                       sigma, mode, dtype, stream, coef_dev, ws, phi);
-}
-
-// The step of im360_cfg_ddim_step on the per-frame weighted blend of nW sliding-window predictions (see the kernel's comment):
-// x / noise / out [outer, F, inner], pred [nW, 2, outer, L, inner], start int32[nW] and weight float[L] on the device.  The host
-// cannot see the tables: the caller guarantees 0 <= start[k] <= F - L and that every frame is covered (imagine360_amd/context.py).
-extern "C" __attribute__((visibility("default"))) int im360_cfg_ddim_step_windows(const void* pred, const void* x, const void* noise, void* out,
-                                   const void* start, const void* weight, int nW, int64_t outer, int64_t F, int64_t L,
-                                   int64_t inner, float guidance, float sqrt_a, float sqrt_b, float sqrt_a_prev, float dir,
-                                   float sigma, int mode, int dtype, void* stream, const void* coef_dev) {
-    IM360_CHECK_CFG_DDIM_STEP_WINDOWS("cfg_ddim_step_windows");
-    return im360::launch_cfg_ddim_step_windows("cfg_ddim_step_windows", pred, x, noise, out, start, weight, nW, outer, F, L, 0, inner, guidance,
-                                               sqrt_a, sqrt_b, sqrt_a_prev, dir, sigma, mode, dtype, stream, coef_dev, nullptr, 0.0f);
-}
-
-// the same on r times the blend, r from the records im360_cfg_rescale_stats_windows left in ws for the same clip
-extern "C" __attribute__((visibility("default"))) int im360_cfg_ddim_step_windows_rescale(const void* pred, const void* x, const void* noise, void* out,
-                                   const void* start, const void* weight, int nW, int64_t outer, int64_t F, int64_t L,
-                                   int64_t inner, float guidance, float sqrt_a, float sqrt_b, float sqrt_a_prev, float dir,
-                                   float sigma, int mode, float phi, const void* ws, int64_t ws_floats, int dtype, void* stream,
-                                   const void* coef_dev) {
-    IM360_CHECK_CFG_DDIM_STEP_WINDOWS("cfg_ddim_step_windows_rescale");
-    IM360_CHECK_ARG(std::isfinite(phi), "cfg_ddim_step_windows_rescale: rescale=%g must be finite", (double)phi);
-    IM360_CHECK_RESCALE_WS("cfg_ddim_step_windows_rescale", outer * F * inner);
-    return im360::launch_cfg_ddim_step_windows("cfg_ddim_step_windows_rescale", pred, x, noise, out, start, weight, nW, outer, F, L, 0, inner,
-                                               guidance, sqrt_a, sqrt_b, sqrt_a_prev, dir, sigma, mode, dtype, stream, coef_dev, ws, phi);
-}
-
-// im360_cfg_ddim_step_windows with the windows on a ring of F frames: window k covers the frames (start[k] + j) mod F, j = 0 .. L - 1,
-// position j of its prediction.  Same blend, same slot order, same step.  The host cannot see the tables: the caller guarantees
-// 0 <= start[k] < F, every frame covered, L <= F (imagine360_amd/context.py, loop=True).
-extern "C" __attribute__((visibility("default"))) int im360_cfg_ddim_step_windows_ring(const void* pred, const void* x, const void* noise, void* out,
-                                   const void* start, const void* weight, int nW, int64_t outer, int64_t F, int64_t L,
-                                   int64_t inner, float guidance, float sqrt_a, float sqrt_b, float sqrt_a_prev, float dir,
-                                   float sigma, int mode, int dtype, void* stream, const void* coef_dev) {
-    IM360_CHECK_CFG_DDIM_STEP_WINDOWS("cfg_ddim_step_windows_ring");
-    return im360::launch_cfg_ddim_step_windows("cfg_ddim_step_windows_ring", pred, x, noise, out, start, weight, nW, outer, F, L, (int)F, inner,
-                                               guidance, sqrt_a, sqrt_b, sqrt_a_prev, dir, sigma, mode, dtype, stream, coef_dev, nullptr, 0.0f);
-}
-
-// the same on r times the blend, r from the records im360_cfg_rescale_stats_windows_ring left in ws for the same clip; the
-// precondition of im360_cfg_ddim_step_windows_ring: 0 <= start[k] < F, every frame covered, L <= F
-extern "C" __attribute__((visibility("default"))) int im360_cfg_ddim_step_windows_ring_rescale(const void* pred, const void* x, const void* noise,
-                                   void* out, const void* start, const void* weight, int nW, int64_t outer, int64_t F, int64_t L,
-                                   int64_t inner, float guidance, float sqrt_a, float sqrt_b, float sqrt_a_prev, float dir,
-                                   float sigma, int mode, float phi, const void* ws, int64_t ws_floats, int dtype, void* stream,
-                                   const void* coef_dev) {
-    IM360_CHECK_CFG_DDIM_STEP_WINDOWS("cfg_ddim_step_windows_ring_rescale");
-    IM360_CHECK_ARG(std::isfinite(phi), "cfg_ddim_step_windows_ring_rescale: rescale=%g must be finite", (double)phi);
-    IM360_CHECK_RESCALE_WS("cfg_ddim_step_windows_ring_rescale", outer * F * inner);
-    return im360::launch_cfg_ddim_step_windows("cfg_ddim_step_windows_ring_rescale", pred, x, noise, out, start, weight, nW, outer, F, L, (int)F,
-                                               inner, guidance, sqrt_a, sqrt_b, sqrt_a_prev, dir, sigma, mode, dtype, stream, coef_dev, ws, phi);
+    return im360_launch_status();
 }

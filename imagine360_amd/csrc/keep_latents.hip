@@ -1,7 +1,7 @@
 // Regenerating part of a given clip (AnimationPipeline regenerate_mask): after every step of the loop both latents are blended, in
 // place, with the clean clip noised to the noise level the latents now have; one launch for both branches.
 //
-//      known[c, f, p]   = T(sa * x0[c, f, p] + sb * noise[f, c, p])                 the `noised` expression of noise_latents.hip, one rounding
+//      known[c, f, p]   = T(sa * x0[c, f, p] + sb * noise[f, c, p])                 `noised` of latent_plane.h, one rounding
 //      pano[c, f, p]    = blend(pano[c, f, p], known[c, f, p], mask[f, p])
 //      pers[m, c, f, q] = ok[m, q] ? blend(pers[m, c, f, q], known[c, f, idx[m, q]], mask[f, idx[m, q]]) : pers[m, c, f, q]
 //
@@ -13,49 +13,22 @@
 // the same coefficients the two latents are what noise_latents_kernel writes (where ok), bit for bit: one expression, one rounding.
 //
 // One workgroup per (c, f) plane, as in noise_latents.hip.  `known` is never read back from pano: the plane pass forms it from x0
-// and noise and (LDS path, 2 * HW bytes <= kKeepLdsBytes) keeps the rounded plane in LDS, from which all M * Q perspective elements
+// and noise and (LDS path, 2 * HW bytes <= kPlaneLdsBytes) keeps the rounded plane in LDS, from which all M * Q perspective elements
 // are served after one barrier; larger planes (global path) form every gathered element again from x0 and noise at idx.  Every
 // element of pano and pers is read and written by one thread of one workgroup only, so the update in place has no hazard between
 // workgroups.  V = 8: 16-byte lanes in both passes (HW % 8 == 0, Q % 8 == 0, every pointer aligned for its widest access; a group of
-// eight that changes nothing is not stored); V = 1: scalar.  idx is clamped into [0, HW) as an unsigned value.
+// eight that changes nothing is not stored); V = 1: scalar.  idx is clamped into [0, HW) (plane_index).
 // coef (device float[2], may be null): sa, sb read by the kernel instead of the arguments (graph replay).
-#include "common.h"
-#include "fma_f32.h"
+#include "latent_plane.h"
 
 namespace im360 {
-
-constexpr int kKeepLdsBytes = 64 * 1024;         // the plane of a 128 x 256 latent; what a workgroup gets without asking for more
-
-// (the same expression as `noised` of noise_latents.hip: the cross-kernel contract is bit for bit)
-__device__ __forceinline__ float keep_noised(float x, float n, float sa, float sb) { return fma_f32(sa, x, sb * n); }
-
-template <typename T> __device__ __forceinline__ uint16_t keep_bits16(float v) {
-    const T t = from_f32<T>(v);
-    return __builtin_bit_cast(uint16_t, t);
-}
-template <typename T> __device__ __forceinline__ float keep_f32(uint16_t b) { return to_f32(__builtin_bit_cast(T, b)); }
 
 // bits of blend(x, k, w); x and k as 16-bit patterns of T
 template <typename T> __device__ __forceinline__ uint16_t keep_blend(uint16_t x, uint16_t k, float w) {
     if (w >= 1.0f) return x;
     if (w <= 0.0f) return k;
-    const float kf = keep_f32<T>(k);
-    return keep_bits16<T>(fma_f32(w, keep_f32<T>(x) - kf, kf));
-}
-
-__device__ __forceinline__ uint4 keep_pack(const uint16_t* g) {
-    uint4 v;
-    v.x = (uint32_t)g[0] | ((uint32_t)g[1] << 16);
-    v.y = (uint32_t)g[2] | ((uint32_t)g[3] << 16);
-    v.z = (uint32_t)g[4] | ((uint32_t)g[5] << 16);
-    v.w = (uint32_t)g[6] | ((uint32_t)g[7] << 16);
-    return v;
-}
-__device__ __forceinline__ void keep_unpack(uint4 v, uint16_t* g) {
-    g[0] = (uint16_t)v.x; g[1] = (uint16_t)(v.x >> 16);
-    g[2] = (uint16_t)v.y; g[3] = (uint16_t)(v.y >> 16);
-    g[4] = (uint16_t)v.z; g[5] = (uint16_t)(v.z >> 16);
-    g[6] = (uint16_t)v.w; g[7] = (uint16_t)(v.w >> 16);
+    const float kf = bits16_f32<T>(k);
+    return bits16<T>(fma_f32(w, bits16_f32<T>(x) - kf, kf));
 }
 
 template <typename T, int V, bool LDS>
@@ -86,7 +59,7 @@ __global__ __launch_bounds__(256) void keep_latents_kernel(T* __restrict__ pano,
             const float n[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
             const float w[8] = {wa.x, wa.y, wa.z, wa.w, wb.x, wb.y, wb.z, wb.w};
 #pragma unroll
-            for (int e = 0; e < 8; ++e) x[e] = keep_noised(x[e], n[e], sa, sb);
+            for (int e = 0; e < 8; ++e) x[e] = noised(x[e], n[e], sa, sb);
             const uint4 kv = pack8<T>(x);
             if constexpr (LDS) ((uint4*)plane)[i] = kv;
             bool all_new = true;
@@ -94,16 +67,16 @@ __global__ __launch_bounds__(256) void keep_latents_kernel(T* __restrict__ pano,
             for (int e = 0; e < 8; ++e) all_new = all_new && w[e] >= 1.0f;
             if (!all_new) {
                 uint16_t k[8], cur[8];
-                keep_unpack(kv, k);
-                keep_unpack(((const uint4*)pp)[i], cur);
+                bits16_unpack(kv, k);
+                bits16_unpack(((const uint4*)pp)[i], cur);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) cur[e] = keep_blend<T>(cur[e], k[e], w[e]);
-                ((uint4*)pp)[i] = keep_pack(cur);
+                ((uint4*)pp)[i] = bits16_pack(cur);
             }
         }
     } else {
         for (int i = threadIdx.x; i < HW; i += 256) {
-            const uint16_t k = keep_bits16<T>(keep_noised(to_f32(xp[i]), np[i], sa, sb));
+            const uint16_t k = bits16<T>(noised(to_f32(xp[i]), np[i], sa, sb));
             if constexpr (LDS) plane[i] = k;
             const float w = mp[i];
             if (!(w >= 1.0f)) pp[i] = keep_blend<T>(pp[i], k, w);
@@ -115,12 +88,12 @@ __global__ __launch_bounds__(256) void keep_latents_kernel(T* __restrict__ pano,
     // view sees the panorama, unchanged elsewhere
     auto element = [&](uint16_t cur, int id, uint8_t valid) -> uint16_t {
         if (!valid) return cur;
-        const unsigned p = min((unsigned)id, (unsigned)(HW - 1));
+        const unsigned p = plane_index(id, HW);
         const float w = mp[p];
         if (w >= 1.0f) return cur;
         uint16_t k;
         if constexpr (LDS) k = plane[p];
-        else k = keep_bits16<T>(keep_noised(to_f32(xp[p]), np[p], sa, sb));
+        else k = bits16<T>(noised(to_f32(xp[p]), np[p], sa, sb));
         return keep_blend<T>(cur, k, w);
     };
     const long CF = (long)C * F;
@@ -135,14 +108,14 @@ __global__ __launch_bounds__(256) void keep_latents_kernel(T* __restrict__ pano,
             const int id[8] = {ia.x, ia.y, ia.z, ia.w, ib.x, ib.y, ib.z, ib.w};
             uint4* dst = (uint4*)(vp + ((long)m * CF + blockIdx.x) * Q + q);
             uint16_t cur[8], nxt[8];
-            keep_unpack(*dst, cur);
+            bits16_unpack(*dst, cur);
             bool changed = false;
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                nxt[e] = element(cur[e], id[e], (uint8_t)(((e < 4 ? k2.x : k2.y) >> (8 * (e & 3))) & 0xffu));
+                nxt[e] = element(cur[e], id[e], ok_byte(k2, e));
                 changed = changed || nxt[e] != cur[e];
             }
-            if (changed) *dst = keep_pack(nxt);
+            if (changed) *dst = bits16_pack(nxt);
         }
     } else {
         for (int j = threadIdx.x; j < MQ; j += 256) {
@@ -165,31 +138,20 @@ extern "C" __attribute__((visibility("default"))) int im360_keep_latents(void* p
                                   float sqrt_a, float sqrt_b, int dtype, void* stream, const void* coef_dev) {
     using namespace im360;
     IM360_CHECK_ARG(pano && pers && x0 && noise && mask && idx && ok, "keep_latents: null pointer");
-    IM360_CHECK_ARG(F > 0 && C > 0 && HW > 0 && M > 0 && Q > 0, "keep_latents: F=%ld C=%ld HW=%ld M=%ld Q=%ld must be positive", (long)F,
-                    (long)C, (long)HW, (long)M, (long)Q);
-    // int32 inside the kernel: a plane index (idx is int32), a gather index j < M Q, the grid C F; element offsets are 64-bit
-    const int64_t lim = (int64_t)1 << 31;
-    IM360_CHECK_ARG(F < lim && C < lim && M < lim && Q < lim && HW < lim && C * F < lim && M * Q < lim,
-                    "keep_latents: HW=%ld, C*F=%ld*%ld or M*Q=%ld*%ld reaches 2^31", (long)HW, (long)C, (long)F, (long)M, (long)Q);
+    PlaneLaunch pl;
+    if (const int rc = plane_launch("keep_latents", F, C, HW, M, Q, {x0, noise, mask, idx, pano, pers}, ok, &pl)) return rc;
     IM360_CHECK_ARG(((uintptr_t)noise % 4) == 0 && ((uintptr_t)mask % 4) == 0 && ((uintptr_t)idx % 4) == 0 && ((uintptr_t)coef_dev % 4) == 0,
                     "keep_latents: misaligned noise, mask, idx or coef_dev (4 bytes)");
     IM360_CHECK_ARG(((uintptr_t)x0 % 2) == 0 && ((uintptr_t)pano % 2) == 0 && ((uintptr_t)pers % 2) == 0,
                     "keep_latents: misaligned 16-bit tensor");
     IM360_CHECK_ARG(x0 != pano, "keep_latents: x0 aliases pano (the clean clip would be overwritten)");
-    const bool vec = (HW % 8) == 0 && (Q % 8) == 0 && ((uintptr_t)x0 % 16) == 0 && ((uintptr_t)noise % 16) == 0 &&
-                     ((uintptr_t)mask % 16) == 0 && ((uintptr_t)idx % 16) == 0 && ((uintptr_t)ok % 8) == 0 &&
-                     ((uintptr_t)pano % 16) == 0 && ((uintptr_t)pers % 16) == 0;
-    const bool lds = 2 * HW <= kKeepLdsBytes;
-    const size_t smem = lds ? (size_t)((2 * HW + 15) / 16 * 16) : 0;
-    hipStream_t s = (hipStream_t)stream;
     return with_dtype(dtype, "keep_latents", [&](auto t) {
         using T = typename decltype(t)::type;
-        with_const<1, 8>(vec ? 8 : 1, [&](auto v) { with_bool(lds, [&](auto l) {
-            hipLaunchKernelGGL((keep_latents_kernel<T, decltype(v)::value, decltype(l)::value>), dim3((unsigned)(C * F)), dim3(256), smem, s,
+        with_const<1, 8>(pl.vec ? 8 : 1, [&](auto v) { with_bool(pl.lds, [&](auto l) {
+            hipLaunchKernelGGL((keep_latents_kernel<T, decltype(v)::value, decltype(l)::value>), dim3((unsigned)(C * F)), dim3(256), pl.smem, (hipStream_t)stream,
                                (T*)pano, (T*)pers, (const T*)x0, noise, mask, (const int*)idx, ok, (int)F, (int)C, (int)HW, (int)M, (int)Q,
                                sqrt_a, sqrt_b, (const float*)coef_dev);
         }); });
-        IM360_CHECK_LAUNCH();
-        return IM360_OK;
+        return im360_launch_status();
     });
 }

@@ -10,28 +10,15 @@
 // the fp32 sum so that both branches begin from the same numbers, exactly as init_noise derives the perspective noise from the
 // panorama noise; a pixel seen by two views, or by a view and the panorama, has one value.
 //
-// One workgroup per (c, f) plane.  LDS path (2 * HW bytes <= kNoiseLdsBytes): the plane is formed once, written to out_pano and kept
+// One workgroup per (c, f) plane.  LDS path (2 * HW bytes <= kPlaneLdsBytes): the plane is formed once, written to out_pano and kept
 // in LDS as 16-bit values; after one barrier all M * Q gathers of the plane are served from LDS.  Global path (larger planes): the
 // plane is formed and stored, then every gathered element is formed again from x0 and noise at idx -- the same `noised` expression on
 // the same inputs, hence the same bits as out_pano -- so no workgroup reads what another one (or it itself) has just written.
 // V = 8: 16-byte lanes in both phases (HW % 8 == 0, Q % 8 == 0, every pointer aligned for its widest access); V = 1: scalar.
-// idx is clamped into [0, HW) as an unsigned value: a table that breaks the precondition gives a wrong element, never a read
-// outside the plane.
-#include "common.h"
-#include "fma_f32.h"
+// idx is clamped into [0, HW) (plane_index).  `noised`, the 16-bit patterns and the contract with keep_latents.hip: latent_plane.h.
+#include "latent_plane.h"
 
 namespace im360 {
-
-constexpr int kNoiseLdsBytes = 64 * 1024;        // the plane of a 128 x 256 latent; what a workgroup gets without asking for more
-
-// explicit fma: the two places that form an element (plane pass, global-path gather) must round alike whatever hipcc contracts or
-// folds into the conversion that follows (fma_f32.h)
-__device__ __forceinline__ float noised(float x, float n, float sa, float sb) { return fma_f32(sa, x, sb * n); }
-
-template <typename T> __device__ __forceinline__ uint16_t bits16(float v) {
-    const T t = from_f32<T>(v);
-    return __builtin_bit_cast(uint16_t, t);
-}
 
 template <typename T, int V, bool LDS>
 __global__ __launch_bounds__(256) void noise_latents_kernel(const T* __restrict__ x0, const float* __restrict__ noise,
@@ -71,7 +58,7 @@ __global__ __launch_bounds__(256) void noise_latents_kernel(const T* __restrict_
 
     // ---- the M * Q gathers of the plane; one element: rounded plane value at the clamped index, or 0 where the view sees nothing
     auto gather = [&](int id, uint8_t valid) -> uint16_t {
-        const unsigned p = min((unsigned)id, (unsigned)(HW - 1));
+        const unsigned p = plane_index(id, HW);
         uint16_t v;
         if constexpr (LDS) v = plane[p];
         else v = bits16<T>(noised(to_f32(xp[p]), np[p], sa, sb));
@@ -87,12 +74,10 @@ __global__ __launch_bounds__(256) void noise_latents_kernel(const T* __restrict_
             const int id[8] = {ia.x, ia.y, ia.z, ia.w, ib.x, ib.y, ib.z, ib.w};
             uint16_t g[8];
 #pragma unroll
-            for (int e = 0; e < 8; ++e) g[e] = gather(id[e], (uint8_t)(((e < 4 ? k2.x : k2.y) >> (8 * (e & 3))) & 0xffu));
-            uint4 v;
-            v.x = (uint32_t)g[0] | ((uint32_t)g[1] << 16);
-            v.y = (uint32_t)g[2] | ((uint32_t)g[3] << 16);
-            v.z = (uint32_t)g[4] | ((uint32_t)g[5] << 16);
-            v.w = (uint32_t)g[6] | ((uint32_t)g[7] << 16);
+            for (int e = 0; e < 8; ++e) g[e] = gather(id[e], ok_byte(k2, e));
+            // bits16_pack(g), kept written out: behind the call hipcc packs with shift + or instead of v_perm_b32 and moves the gather's v_cvt
+            const uint4 v = {(uint32_t)g[0] | ((uint32_t)g[1] << 16), (uint32_t)g[2] | ((uint32_t)g[3] << 16),
+                             (uint32_t)g[4] | ((uint32_t)g[5] << 16), (uint32_t)g[6] | ((uint32_t)g[7] << 16)};
             *(uint4*)(out_pers + ((long)m * CF + blockIdx.x) * Q + q) = v;
         }
     } else {
@@ -112,29 +97,18 @@ extern "C" __attribute__((visibility("default"))) int im360_noise_latents(const 
                                    float sqrt_a, float sqrt_b, int dtype, void* stream) {
     using namespace im360;
     IM360_CHECK_ARG(x0 && noise && idx && ok && out_pano && out_pers, "noise_latents: null pointer");
-    IM360_CHECK_ARG(F > 0 && C > 0 && HW > 0 && M > 0 && Q > 0, "noise_latents: F=%ld C=%ld HW=%ld M=%ld Q=%ld must be positive", (long)F,
-                    (long)C, (long)HW, (long)M, (long)Q);
-    // int32 inside the kernel: a plane index (idx is int32), a gather index j < M Q, the grid C F; element offsets are 64-bit
-    const int64_t lim = (int64_t)1 << 31;
-    IM360_CHECK_ARG(F < lim && C < lim && M < lim && Q < lim && HW < lim && C * F < lim && M * Q < lim,
-                    "noise_latents: HW=%ld, C*F=%ld*%ld or M*Q=%ld*%ld reaches 2^31", (long)HW, (long)C, (long)F, (long)M, (long)Q);
+    PlaneLaunch pl;
+    if (const int rc = plane_launch("noise_latents", F, C, HW, M, Q, {x0, noise, idx, out_pano, out_pers}, ok, &pl)) return rc;
     IM360_CHECK_ARG(((uintptr_t)noise % 4) == 0 && ((uintptr_t)idx % 4) == 0, "noise_latents: misaligned noise or idx (4 bytes)");
     IM360_CHECK_ARG(((uintptr_t)x0 % 2) == 0 && ((uintptr_t)out_pano % 2) == 0 && ((uintptr_t)out_pers % 2) == 0,
                     "noise_latents: misaligned 16-bit tensor");
-    const bool vec = (HW % 8) == 0 && (Q % 8) == 0 && ((uintptr_t)x0 % 16) == 0 && ((uintptr_t)noise % 16) == 0 &&
-                     ((uintptr_t)idx % 16) == 0 && ((uintptr_t)ok % 8) == 0 && ((uintptr_t)out_pano % 16) == 0 &&
-                     ((uintptr_t)out_pers % 16) == 0;
-    const bool lds = 2 * HW <= kNoiseLdsBytes;
-    const size_t smem = lds ? (size_t)((2 * HW + 15) / 16 * 16) : 0;
-    hipStream_t s = (hipStream_t)stream;
     return with_dtype(dtype, "noise_latents", [&](auto t) {
         using T = typename decltype(t)::type;
-        with_const<1, 8>(vec ? 8 : 1, [&](auto v) { with_bool(lds, [&](auto l) {
-            hipLaunchKernelGGL((noise_latents_kernel<T, decltype(v)::value, decltype(l)::value>), dim3((unsigned)(C * F)), dim3(256), smem, s,
+        with_const<1, 8>(pl.vec ? 8 : 1, [&](auto v) { with_bool(pl.lds, [&](auto l) {
+            hipLaunchKernelGGL((noise_latents_kernel<T, decltype(v)::value, decltype(l)::value>), dim3((unsigned)(C * F)), dim3(256), pl.smem, (hipStream_t)stream,
                                (const T*)x0, noise, (const int*)idx, ok, (T*)out_pano, (T*)out_pers, (int)F, (int)C, (int)HW, (int)M, (int)Q,
                                sqrt_a, sqrt_b);
         }); });
-        IM360_CHECK_LAUNCH();
-        return IM360_OK;
+        return im360_launch_status();
     });
 }

@@ -1,0 +1,611 @@
+// The sampler-step family on 16-bit latents, gfx950: classifier-free guidance fused with the scheduler update in one elementwise pass
+// (cfg_ddim_kernel, cfg_ddim_step_kernel), the same step on the blend of temporal context windows on a line or a ring
+// (cfg_ddim_step_windows_kernel), and the statistics pass of the guidance rescale (cfg_rescale_*).
+// Replaces: the guidance combine + scheduler.step of the denoising loop (pipeline_animation_inference_dual.py:791-800) with
+// DDIMScheduler.step (diffusers/schedulers/scheduling_ddim.py:251-373; eta = 0, v-prediction: 300-350).  Context windows and the
+// guidance rescale have no call site in the reference pipeline: they compose that same step (see their comments).
+// Device code first; then the host side: two aggregates with their checks, the launchers, the entry points (fill, check, launch).
+#include <cmath>
+#include <initializer_list>
+
+#include "common.h"
+
+namespace im360 {
+
+// ---- CFG combine + DDIM v-prediction update (eta = 0), one elementwise pass
+//      (pipeline_animation_inference_dual.py:791-800; diffusers/schedulers/scheduling_ddim.py:300-350):
+//      v = u + g (c - u);  x_prev = cx * x + cv * v   with cx, cv precomputed on the host in fp64
+template <typename T>
+__global__ void cfg_ddim_kernel(const T* __restrict__ uncond, const T* __restrict__ cond, const T* __restrict__ x,
+                                T* __restrict__ out, long n8, float g, float cx, float cv, const float* __restrict__ coef) {
+    if (coef != nullptr) {          // (guidance, cx, cv) read on the device: the launch can be replayed from a hipGraph
+        g = coef[0];
+        cx = coef[1];
+        cv = coef[2];
+    }
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
+        float u[8], c[8], s[8];
+        unpack8<T>(((const uint4*)uncond)[i], u);
+        unpack8<T>(((const uint4*)cond)[i], c);
+        unpack8<T>(((const uint4*)x)[i], s);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) s[e] = cx * s[e] + cv * (u[e] + g * (c[e] - u[e]));
+        ((uint4*)out)[i] = pack8<T>(s);
+    }
+}
+
+// ---- CFG combine + the full DDIMScheduler.step (diffusers/schedulers/scheduling_ddim.py:251-373), one elementwise pass:
+//      m = u + g (c - u);  x0 / e from the prediction type (mode bits 0-1: 0 epsilon, 1 v, 2 sample);  x0 clamped to [-1, 1]
+//      (bit 2);  e re-derived from the clamped x0 (bit 3);  out = sa_prev x0 + dir e + sigma z.  sa, sb = sqrt(a_t), sqrt(1 - a_t);
+//      dir = sqrt(1 - a_prev - sigma^2), sigma = eta sqrt(var) come from fp64 host math.  noise == nullptr: z = 0.
+// The step arithmetic of one element, shared by cfg_ddim_step_kernel and cfg_ddim_step_windows_kernel: m is the guided model output,
+// s the sample, z the variance noise (0 without one); isa = 1 / sa, isb = 1 / sb.
+struct DdimCoefs {
+    float g, sa, sb, sap, dir, sigma, isa, isb;
+    int pred;
+    bool clip, clipped_out;
+};
+
+__device__ __forceinline__ DdimCoefs ddim_coefs(float g, float sa, float sb, float sap, float dir, float sigma, int mode,
+                                                const float* __restrict__ coef) {
+    if (coef != nullptr) {          // (guidance, sa, sb, sa_prev, dir, sigma) read on the device: hipGraph replay
+        g = coef[0];
+        sa = coef[1];
+        sb = coef[2];
+        sap = coef[3];
+        dir = coef[4];
+        sigma = coef[5];
+    }
+    DdimCoefs k;
+    k.g = g, k.sa = sa, k.sb = sb, k.sap = sap, k.dir = dir, k.sigma = sigma;
+    k.isa = 1.0f / sa, k.isb = 1.0f / sb;
+    k.pred = mode & 3;
+    k.clip = (mode & 4) != 0, k.clipped_out = (mode & 8) != 0;
+    return k;
+}
+
+__device__ __forceinline__ float cfg_combine(float u, float c, float g) { return u + g * (c - u); }
+
+__device__ __forceinline__ float ddim_step_elem(float m, float s, float z, const DdimCoefs& k) {
+    float x0, eps;
+    if (k.pred == 0) {
+        x0 = (s - k.sb * m) * k.isa;
+        eps = m;
+    } else if (k.pred == 1) {
+        x0 = k.sa * s - k.sb * m;
+        eps = k.sa * m + k.sb * s;
+    } else {
+        x0 = m;
+        eps = m;                     // the reference's direction term multiplies the model output, i.e. x0 itself
+    }
+    if (k.clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    if (k.clipped_out) eps = (s - k.sa * x0) * k.isb;
+    return k.sap * x0 + k.dir * eps + k.sigma * z;
+}
+
+// ---- guidance rescale (arXiv 2305.08891, section 3.4): m' = r m with r = phi std(c) / std(m) + (1 - phi), the standard deviations
+//      (correction 1) over the whole tensor.  Two launches: a statistics pass writes one record of partial moments per workgroup,
+//      and every workgroup of the step kernel merges ALL records itself, in one fixed order, so that all of them multiply by the
+//      same bits -- no atomics, no counter, no workgroup waits for another one, nothing read back by the host.
+//      Moments are carried as (count, mean, M2 = sum (x - mean)^2) and merged with Chan's formula, never as sum x, sum x^2: the
+//      variance of a prediction whose mean is far from zero would cancel in fp32.  c and m share the count.  Counts are fp32
+//      (exact below 2^24 elements, 6e-8 relative above).
+struct CfgMoments {
+    float n, mc, qc, mm, qm;         // count;  mean, M2 of the text prediction c;  mean, M2 of the guided prediction m
+};
+
+constexpr int kRescaleMaxRecords = 256;      // grid cap of the statistics pass (about one workgroup per CU) = threads of a consumer
+constexpr int kRescaleRecord = 8;            // floats per record (five used)
+
+// a <- a (+) b, Chan et al.; an empty side leaves the other one untouched
+__device__ __forceinline__ void moments_merge(CfgMoments& a, const CfgMoments& b) {
+    if (b.n == 0.0f) return;
+    if (a.n == 0.0f) {
+        a = b;
+        return;
+    }
+    const float n = a.n + b.n, f = b.n / n, w = a.n * f;
+    const float dc = b.mc - a.mc, dm = b.mm - a.mm;
+    a.mc = __fmaf_rn(dc, f, a.mc);
+    a.qc = __fmaf_rn(dc * dc, w, a.qc + b.qc);
+    a.mm = __fmaf_rn(dm, f, a.mm);
+    a.qm = __fmaf_rn(dm * dm, w, a.qm + b.qm);
+    a.n = n;
+}
+
+// a <- a (+) the cnt (1 .. 8) leading values of c[] / m[]: their own mean first, then the squared distances to it
+__device__ __forceinline__ void moments_add(CfgMoments& a, const float* c, const float* m, int cnt) {
+    float sc = 0.0f, sm = 0.0f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        if (e < cnt) {
+            sc += c[e];
+            sm += m[e];
+        }
+    }
+    CfgMoments b;
+    b.n = (float)cnt;
+    b.mc = sc / b.n, b.mm = sm / b.n;
+    b.qc = 0.0f, b.qm = 0.0f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        if (e < cnt) {
+            const float dc = c[e] - b.mc, dm = m[e] - b.mm;
+            b.qc = __fmaf_rn(dc, dc, b.qc);
+            b.qm = __fmaf_rn(dm, dm, b.qm);
+        }
+    }
+    moments_merge(a, b);
+}
+
+// The moments of a workgroup of exactly 256 threads (four waves; every kernel that calls this is launched so and carries
+// __launch_bounds__(256)), valid in thread 0: lane l takes lane l + 1, + 2, ... + 32 of its wave (lane 0 ends with
+// lanes 0 .. 63 in ascending order), then thread 0 takes the four waves in ascending order.  `lds`: 4 records.
+__device__ __forceinline__ CfgMoments moments_block_reduce(CfgMoments a, CfgMoments* lds) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        CfgMoments b;
+        b.n = __shfl_down(a.n, o), b.mc = __shfl_down(a.mc, o), b.qc = __shfl_down(a.qc, o);
+        b.mm = __shfl_down(a.mm, o), b.qm = __shfl_down(a.qm, o);
+        moments_merge(a, b);          // (lanes past 63 - o read their own value: never part of what lane 0 collects)
+    }
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = a;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        a = lds[0];
+        for (int w = 1; w < (int)(blockDim.x >> 6); ++w) moments_merge(a, lds[w]);
+    }
+    return a;
+}
+
+__device__ __forceinline__ void moments_store(float* __restrict__ ws, const CfgMoments& a) {
+    float* rec = ws + (long)blockIdx.x * kRescaleRecord;
+    rec[0] = a.n, rec[1] = a.mc, rec[2] = a.qc, rec[3] = a.mm, rec[4] = a.qm;
+}
+
+// r from the nrec records of a statistics pass, the same bits in every thread of every workgroup that calls it.  One record per
+// thread: nrec <= kRescaleMaxRecords = 256 = blockDim.x (im360_cfg_rescale_records caps the statistics grid there).
+__device__ __forceinline__ float rescale_factor(const float* ws, int nrec, float phi) {
+    __shared__ CfgMoments lds[4];
+    __shared__ float r_lds;
+    CfgMoments a;
+    a.n = a.mc = a.qc = a.mm = a.qm = 0.0f;
+    if ((int)threadIdx.x < nrec) {
+        const float* rec = ws + (long)threadIdx.x * kRescaleRecord;
+        a.n = rec[0], a.mc = rec[1], a.qc = rec[2], a.mm = rec[3], a.qm = rec[4];
+    }
+    a = moments_block_reduce(a, lds);
+    if (threadIdx.x == 0) {
+        const float std_c = sqrtf(a.qc / (a.n - 1.0f)), std_m = sqrtf(a.qm / (a.n - 1.0f));
+        r_lds = phi * std_c / std_m + (1.0f - phi);          // std_m = 0 or n = 1: inf / NaN, as the formula gives
+    }
+    __syncthreads();
+    return r_lds;
+}
+
+// statistics pass over (u, c): n8 16-byte lanes, grid <= kRescaleMaxRecords, one record per workgroup
+template <typename T>
+__global__ __launch_bounds__(256) void cfg_rescale_stats_kernel(const T* __restrict__ uncond, const T* __restrict__ cond, long n8,
+                                                                 float g, const float* __restrict__ coef, float* __restrict__ ws) {
+    __shared__ CfgMoments lds[4];
+    if (coef != nullptr) g = coef[0];
+    CfgMoments a;
+    a.n = a.mc = a.qc = a.mm = a.qm = 0.0f;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
+        float u[8], c[8], m[8];
+        unpack8<T>(((const uint4*)uncond)[i], u);
+        unpack8<T>(((const uint4*)cond)[i], c);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) m[e] = cfg_combine(u[e], c[e], g);
+        moments_add(a, c, m, 8);
+    }
+    a = moments_block_reduce(a, lds);
+    if (threadIdx.x == 0) moments_store(ws, a);
+}
+
+// r alone, for tests and tools: one workgroup, the reduction every step workgroup makes
+__global__ __launch_bounds__(256) void cfg_rescale_factor_kernel(const float* __restrict__ ws, int nrec, float phi, float* __restrict__ out) {
+    const float r = rescale_factor(ws, nrec, phi);
+    if (threadIdx.x == 0) out[0] = r;
+}
+
+// r * m as ONE fp32 multiplication of exactly these two values.  This file is built with -ffast-math: without the two value barriers
+// hipcc folds r into the step's coefficients in one kernel and into the blend's division in another, and the windows kernel would
+// no longer give the plain kernel's bits for one uniform window.
+__device__ __forceinline__ float rescale_mul(float r, float m) {
+    asm volatile("" : "+v"(m));
+    float p = r * m;
+    asm volatile("" : "+v"(p));
+    return p;
+}
+
+// RS: the guided prediction is multiplied by rescale_factor(ws, nrec, phi) before the step; those instantiations need workgroups of
+// 256 threads and say so in their launch bounds (1024 is the default, i.e. what the kernel without the factor always had)
+template <typename T, bool RS>
+__global__ __launch_bounds__(RS ? 256 : 1024) void cfg_ddim_step_kernel(const T* __restrict__ uncond, const T* __restrict__ cond, const T* __restrict__ x,
+                                     const T* __restrict__ noise, T* __restrict__ out, long n8, float g, float sa, float sb,
+                                     float sap, float dir, float sigma, int mode, const float* __restrict__ coef,
+                                     const float* __restrict__ ws, int nrec, float phi) {
+    const DdimCoefs k = ddim_coefs(g, sa, sb, sap, dir, sigma, mode, coef);
+    float r = 1.0f;
+    if (RS) r = rescale_factor(ws, nrec, phi);
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
+        float u[8], c[8], s[8], z[8];
+        unpack8<T>(((const uint4*)uncond)[i], u);
+        unpack8<T>(((const uint4*)cond)[i], c);
+        unpack8<T>(((const uint4*)x)[i], s);
+        if (noise != nullptr) unpack8<T>(((const uint4*)noise)[i], z);
+        else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) z[e] = 0.0f;
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float m = cfg_combine(u[e], c[e], k.g);
+            s[e] = ddim_step_elem(RS ? rescale_mul(r, m) : m, s[e], z[e], k);
+        }
+        ((uint4*)out)[i] = pack8<T>(s);
+    }
+}
+
+// ---- the same step on the per-frame blend of sliding temporal context windows.  x / noise / out are [outer, F, inner]; the
+//      predictions of all windows sit in one buffer pred[nW, 2, outer, L, inner] (window, CFG half, the model's own layout);
+//      start[nW] ascending window start frames, weight[L] the blend weight of each position inside a window.  Per element at frame f:
+//          m = (sum_k w[f - s_k] (u_k + g (c_k - u_k))) / (sum_k w[f - s_k])   over the windows with s_k <= f < s_k + L, k ascending
+//      (a fixed summation order: deterministic), then ddim_step_elem; one rounding, at the store.  V = 8: 16-byte lanes (inner % 8
+//      == 0, so a lane never straddles a frame); V = 1: the scalar path for any inner.  The first covering window initialises the
+//      sums, so one window with weight 1 gives m = 1 * m_0 / 1 = m_0 exactly: bit-identical to cfg_ddim_step_kernel.
+//      wrap = 0: the windows lie on a line (above).  wrap = F: they lie on a ring of F frames, window k covers the frames
+//      (s_k + j) mod F, j = 0 .. L - 1, and a frame in front of s_k is at position f - s_k + F.  One integer compare-and-add per
+//      window and lane; slot order and float arithmetic are those of the line.  j indexes pred / weight only when 0 <= j < L,
+//      whatever the table holds.
+// The blend of the V elements from element e0 on (V = 8: one 16-byte lane inside one frame): mb[] = the guided prediction m above;
+// cb[] (CB only) = the same blend of the text half c_k alone, what the guidance rescale takes std(c) of.
+template <typename T, int V, bool CB>
+__device__ __forceinline__ void windows_blend(const T* __restrict__ pred, const int* __restrict__ start, const float* __restrict__ weight,
+                                              int nW, int F, int L, int wrap, long inner, long half, long e0, float g, float* mb, float* cb) {
+    const long r = e0 % inner, of = e0 / inner;
+    const int f = (int)(of % F);
+    const long o = of / F;
+    float acc[V], cacc[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) acc[e] = cacc[e] = 0.0f;
+    float wsum = 0.0f;
+    bool first = true;
+    for (int w = 0; w < nW; ++w) {
+        int j = f - start[w];
+        if (j < 0) j += wrap;
+        if (j < 0 || j >= L) continue;
+        const float wt = weight[j];
+        const long at = (long)w * 2 * half + (o * L + j) * inner + r;
+        float u[V], c[V];
+        if (V == 8) {
+            unpack8<T>(*(const uint4*)(pred + at), u);
+            unpack8<T>(*(const uint4*)(pred + at + half), c);
+        } else {
+            u[0] = to_f32<T>(pred[at]);
+            c[0] = to_f32<T>(pred[at + half]);
+        }
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+            const float m = wt * cfg_combine(u[e], c[e], g);
+            acc[e] = first ? m : acc[e] + m;
+            if (CB) {
+                const float t = wt * c[e];
+                cacc[e] = first ? t : cacc[e] + t;
+            }
+        }
+        wsum = first ? wt : wsum + wt;
+        first = false;
+    }
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+        mb[e] = acc[e] / wsum;
+        if (CB) cb[e] = cacc[e] / wsum;
+    }
+}
+
+// statistics pass of the guidance rescale over the blends (windows_blend: the step kernel's own m, and c blended the same way), the
+// moments over the whole clip [outer, F, inner].  A thread takes the elements in the groups of 8 of cfg_rescale_stats_kernel for
+// either V (V = 1: eight scalar blends, the last group may be short), so one uniform window with L = F writes that kernel's records.
+template <typename T, int V>
+__global__ __launch_bounds__(256) void cfg_rescale_stats_windows_kernel(const T* __restrict__ pred, const int* __restrict__ start,
+                                                                         const float* __restrict__ weight, int nW, long outer, int F, int L,
+                                                                         int wrap, long inner, float g, const float* __restrict__ coef,
+                                                                         float* __restrict__ ws) {
+    __shared__ CfgMoments lds[4];
+    if (coef != nullptr) g = coef[0];
+    const long n = outer * F * inner, n8 = (n + 7) / 8;
+    const long half = outer * L * inner;
+    CfgMoments a;
+    a.n = a.mc = a.qc = a.mm = a.qm = 0.0f;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
+        float c[8], m[8];
+        int cnt = 8;
+        if (V == 8) windows_blend<T, 8, true>(pred, start, weight, nW, F, L, wrap, inner, half, i * 8, g, m, c);
+        else {
+            cnt = (int)(n - i * 8 < 8 ? n - i * 8 : 8);
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+                if (e < cnt) windows_blend<T, 1, true>(pred, start, weight, nW, F, L, wrap, inner, half, i * 8 + e, g, &m[e], &c[e]);
+        }
+        moments_add(a, c, m, cnt);
+    }
+    a = moments_block_reduce(a, lds);
+    if (threadIdx.x == 0) moments_store(ws, a);
+}
+
+template <typename T, int V, bool RS>
+__global__ __launch_bounds__(RS ? 256 : 1024) void cfg_ddim_step_windows_kernel(const T* __restrict__ pred, const T* __restrict__ x, const T* __restrict__ noise,
+                                             T* __restrict__ out, const int* __restrict__ start, const float* __restrict__ weight,
+                                             int nW, long outer, int F, int L, int wrap, long inner, float g, float sa, float sb, float sap,
+                                             float dir, float sigma, int mode, const float* __restrict__ coef,
+                                             const float* __restrict__ ws, int nrec, float phi) {
+    const DdimCoefs k = ddim_coefs(g, sa, sb, sap, dir, sigma, mode, coef);
+    float r = 1.0f;
+    if (RS) r = rescale_factor(ws, nrec, phi);
+    const long nv = outer * F * inner / V;
+    const long half = outer * L * inner;              // one CFG half of one window
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
+        float m[V], s[V], z[V];
+        windows_blend<T, V, false>(pred, start, weight, nW, F, L, wrap, inner, half, i * V, k.g, m, nullptr);
+        if (V == 8) {
+            unpack8<T>(((const uint4*)x)[i], s);
+            if (noise != nullptr) unpack8<T>(((const uint4*)noise)[i], z);
+        } else {
+            s[0] = to_f32<T>(x[i]);
+            if (noise != nullptr) z[0] = to_f32<T>(noise[i]);
+        }
+        if (noise == nullptr) {
+#pragma unroll
+            for (int e = 0; e < V; ++e) z[e] = 0.0f;
+        }
+#pragma unroll
+        for (int e = 0; e < V; ++e) s[e] = ddim_step_elem(RS ? rescale_mul(r, m[e]) : m[e], s[e], z[e], k);
+        if (V == 8) ((uint4*)out)[i] = pack8<T>(s);
+        else out[i] = from_f32<T>(s[0]);
+    }
+}
+
+}  // namespace im360
+
+// Records a statistics pass of the guidance rescale writes for n elements = its grid: one workgroup per 256 groups of 8 elements,
+// at most kRescaleMaxRecords (every consumer thread reads one record).
+extern "C" __attribute__((visibility("default"))) int64_t im360_cfg_rescale_records(int64_t n) {
+    const int64_t blocks = ((n + 7) / 8 + 255) / 256;
+    return blocks < 1 ? 1 : blocks > im360::kRescaleMaxRecords ? im360::kRescaleMaxRecords : blocks;
+}
+
+namespace im360 {
+// What a step entry point is given besides its tensors: the coefficients (the kernel reads coef_dev[0 .. 5] instead when that is given),
+// the mode bits, the variance noise (may be null) and, with the guidance rescale, the workspace of records and the strength phi.
+struct StepArgs {
+    float g, sa, sb, sap, dir, sigma;
+    int mode;
+    const void *noise, *coef_dev, *ws;
+    int64_t ws_floats;
+    float phi;
+};
+// The predictions of sliding context windows (layout, tables: cfg_ddim_step_windows_kernel); wrap = 0: on a line, wrap = F: on a ring.
+struct Windows {
+    const void *pred, *start, *weight;
+    int nW, wrap;
+    int64_t outer, F, L, inner;
+    int64_t elements() const { return outer * F * inner; }
+};
+// n elements in the tensors `must` (none null) and `may` (null allowed), read and written 16 bytes at a time
+static int check_tensors(const char* name, std::initializer_list<const void*> must, const void* may, int64_t n) {
+    bool all = true;
+    uintptr_t bits = (uintptr_t)may;
+    for (const void* p : must) all = all && p, bits |= (uintptr_t)p;
+    IM360_CHECK_ARG(all, "%s: null pointer", name);
+    IM360_CHECK_ARG(n > 0 && (n % 8) == 0, "%s: n=%ld must be a positive multiple of 8", name, (long)n);
+    IM360_CHECK_ARG((bits % 16) == 0, "%s: misaligned pointer", name);
+    return IM360_OK;
+}
+// the workspace of n elements: present, 4-byte aligned, large enough for the grid
+static int check_rescale_ws(const char* name, const void* ws, int64_t ws_floats, int64_t n) {
+    IM360_CHECK_ARG(ws && ((uintptr_t)ws % 4) == 0, "%s: null or misaligned workspace", name);
+    IM360_CHECK_ARG(ws_floats >= im360_cfg_rescale_records(n) * kRescaleRecord, "%s: workspace of %ld floats, %ld needed", name,
+                    (long)ws_floats, (long)(im360_cfg_rescale_records(n) * kRescaleRecord));
+    return IM360_OK;
+}
+// StepArgs: mode and noise, which every step entry point checks in the middle of its list ...
+static int check_step(const char* name, const StepArgs& s) {
+    IM360_CHECK_ARG(s.mode >= 0 && s.mode < 16 && (s.mode & 3) != 3, "%s: mode %d unsupported", name, s.mode);
+    IM360_CHECK_ARG(s.noise || s.coef_dev || s.sigma == 0.0f, "%s: sigma=%g needs a noise tensor", name, (double)s.sigma);
+    return IM360_OK;
+}
+// ... and phi and the workspace for n elements, which the _rescale entry points check at the end of theirs
+static int check_step_rescale(const char* name, const StepArgs& s, int64_t n) {
+    IM360_CHECK_ARG(std::isfinite(s.phi), "%s: rescale=%g must be finite", name, (double)s.phi);
+    return check_rescale_ws(name, s.ws, s.ws_floats, n);
+}
+// Windows; `others`: the entry point's other mandatory pointers are there; `step` (null for a statistics pass) is checked in between.
+static int check_windows(const char* name, const Windows& w, bool others, const StepArgs* step) {
+    IM360_CHECK_ARG(w.pred && others && w.start && w.weight, "%s: null pointer", name);
+    IM360_CHECK_ARG(w.nW > 0 && w.outer > 0 && w.inner > 0 && w.L > 0 && w.L <= w.F && w.F < (1 << 30),
+                    "%s: nW=%d outer=%ld F=%ld L=%ld inner=%ld out of range", name, w.nW, (long)w.outer, (long)w.F, (long)w.L, (long)w.inner);
+    if (const int rc = step ? check_step(name, *step) : IM360_OK) return rc;
+    IM360_CHECK_ARG(((uintptr_t)w.start % 4) == 0 && ((uintptr_t)w.weight % 4) == 0, "%s: misaligned table", name);
+    return IM360_OK;
+}
+static unsigned step_blocks(long lanes) { return (unsigned)((lanes + 255) / 256 > 4096 ? 4096 : (lanes + 255) / 256); }
+
+// im360_cfg_ddim_step and, with the guidance rescale, im360_cfg_ddim_step_rescale: checks, then the launch
+static int cfg_ddim_step(const char* name, const void* uncond, const void* cond, const void* x, void* out, int64_t n, const StepArgs& s,
+                         bool rescale, int dtype, void* stream) {
+    if (const int rc = check_tensors(name, {uncond, cond, x, out}, s.noise, n)) return rc;
+    if (const int rc = check_step(name, s)) return rc;
+    if (const int rc = rescale ? check_step_rescale(name, s, n) : IM360_OK) return rc;
+    const long n8 = n / 8;
+    const int nrec = rescale ? (int)im360_cfg_rescale_records(n) : 0;
+    return with_dtype(dtype, name, [&](auto t) {
+        using T = typename decltype(t)::type;
+        with_bool(rescale, [&](auto rs) {
+            hipLaunchKernelGGL((cfg_ddim_step_kernel<T, decltype(rs)::value>), dim3(step_blocks(n8)), dim3(256), 0, (hipStream_t)stream,
+                               (const T*)uncond, (const T*)cond, (const T*)x, (const T*)s.noise, (T*)out, n8, s.g, s.sa, s.sb, s.sap, s.dir,
+                               s.sigma, s.mode, (const float*)s.coef_dev, (const float*)s.ws, nrec, s.phi);
+        });
+        return im360_launch_status();
+    });
+}
+
+// the four windowed step entry points (w.wrap: line or ring; rescale: with or without the guidance rescale): checks, then the launch
+static int cfg_ddim_step_windows(const char* name, const Windows& w, const void* x, void* out, const StepArgs& s, bool rescale, int dtype,
+                                 void* stream) {
+    if (const int rc = check_windows(name, w, x && out, &s)) return rc;          // (mode and noise of `s` inside: the entry points' order)
+    if (const int rc = rescale ? check_step_rescale(name, s, w.elements()) : IM360_OK) return rc;
+    const bool vec = (w.inner % 8) == 0 && (((uintptr_t)w.pred | (uintptr_t)x | (uintptr_t)s.noise | (uintptr_t)out) % 16) == 0;
+    const long nv = (long)w.elements() / (vec ? 8 : 1);
+    const int nrec = rescale ? (int)im360_cfg_rescale_records(w.elements()) : 0;
+    return with_dtype(dtype, name, [&](auto t) {
+        using T = typename decltype(t)::type;
+        with_const<1, 8>(vec ? 8 : 1, [&](auto v) { with_bool(rescale, [&](auto rs) {
+            hipLaunchKernelGGL((cfg_ddim_step_windows_kernel<T, decltype(v)::value, decltype(rs)::value>), dim3(step_blocks(nv)), dim3(256), 0,
+                               (hipStream_t)stream, (const T*)w.pred, (const T*)x, (const T*)s.noise, (T*)out, (const int*)w.start,
+                               (const float*)w.weight, w.nW, (long)w.outer, (int)w.F, (int)w.L, w.wrap, (long)w.inner, s.g, s.sa, s.sb, s.sap,
+                               s.dir, s.sigma, s.mode, (const float*)s.coef_dev, (const float*)s.ws, nrec, s.phi);
+        }); });
+        return im360_launch_status();
+    });
+}
+
+// im360_cfg_rescale_stats_windows (w.wrap = 0) and im360_cfg_rescale_stats_windows_ring (w.wrap = F): checks, then the launch
+static int cfg_rescale_stats_windows(const char* name, const Windows& w, float guidance, void* ws, int64_t ws_floats, int dtype, void* stream,
+                                     const void* coef_dev) {
+    if (const int rc = check_windows(name, w, true, nullptr)) return rc;         // (no other pointer, no step arguments to check)
+    if (const int rc = check_rescale_ws(name, ws, ws_floats, w.elements())) return rc;
+    const bool vec = (w.inner % 8) == 0 && ((uintptr_t)w.pred % 16) == 0;
+    const unsigned blocks = (unsigned)im360_cfg_rescale_records(w.elements());
+    return with_dtype(dtype, name, [&](auto t) {
+        using T = typename decltype(t)::type;
+        with_const<1, 8>(vec ? 8 : 1, [&](auto v) {
+            hipLaunchKernelGGL((cfg_rescale_stats_windows_kernel<T, decltype(v)::value>), dim3(blocks), dim3(256), 0, (hipStream_t)stream,
+                               (const T*)w.pred, (const int*)w.start, (const float*)w.weight, w.nW, (long)w.outer, (int)w.F, (int)w.L, w.wrap,
+                               (long)w.inner, guidance, (const float*)coef_dev, (float*)ws);
+        });
+        return im360_launch_status();
+    });
+}
+}  // namespace im360
+
+// out = cx * x + cv * (uncond + g (cond - uncond)), n elements (n % 8 == 0), all same dtype
+extern "C" __attribute__((visibility("default"))) int im360_cfg_ddim_update(const void* uncond, const void* cond, const void* x, void* out, int64_t n,
+                                   float guidance, float cx, float cv, int dtype, void* stream, const void* coef_dev) {
+    using namespace im360;
+    if (const int rc = check_tensors("cfg_ddim_update", {uncond, cond, x, out}, nullptr, n)) return rc;
+    return with_dtype(dtype, "cfg_ddim_update", [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((cfg_ddim_kernel<T>), dim3(step_blocks(n / 8)), dim3(256), 0, (hipStream_t)stream, (const T*)uncond, (const T*)cond,
+                           (const T*)x, (T*)out, (long)(n / 8), guidance, cx, cv, (const float*)coef_dev);
+        return im360_launch_status();
+    });
+}
+
+// partial moments of cond and of uncond + g (cond - uncond) over n elements (n % 8 == 0) -> ws
+extern "C" __attribute__((visibility("default"))) int im360_cfg_rescale_stats(const void* uncond, const void* cond, int64_t n, float guidance,
+                                   void* ws, int64_t ws_floats, int dtype, void* stream, const void* coef_dev) {
+    using namespace im360;
+    if (const int rc = check_tensors("cfg_rescale_stats", {uncond, cond}, nullptr, n)) return rc;
+    if (const int rc = check_rescale_ws("cfg_rescale_stats", ws, ws_floats, n)) return rc;
+    const unsigned blocks = (unsigned)im360_cfg_rescale_records(n);
+    return with_dtype(dtype, "cfg_rescale_stats", [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((cfg_rescale_stats_kernel<T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const T*)uncond, (const T*)cond,
+                           (long)(n / 8), guidance, (const float*)coef_dev, (float*)ws);
+        return im360_launch_status();
+    });
+}
+
+// the same over the per-frame blends of nW sliding-window predictions (layout and tables of im360_cfg_ddim_step_windows)
+extern "C" __attribute__((visibility("default"))) int im360_cfg_rescale_stats_windows(const void* pred, const void* start, const void* weight, int nW,
+                                   int64_t outer, int64_t F, int64_t L, int64_t inner, float guidance, void* ws, int64_t ws_floats, int dtype,
+                                   void* stream, const void* coef_dev) {
+    const im360::Windows w{pred, start, weight, nW, 0, outer, F, L, inner};
+    return im360::cfg_rescale_stats_windows("cfg_rescale_stats_windows", w, guidance, ws, ws_floats, dtype, stream, coef_dev);
+}
+
+// the same with the windows on a ring of F frames (tables of im360_cfg_ddim_step_windows_ring).  The host cannot see the tables:
+// the caller guarantees 0 <= start[k] < F, every frame covered, L <= F.
+extern "C" __attribute__((visibility("default"))) int im360_cfg_rescale_stats_windows_ring(const void* pred, const void* start, const void* weight,
+                                   int nW, int64_t outer, int64_t F, int64_t L, int64_t inner, float guidance, void* ws, int64_t ws_floats, int dtype,
+                                   void* stream, const void* coef_dev) {
+    const im360::Windows w{pred, start, weight, nW, (int)F, outer, F, L, inner};
+    return im360::cfg_rescale_stats_windows("cfg_rescale_stats_windows_ring", w, guidance, ws, ws_floats, dtype, stream, coef_dev);
+}
+
+// out[0] = r = phi std(c) / std(m) + (1 - phi) from the records a statistics pass over n elements left in ws
+extern "C" __attribute__((visibility("default"))) int im360_cfg_rescale_factor(const void* ws, int64_t ws_floats, int64_t n, float phi, void* out,
+                                   void* stream) {
+    using namespace im360;
+    IM360_CHECK_ARG(out && ((uintptr_t)out % 4) == 0 && n > 0, "cfg_rescale_factor: null or misaligned output / empty problem");
+    IM360_CHECK_ARG(std::isfinite(phi), "cfg_rescale_factor: rescale=%g must be finite", (double)phi);
+    if (const int rc = check_rescale_ws("cfg_rescale_factor", ws, ws_floats, n)) return rc;
+    hipLaunchKernelGGL(cfg_rescale_factor_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)ws,
+                       (int)im360_cfg_rescale_records(n), phi, (float*)out);
+    return im360_launch_status();
+}
+
+// out = DDIMScheduler.step(uncond + g (cond - uncond), x, noise) for any prediction type / clip / eta, n elements (n % 8 == 0),
+// all same dtype; noise may be null (zero noise)
+extern "C" __attribute__((visibility("default"))) int im360_cfg_ddim_step(const void* uncond, const void* cond, const void* x, const void* noise,
+                                   void* out, int64_t n, float guidance, float sqrt_a, float sqrt_b, float sqrt_a_prev, float dir, float sigma,
+                                   int mode, int dtype, void* stream, const void* coef_dev) {
+    const im360::StepArgs s{guidance, sqrt_a, sqrt_b, sqrt_a_prev, dir, sigma, mode, noise, coef_dev, nullptr, 0, 0.0f};
+    return im360::cfg_ddim_step("cfg_ddim_step", uncond, cond, x, out, n, s, false, dtype, stream);
+}
+
+// the same step on r (uncond + g (cond - uncond)), r from the records im360_cfg_rescale_stats left in ws for the same n
+extern "C" __attribute__((visibility("default"))) int im360_cfg_ddim_step_rescale(const void* uncond, const void* cond, const void* x,
+                                   const void* noise, void* out, int64_t n, float guidance, float sqrt_a, float sqrt_b, float sqrt_a_prev, float dir,
+                                   float sigma, int mode, float phi, const void* ws, int64_t ws_floats, int dtype, void* stream,
+                                   const void* coef_dev) {
+    const im360::StepArgs s{guidance, sqrt_a, sqrt_b, sqrt_a_prev, dir, sigma, mode, noise, coef_dev, ws, ws_floats, phi};
+    return im360::cfg_ddim_step("cfg_ddim_step_rescale", uncond, cond, x, out, n, s, true, dtype, stream);
+}
+
+// The step of im360_cfg_ddim_step on the per-frame weighted blend of nW sliding-window predictions (see the kernel's comment):
+// x / noise / out [outer, F, inner], pred [nW, 2, outer, L, inner], start int32[nW] and weight float[L] on the device.  The host
+// cannot see the tables: the caller guarantees 0 <= start[k] <= F - L and that every frame is covered (imagine360_amd/context.py).
+extern "C" __attribute__((visibility("default"))) int im360_cfg_ddim_step_windows(const void* pred, const void* x, const void* noise, void* out,
+                                   const void* start, const void* weight, int nW, int64_t outer, int64_t F, int64_t L, int64_t inner, float guidance,
+                                   float sqrt_a, float sqrt_b, float sqrt_a_prev, float dir, float sigma, int mode, int dtype, void* stream,
+                                   const void* coef_dev) {
+    const im360::Windows w{pred, start, weight, nW, 0, outer, F, L, inner};
+    const im360::StepArgs s{guidance, sqrt_a, sqrt_b, sqrt_a_prev, dir, sigma, mode, noise, coef_dev, nullptr, 0, 0.0f};
+    return im360::cfg_ddim_step_windows("cfg_ddim_step_windows", w, x, out, s, false, dtype, stream);
+}
+
+// the same on r times the blend, r from the records im360_cfg_rescale_stats_windows left in ws for the same clip
+extern "C" __attribute__((visibility("default"))) int im360_cfg_ddim_step_windows_rescale(const void* pred, const void* x, const void* noise,
+                                   void* out, const void* start, const void* weight, int nW, int64_t outer, int64_t F, int64_t L, int64_t inner,
+                                   float guidance, float sqrt_a, float sqrt_b, float sqrt_a_prev, float dir, float sigma, int mode, float phi,
+                                   const void* ws, int64_t ws_floats, int dtype, void* stream, const void* coef_dev) {
+    const im360::Windows w{pred, start, weight, nW, 0, outer, F, L, inner};
+    const im360::StepArgs s{guidance, sqrt_a, sqrt_b, sqrt_a_prev, dir, sigma, mode, noise, coef_dev, ws, ws_floats, phi};
+    return im360::cfg_ddim_step_windows("cfg_ddim_step_windows_rescale", w, x, out, s, true, dtype, stream);
+}
+
+// im360_cfg_ddim_step_windows with the windows on a ring of F frames: window k covers the frames (start[k] + j) mod F, j = 0 .. L - 1,
+// position j of its prediction.  Same blend, same slot order, same step.  The host cannot see the tables: the caller guarantees
+// 0 <= start[k] < F, every frame covered, L <= F (imagine360_amd/context.py, loop=True).
+extern "C" __attribute__((visibility("default"))) int im360_cfg_ddim_step_windows_ring(const void* pred, const void* x, const void* noise, void* out,
+                                   const void* start, const void* weight, int nW, int64_t outer, int64_t F, int64_t L, int64_t inner, float guidance,
+                                   float sqrt_a, float sqrt_b, float sqrt_a_prev, float dir, float sigma, int mode, int dtype, void* stream,
+                                   const void* coef_dev) {
+    const im360::Windows w{pred, start, weight, nW, (int)F, outer, F, L, inner};
+    const im360::StepArgs s{guidance, sqrt_a, sqrt_b, sqrt_a_prev, dir, sigma, mode, noise, coef_dev, nullptr, 0, 0.0f};
+    return im360::cfg_ddim_step_windows("cfg_ddim_step_windows_ring", w, x, out, s, false, dtype, stream);
+}
+
+// the same on r times the blend, r from the records im360_cfg_rescale_stats_windows_ring left in ws for the same clip; the
+// precondition of im360_cfg_ddim_step_windows_ring: 0 <= start[k] < F, every frame covered, L <= F
+extern "C" __attribute__((visibility("default"))) int im360_cfg_ddim_step_windows_ring_rescale(const void* pred, const void* x, const void* noise,
+                                   void* out, const void* start, const void* weight, int nW, int64_t outer, int64_t F, int64_t L, int64_t inner,
+                                   float guidance, float sqrt_a, float sqrt_b, float sqrt_a_prev, float dir, float sigma, int mode, float phi,
+                                   const void* ws, int64_t ws_floats, int dtype, void* stream, const void* coef_dev) {
+    const im360::Windows w{pred, start, weight, nW, (int)F, outer, F, L, inner};
+    const im360::StepArgs s{guidance, sqrt_a, sqrt_b, sqrt_a_prev, dir, sigma, mode, noise, coef_dev, ws, ws_floats, phi};
+    return im360::cfg_ddim_step_windows("cfg_ddim_step_windows_ring_rescale", w, x, out, s, true, dtype, stream);
+}

@@ -861,7 +861,7 @@ DDIM_PRED_MODE = {"epsilon": 0, "v_prediction": 1, "sample": 2}
 DDIM_CLIP_SAMPLE, DDIM_CLIPPED_OUTPUT = 4, 8
 
 
-RESCALE_RECORD = 8         # floats per partial-moment record of the guidance-rescale statistics pass (csrc/groupnorm.hip)
+RESCALE_RECORD = 8         # floats per partial-moment record of the guidance-rescale statistics pass (csrc/sampler_step.hip)
 
 
 def _rescale_workspace(like):
@@ -878,6 +878,13 @@ def _rescale_stats(uncond, cond, guidance, coef_dev):
     return ws
 
 
+def _rescale_factor(ws, like, rescale):
+    """The factor from the records ``ws`` of a statistics pass over ``like``: a device float32 scalar."""
+    out = torch.empty((), dtype=torch.float32, device=like.device)
+    _check(lib().im360_cfg_rescale_factor(_p(ws), ws.numel(), like.numel(), float(rescale), _p(out), _stream()), "im360_cfg_rescale_factor")
+    return out
+
+
 def cfg_rescale_factor(uncond, cond, guidance, rescale, coef_dev=None):
     """The guidance-rescale factor r = rescale * std(cond) / std(m) + (1 - rescale), m = uncond + guidance * (cond - uncond) in fp32,
     std = torch.std (correction 1) over the whole tensor: a device float32 scalar, no synchronisation.  Two launches: the statistics
@@ -885,10 +892,17 @@ def cfg_rescale_factor(uncond, cond, guidance, rescale, coef_dev=None):
     makes -- the bits the step multiplies by.  ``coef_dev``: device float32 whose element 0 is read as the guidance instead."""
     _dev(uncond, cond, coef_dev)
     assert uncond.is_contiguous() and cond.is_contiguous() and uncond.shape == cond.shape and uncond.dtype == cond.dtype
-    ws = _rescale_stats(uncond, cond, guidance, coef_dev)
-    out = torch.empty((), dtype=torch.float32, device=cond.device)
-    _check(lib().im360_cfg_rescale_factor(_p(ws), ws.numel(), cond.numel(), float(rescale), _p(out), _stream()), "im360_cfg_rescale_factor")
-    return out
+    return _rescale_factor(_rescale_stats(uncond, cond, guidance, coef_dev), cond, rescale)
+
+
+def _check_step_noise(who, sample, noise, coefs, coef_dev):
+    """``noise`` like ``sample`` or None (refused with sigma > 0), ``coef_dev`` a device float32[6] or None: the step wrappers' rule."""
+    if noise is not None:
+        assert noise.is_contiguous() and noise.shape == sample.shape and noise.dtype == sample.dtype
+    elif coef_dev is None and coefs[5] != 0.0:
+        raise ValueError(f"{who}: sigma > 0 needs a noise tensor")
+    if coef_dev is not None:
+        assert coef_dev.dtype == torch.float32 and coef_dev.numel() == 6 and coef_dev.is_cuda
 
 
 def cfg_ddim_step(uncond, cond, sample, noise, mode, coefs, coef_dev=None, rescale=0.0):
@@ -902,12 +916,7 @@ def cfg_ddim_step(uncond, cond, sample, noise, mode, coefs, coef_dev=None, resca
     _dev(uncond, cond, sample, noise)
     assert uncond.is_contiguous() and cond.is_contiguous() and sample.is_contiguous()
     assert uncond.shape == cond.shape == sample.shape and uncond.dtype == cond.dtype == sample.dtype
-    if noise is not None:
-        assert noise.is_contiguous() and noise.shape == sample.shape and noise.dtype == sample.dtype
-    elif coef_dev is None and coefs[5] != 0.0:
-        raise ValueError("cfg_ddim_step: sigma > 0 needs a noise tensor")
-    if coef_dev is not None:
-        assert coef_dev.dtype == torch.float32 and coef_dev.numel() == 6 and coef_dev.is_cuda
+    _check_step_noise("cfg_ddim_step", sample, noise, coefs, coef_dev)
     out = torch.empty(sample.shape, dtype=sample.dtype, device=sample.device)
     if rescale != 0.0:
         ws = _rescale_stats(uncond, cond, coefs[0], coef_dev)
@@ -950,10 +959,7 @@ def cfg_rescale_factor_windows(preds, sample, starts, weights, guidance, rescale
     workgroup of its step kernel makes.  A device float32 scalar, no synchronisation.  ``ring``: the windows lie on a ring."""
     _dev(preds, sample, starts, weights, coef_dev)
     geometry = _windows_geometry(preds, sample, starts, weights)
-    ws = _rescale_stats_windows(preds, sample, starts, weights, geometry, guidance, coef_dev, ring)
-    out = torch.empty((), dtype=torch.float32, device=sample.device)
-    _check(lib().im360_cfg_rescale_factor(_p(ws), ws.numel(), sample.numel(), float(rescale), _p(out), _stream()), "im360_cfg_rescale_factor")
-    return out
+    return _rescale_factor(_rescale_stats_windows(preds, sample, starts, weights, geometry, guidance, coef_dev, ring), sample, rescale)
 
 
 def cfg_ddim_step_windows(preds, sample, noise, starts, weights, mode, coefs, coef_dev=None, rescale=0.0, ring=False):
@@ -967,12 +973,7 @@ def cfg_ddim_step_windows(preds, sample, noise, starts, weights, mode, coefs, co
     ``_ring`` entry points, the same blend and step."""
     _dev(preds, sample, noise, starts, weights)
     nW, outer, F, L, inner = geometry = _windows_geometry(preds, sample, starts, weights)
-    if noise is not None:
-        assert noise.is_contiguous() and noise.shape == sample.shape and noise.dtype == sample.dtype
-    elif coef_dev is None and coefs[5] != 0.0:
-        raise ValueError("cfg_ddim_step_windows: sigma > 0 needs a noise tensor")
-    if coef_dev is not None:
-        assert coef_dev.dtype == torch.float32 and coef_dev.numel() == 6 and coef_dev.is_cuda
+    _check_step_noise("cfg_ddim_step_windows", sample, noise, coefs, coef_dev)
     out = torch.empty(sample.shape, dtype=sample.dtype, device=sample.device)
     if rescale != 0.0:
         ws = _rescale_stats_windows(preds, sample, starts, weights, geometry, coefs[0], coef_dev, ring)
@@ -989,6 +990,26 @@ def cfg_ddim_step_windows(preds, sample, noise, starts, weights, mode, coefs, co
     return out
 
 
+def _check_latent_tables(who, ref_name, ref, noise, idx, ok):
+    """``idx`` int32 / ``ok`` uint8 of one [M, ph, pw] and ``noise`` [1, F, C, h, w] for the latent ``ref`` ([1, C, F, h, w], called
+    ``ref_name`` in the messages) of ``noise_latents`` / ``keep_latents``; returns (C, F, h, w, M, ph, pw)."""
+    if idx.dtype != torch.int32 or ok.dtype != torch.uint8:
+        raise TypeError(f"{who}: idx must be int32 and ok uint8, got {idx.dtype} and {ok.dtype}")
+    if ref.dim() != 5 or ref.shape[0] != 1:
+        raise ValueError(f"{who}: {ref_name} must be [1, C, F, h, w], got {list(ref.shape)}")
+    _, C, F, h, w = ref.shape
+    if tuple(noise.shape) != (1, F, C, h, w):
+        raise ValueError(f"{who}: noise must be {[1, F, C, h, w]} for {ref_name} {list(ref.shape)}, got {list(noise.shape)}")
+    if idx.dim() != 3 or idx.shape != ok.shape:
+        raise ValueError(f"{who}: idx and ok must be one [M, ph, pw], got {list(idx.shape)} and {list(ok.shape)}")
+    return (C, F, h, w, *idx.shape)
+
+
+def _check_one_device(who, names, tensors):
+    if not all(t.is_contiguous() and t.device == tensors[0].device for t in tensors):
+        raise ValueError(f"{who}: {names} must be contiguous and on one device")
+
+
 def noise_latents(x0, noise, idx, ok, sqrt_a, sqrt_b):
     """The start latents of a run that begins from a given clip, one launch: ``pano = T(sqrt_a * x0 + sqrt_b * noise)`` (fp32, one
     rounding) and ``pers`` = the nearest-neighbour E2P gather of the ROUNDED ``pano``, zero where a view sees nothing.
@@ -999,18 +1020,8 @@ def noise_latents(x0, noise, idx, ok, sqrt_a, sqrt_b):
     dt = _dt(x0)
     if noise.dtype != torch.float32:
         raise TypeError(f"noise_latents: noise must be float32 (the dtype init_noise draws in), got {noise.dtype}")
-    if idx.dtype != torch.int32 or ok.dtype != torch.uint8:
-        raise TypeError(f"noise_latents: idx must be int32 and ok uint8, got {idx.dtype} and {ok.dtype}")
-    if x0.dim() != 5 or x0.shape[0] != 1:
-        raise ValueError(f"noise_latents: x0 must be [1, C, F, h, w], got {list(x0.shape)}")
-    _, C, F, h, w = x0.shape
-    if tuple(noise.shape) != (1, F, C, h, w):
-        raise ValueError(f"noise_latents: noise must be {[1, F, C, h, w]} for x0 {list(x0.shape)}, got {list(noise.shape)}")
-    if idx.dim() != 3 or idx.shape != ok.shape:
-        raise ValueError(f"noise_latents: idx and ok must be one [M, ph, pw], got {list(idx.shape)} and {list(ok.shape)}")
-    if not all(t.is_contiguous() and t.device == x0.device for t in (x0, noise, idx, ok)):
-        raise ValueError("noise_latents: x0, noise, idx and ok must be contiguous and on one device")
-    M, ph, pw = idx.shape
+    C, F, h, w, M, ph, pw = _check_latent_tables("noise_latents", "x0", x0, noise, idx, ok)
+    _check_one_device("noise_latents", "x0, noise, idx and ok", (x0, noise, idx, ok))
     pano = torch.empty((1, C, F, h, w), dtype=x0.dtype, device=x0.device)
     pers = torch.empty((1, M, C, F, ph, pw), dtype=x0.dtype, device=x0.device)
     rc = lib().im360_noise_latents(_p(x0), _p(noise), _p(idx), _p(ok), _p(pano), _p(pers), F, C, h * w, M, ph * pw, float(sqrt_a),
@@ -1033,24 +1044,15 @@ def keep_latents(pano, pers, x0, noise, mask, idx, ok, sqrt_a, sqrt_b, coef_dev=
         raise TypeError(f"keep_latents: pano, pers and x0 must have one dtype, got {pano.dtype}, {pers.dtype} and {x0.dtype}")
     if noise.dtype != torch.float32 or mask.dtype != torch.float32:
         raise TypeError(f"keep_latents: noise and mask must be float32, got {noise.dtype} and {mask.dtype}")
-    if idx.dtype != torch.int32 or ok.dtype != torch.uint8:
-        raise TypeError(f"keep_latents: idx must be int32 and ok uint8, got {idx.dtype} and {ok.dtype}")
-    if pano.dim() != 5 or pano.shape[0] != 1:
-        raise ValueError(f"keep_latents: pano must be [1, C, F, h, w], got {list(pano.shape)}")
-    _, C, F, h, w = pano.shape
+    # (the shapes of noise and idx / ok are checked in front of those of x0 and mask: of two wrong shapes the first of this list is named)
+    C, F, h, w, M, ph, pw = _check_latent_tables("keep_latents", "pano", pano, noise, idx, ok)
     if x0.shape != pano.shape:
         raise ValueError(f"keep_latents: x0 must be {list(pano.shape)} like pano, got {list(x0.shape)}")
-    if tuple(noise.shape) != (1, F, C, h, w):
-        raise ValueError(f"keep_latents: noise must be {[1, F, C, h, w]} for pano {list(pano.shape)}, got {list(noise.shape)}")
     if tuple(mask.shape) != (F, h, w):
         raise ValueError(f"keep_latents: mask must be {[F, h, w]} for pano {list(pano.shape)}, got {list(mask.shape)}")
-    if idx.dim() != 3 or idx.shape != ok.shape:
-        raise ValueError(f"keep_latents: idx and ok must be one [M, ph, pw], got {list(idx.shape)} and {list(ok.shape)}")
-    M, ph, pw = idx.shape
     if tuple(pers.shape) != (1, M, C, F, ph, pw):
         raise ValueError(f"keep_latents: pers must be {[1, M, C, F, ph, pw]}, got {list(pers.shape)}")
-    if not all(t.is_contiguous() and t.device == pano.device for t in (pano, pers, x0, noise, mask, idx, ok)):
-        raise ValueError("keep_latents: pano, pers, x0, noise, mask, idx and ok must be contiguous and on one device")
+    _check_one_device("keep_latents", "pano, pers, x0, noise, mask, idx and ok", (pano, pers, x0, noise, mask, idx, ok))
     if x0.data_ptr() == pano.data_ptr():
         raise ValueError("keep_latents: x0 aliases pano (the update is in place: the clean clip would be overwritten)")
     if coef_dev is not None:

@@ -1,4 +1,4 @@
-"""Torch stand-in of ``kernels.cfg_ddim_step_windows`` (csrc/groupnorm.hip cfg_ddim_step_windows_kernel) for the CPU tier: the
+"""Torch stand-in of ``kernels.cfg_ddim_step_windows`` (csrc/sampler_step.hip cfg_ddim_step_windows_kernel) for the CPU tier: the
 per-frame weighted blend of the windows' CFG-combined predictions in fp32, accumulated over the windows in ascending order, then
 the step formulas of _emu_ddim_step.py; one rounding to the sample's dtype at the end.  Used on top of
 _emu_kernels.patched_kernels()."""

@@ -1,4 +1,4 @@
-"""Torch stand-in of ``kernels.cfg_ddim_step`` (csrc/groupnorm.hip cfg_ddim_step_kernel) for the CPU tier: the same
+"""Torch stand-in of ``kernels.cfg_ddim_step`` (csrc/sampler_step.hip cfg_ddim_step_kernel) for the CPU tier: the same
 per-element formulas in fp32, one rounding to the sample's dtype at the end.  Used together with
 _emu_kernels.patched_kernels(), which covers the other kernels."""
 import contextlib

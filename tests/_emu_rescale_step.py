@@ -1,4 +1,4 @@
-"""Torch stand-ins of the guidance-rescale kernels (csrc/groupnorm.hip: cfg_rescale_stats_kernel / cfg_rescale_stats_windows_kernel +
+"""Torch stand-ins of the guidance-rescale kernels (csrc/sampler_step.hip: cfg_rescale_stats_kernel / cfg_rescale_stats_windows_kernel +
 the rescaled cfg_ddim_step_kernel / cfg_ddim_step_windows_kernel) for the CPU tier: ``kernels.cfg_ddim_step`` and
 ``kernels.cfg_ddim_step_windows`` with the ``rescale`` keyword, and ``kernels.cfg_rescale_factor``.  rescale = 0 is the stand-in of
 _emu_ddim_step.py / _emu_ctx_step.py unchanged; otherwise the guided prediction m (for windows: the blend) is formed in fp32, multiplied

@@ -1,4 +1,4 @@
-"""Torch stand-ins of the ring entry points (csrc/groupnorm.hip: cfg_ddim_step_windows_kernel / cfg_rescale_stats_windows_kernel with
+"""Torch stand-ins of the ring entry points (csrc/sampler_step.hip: cfg_ddim_step_windows_kernel / cfg_rescale_stats_windows_kernel with
 wrap = F) for the CPU tier: ``kernels.cfg_ddim_step_windows`` with the ``ring`` keyword and ``kernels.cfg_rescale_factor_windows``.
 ring = False is the stand-in of _emu_rescale_step.py unchanged.  ring = True: window k adds its weighted predictions to the frames
 (starts[k] + j) mod F in fp32, k ascending (no window covers a frame twice, so the order per frame is the kernel's), the sums are divided

@@ -18,7 +18,7 @@ from imagine360_amd.scheduler import DDIMScheduler  # noqa: E402
 
 torch.set_grad_enabled(False)
 
-LDS_PLANE = 32768          # elements of the largest plane the kernel keeps in LDS (64 KiB; kNoiseLdsBytes of csrc/noise_latents.hip)
+LDS_PLANE = 32768          # elements of the largest plane the kernel keeps in LDS (64 KiB; kPlaneLdsBytes of csrc/latent_plane.h)
 
 # (F, C, h, w, M, ph, pw), byte offset of x0 from its alignment: one case on each side of every choice the launcher makes
 CASES = {
