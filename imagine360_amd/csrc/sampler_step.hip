@@ -1,6 +1,8 @@
 // The sampler-step family on 16-bit latents, gfx950: classifier-free guidance fused with the scheduler update in one elementwise pass
 // (cfg_ddim_kernel, cfg_ddim_step_kernel), the same step on the blend of temporal context windows on a line or a ring
-// (cfg_ddim_step_windows_kernel), and the statistics pass of the guidance rescale (cfg_rescale_*).
+// (cfg_ddim_step_windows_kernel), the statistics pass of the guidance rescale (cfg_rescale_*), and the DPM-Solver++ 2M update
+// (arXiv 2211.01095, algorithm 2) on the same combine, blend, rescale and x0 conversion (cfg_multistep_step_kernel,
+// cfg_multistep_step_windows_kernel), with its fp32 x0 history updated in place.
 // Replaces: the guidance combine + scheduler.step of the denoising loop (pipeline_animation_inference_dual.py:791-800) with
 // DDIMScheduler.step (diffusers/schedulers/scheduling_ddim.py:251-373; eta = 0, v-prediction: 300-350).  Context windows and the
 // guidance rescale have no call site in the reference pipeline: they compose that same step (see their comments).
@@ -81,6 +83,74 @@ __device__ __forceinline__ float ddim_step_elem(float m, float s, float z, const
     if (k.clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
     if (k.clipped_out) eps = (s - k.sa * x0) * k.isb;
     return k.sap * x0 + k.dir * eps + k.sigma * z;
+}
+
+// The x0 of ddim_step_elem alone, for an update that needs no e: prediction type `pred` (mode bits 0-1), clamp with `clip` (mode bit 2),
+// isa = 1 / sa.  ddim_step_elem keeps its own interleaved x0 / e branches: routing it through this function changes the code hipcc
+// emits for the DDIM kernels (-ffast-math), and the default sampler has to give the bits it gave.
+__device__ __forceinline__ float step_x0(float m, float s, int pred, bool clip, float sa, float sb, float isa) {
+    float x0;
+    if (pred == 0) x0 = (s - sb * m) * isa;
+    else if (pred == 1) x0 = sa * s - sb * m;
+    else x0 = m;
+    if (clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    return x0;
+}
+
+// ---- the DPM-Solver++ 2M update (arXiv 2211.01095, algorithm 2; data prediction, multistep order <= 2) in its linear form
+//          out = cx * x + c0 * x0 + c1 * x0_old,      hist <- x0
+//      with x0 = step_x0 of the guided prediction (the three prediction types and the clamp of the DDIM step) and x0_old the x0 of
+//      the step run before, kept in fp32 (never rounded to 16 bits: |c0|, |c1| reach 2.7 and 1.75 on the shipped grid).  cx, c0, c1
+//      come from fp64 host math (DPMSolverMultistepScheduler.multistep_coefficients); a first-order step (the first and the last
+//      one of a run, solver_order = 1) has c1 == 0 and then `hist` is NOT read: h is 0 and the term is left out, so whatever the
+//      history holds -- NaN included -- cannot reach out.  sa, sb = sqrt(a_t), sqrt(1 - a_t) as in DdimCoefs.
+struct MultistepCoefs {
+    float g, sa, sb, cx, c0, c1, isa;
+    int pred;
+    bool clip, hist;                 // hist: c1 != 0, uniform over the launch
+};
+
+__device__ __forceinline__ MultistepCoefs multistep_coefs(float g, float sa, float sb, float cx, float c0, float c1, int mode,
+                                                          const float* __restrict__ coef) {
+    if (coef != nullptr) {          // (guidance, sa, sb, cx, c0, c1) read on the device: hipGraph replay
+        g = coef[0];
+        sa = coef[1];
+        sb = coef[2];
+        cx = coef[3];
+        c0 = coef[4];
+        c1 = coef[5];
+    }
+    MultistepCoefs k;
+    k.g = g, k.sa = sa, k.sb = sb, k.cx = cx, k.c0 = c0, k.c1 = c1;
+    k.isa = 1.0f / sa;
+    k.pred = mode & 3;
+    k.clip = (mode & 4) != 0;
+    k.hist = c1 != 0.0f;
+    return k;
+}
+
+// One element: m the guided prediction, s the sample, h the old x0 (0 when !k.hist).  Returns out and leaves the new x0 in h.  The two
+// value barriers keep m and x0 the values the caller / the history see: this file is built with -ffast-math, and what produced m (the
+// blend's division, the rescale) must not be folded into the coefficients differently in the plain and in the windows kernel.
+__device__ __forceinline__ float multistep_step_elem(float m, float s, float& h, const MultistepCoefs& k) {
+    asm volatile("" : "+v"(m));
+    float x0 = step_x0(m, s, k.pred, k.clip, k.sa, k.sb, k.isa);
+    asm volatile("" : "+v"(x0));
+    float o = __fmaf_rn(k.c0, x0, k.cx * s);
+    if (k.hist) o = __fmaf_rn(k.c1, h, o);
+    h = x0;
+    return o;
+}
+
+// the fp32 history of the 8 elements of lane i: two float4
+__device__ __forceinline__ void hist_load8(const float* __restrict__ hist, long i, float* h) {
+    const float4 a = ((const float4*)hist)[2 * i], b = ((const float4*)hist)[2 * i + 1];
+    h[0] = a.x, h[1] = a.y, h[2] = a.z, h[3] = a.w, h[4] = b.x, h[5] = b.y, h[6] = b.z, h[7] = b.w;
+}
+
+__device__ __forceinline__ void hist_store8(float* __restrict__ hist, long i, const float* h) {
+    ((float4*)hist)[2 * i] = make_float4(h[0], h[1], h[2], h[3]);
+    ((float4*)hist)[2 * i + 1] = make_float4(h[4], h[5], h[6], h[7]);
 }
 
 // ---- guidance rescale (arXiv 2305.08891, section 3.4): m' = r m with r = phi std(c) / std(m) + (1 - phi), the standard deviations
@@ -248,6 +318,36 @@ __global__ __launch_bounds__(RS ? 256 : 1024) void cfg_ddim_step_kernel(const T*
     }
 }
 
+// ---- CFG combine + the multistep update above: the loop of cfg_ddim_step_kernel with the history stream.  hist: float[8 n8], read
+//      (k.hist only) and written by the thread that owns the lane.
+template <typename T, bool RS>
+__global__ __launch_bounds__(RS ? 256 : 1024) void cfg_multistep_step_kernel(const T* __restrict__ uncond, const T* __restrict__ cond, const T* __restrict__ x,
+                                     float* __restrict__ hist, T* __restrict__ out, long n8, float g, float sa, float sb, float cx,
+                                     float c0, float c1, int mode, const float* __restrict__ coef, const float* __restrict__ ws,
+                                     int nrec, float phi) {
+    const MultistepCoefs k = multistep_coefs(g, sa, sb, cx, c0, c1, mode, coef);
+    float r = 1.0f;
+    if (RS) r = rescale_factor(ws, nrec, phi);
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
+        float u[8], c[8], s[8], h[8];
+        unpack8<T>(((const uint4*)uncond)[i], u);
+        unpack8<T>(((const uint4*)cond)[i], c);
+        unpack8<T>(((const uint4*)x)[i], s);
+        if (k.hist) hist_load8(hist, i, h);
+        else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) h[e] = 0.0f;
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float m = cfg_combine(u[e], c[e], k.g);
+            s[e] = multistep_step_elem(RS ? rescale_mul(r, m) : m, s[e], h[e], k);
+        }
+        hist_store8(hist, i, h);
+        ((uint4*)out)[i] = pack8<T>(s);
+    }
+}
+
 // ---- the same step on the per-frame blend of sliding temporal context windows.  x / noise / out are [outer, F, inner]; the
 //      predictions of all windows sit in one buffer pred[nW, 2, outer, L, inner] (window, CFG half, the model's own layout);
 //      start[nW] ascending window start frames, weight[L] the blend weight of each position inside a window.  Per element at frame f:
@@ -364,6 +464,42 @@ __global__ __launch_bounds__(RS ? 256 : 1024) void cfg_ddim_step_windows_kernel(
         for (int e = 0; e < V; ++e) s[e] = ddim_step_elem(RS ? rescale_mul(r, m[e]) : m[e], s[e], z[e], k);
         if (V == 8) ((uint4*)out)[i] = pack8<T>(s);
         else out[i] = from_f32<T>(s[0]);
+    }
+}
+
+// the multistep update on the blend of the windows (windows_blend; wrap: line or ring), hist [outer, F, inner] like x
+template <typename T, int V, bool RS>
+__global__ __launch_bounds__(RS ? 256 : 1024) void cfg_multistep_step_windows_kernel(const T* __restrict__ pred, const T* __restrict__ x, float* __restrict__ hist,
+                                             T* __restrict__ out, const int* __restrict__ start, const float* __restrict__ weight,
+                                             int nW, long outer, int F, int L, int wrap, long inner, float g, float sa, float sb, float cx,
+                                             float c0, float c1, int mode, const float* __restrict__ coef,
+                                             const float* __restrict__ ws, int nrec, float phi) {
+    const MultistepCoefs k = multistep_coefs(g, sa, sb, cx, c0, c1, mode, coef);
+    float r = 1.0f;
+    if (RS) r = rescale_factor(ws, nrec, phi);
+    const long nv = outer * F * inner / V;
+    const long half = outer * L * inner;              // one CFG half of one window
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
+        float m[V], s[V], h[V];
+        windows_blend<T, V, false>(pred, start, weight, nW, F, L, wrap, inner, half, i * V, k.g, m, nullptr);
+        if (V == 8) unpack8<T>(((const uint4*)x)[i], s);
+        else s[0] = to_f32<T>(x[i]);
+        if (k.hist) {
+            if (V == 8) hist_load8(hist, i, h);
+            else h[0] = hist[i];
+        } else {
+#pragma unroll
+            for (int e = 0; e < V; ++e) h[e] = 0.0f;
+        }
+#pragma unroll
+        for (int e = 0; e < V; ++e) s[e] = multistep_step_elem(RS ? rescale_mul(r, m[e]) : m[e], s[e], h[e], k);
+        if (V == 8) {
+            hist_store8(hist, i, h);
+            ((uint4*)out)[i] = pack8<T>(s);
+        } else {
+            hist[i] = h[0];
+            out[i] = from_f32<T>(s[0]);
+        }
     }
 }
 
@@ -488,6 +624,65 @@ static int cfg_rescale_stats_windows(const char* name, const Windows& w, float g
         return im360_launch_status();
     });
 }
+
+// What the two multistep entry points are given besides their tensors; `s` carries what the shared checks read (mode, phi, workspace)
+struct MultistepArgs {
+    StepArgs s;
+    float cx, c0, c1;
+    void* hist;
+    bool rescale() const { return s.ws != nullptr; }
+};
+static StepArgs multistep_step_args(float g, float sa, float sb, int mode, float phi, const void* ws, int64_t ws_floats, const void* coef_dev) {
+    return StepArgs{g, sa, sb, 0.0f, 0.0f, 0.0f, mode, nullptr, coef_dev, ws, ws_floats, phi};
+}
+// mode bit 8 (use_clipped_model_output) has no meaning for the multistep update; a strength without a workspace is a forgotten
+// statistics pass; with a workspace: check_step_rescale for n elements
+static int check_multistep(const char* name, const MultistepArgs& a, int64_t n) {
+    IM360_CHECK_ARG((a.s.mode & 8) == 0, "%s: mode %d: bit 8 (use_clipped_model_output) unsupported", name, a.s.mode);
+    IM360_CHECK_ARG(a.rescale() || a.s.phi == 0.0f, "%s: rescale=%g needs the workspace of a statistics pass", name, (double)a.s.phi);
+    return a.rescale() ? check_step_rescale(name, a.s, n) : IM360_OK;
+}
+
+// im360_cfg_multistep_step: checks, then the launch
+static int cfg_multistep_step(const char* name, const void* uncond, const void* cond, const void* x, void* out, int64_t n,
+                              const MultistepArgs& a, int dtype, void* stream) {
+    if (const int rc = check_tensors(name, {uncond, cond, x, a.hist, out}, nullptr, n)) return rc;
+    if (const int rc = check_step(name, a.s)) return rc;
+    if (const int rc = check_multistep(name, a, n)) return rc;
+    const long n8 = n / 8;
+    const int nrec = a.rescale() ? (int)im360_cfg_rescale_records(n) : 0;
+    return with_dtype(dtype, name, [&](auto t) {
+        using T = typename decltype(t)::type;
+        with_bool(a.rescale(), [&](auto rs) {
+            hipLaunchKernelGGL((cfg_multistep_step_kernel<T, decltype(rs)::value>), dim3(step_blocks(n8)), dim3(256), 0, (hipStream_t)stream,
+                               (const T*)uncond, (const T*)cond, (const T*)x, (float*)a.hist, (T*)out, n8, a.s.g, a.s.sa, a.s.sb, a.cx, a.c0,
+                               a.c1, a.s.mode, (const float*)a.s.coef_dev, (const float*)a.s.ws, nrec, a.s.phi);
+        });
+        return im360_launch_status();
+    });
+}
+
+// im360_cfg_multistep_step_windows (w.wrap: line or ring): checks, then the launch
+static int cfg_multistep_step_windows(const char* name, const Windows& w, int64_t wrap, const void* x, void* out, const MultistepArgs& a,
+                                      int dtype, void* stream) {
+    if (const int rc = check_windows(name, w, x && a.hist && out, &a.s)) return rc;
+    IM360_CHECK_ARG(wrap == 0 || wrap == w.F, "%s: wrap=%ld must be 0 (line) or F=%ld (ring)", name, (long)wrap, (long)w.F);
+    IM360_CHECK_ARG(((uintptr_t)a.hist % 4) == 0, "%s: misaligned history", name);
+    if (const int rc = check_multistep(name, a, w.elements())) return rc;
+    const bool vec = (w.inner % 8) == 0 && (((uintptr_t)w.pred | (uintptr_t)x | (uintptr_t)a.hist | (uintptr_t)out) % 16) == 0;
+    const long nv = (long)w.elements() / (vec ? 8 : 1);
+    const int nrec = a.rescale() ? (int)im360_cfg_rescale_records(w.elements()) : 0;
+    return with_dtype(dtype, name, [&](auto t) {
+        using T = typename decltype(t)::type;
+        with_const<1, 8>(vec ? 8 : 1, [&](auto v) { with_bool(a.rescale(), [&](auto rs) {
+            hipLaunchKernelGGL((cfg_multistep_step_windows_kernel<T, decltype(v)::value, decltype(rs)::value>), dim3(step_blocks(nv)), dim3(256), 0,
+                               (hipStream_t)stream, (const T*)w.pred, (const T*)x, (float*)a.hist, (T*)out, (const int*)w.start,
+                               (const float*)w.weight, w.nW, (long)w.outer, (int)w.F, (int)w.L, w.wrap, (long)w.inner, a.s.g, a.s.sa, a.s.sb,
+                               a.cx, a.c0, a.c1, a.s.mode, (const float*)a.s.coef_dev, (const float*)a.s.ws, nrec, a.s.phi);
+        }); });
+        return im360_launch_status();
+    });
+}
 }  // namespace im360
 
 // out = cx * x + cv * (uncond + g (cond - uncond)), n elements (n % 8 == 0), all same dtype
@@ -608,4 +803,24 @@ extern "C" __attribute__((visibility("default"))) int im360_cfg_ddim_step_window
     const im360::Windows w{pred, start, weight, nW, (int)F, outer, F, L, inner};
     const im360::StepArgs s{guidance, sqrt_a, sqrt_b, sqrt_a_prev, dir, sigma, mode, noise, coef_dev, ws, ws_floats, phi};
     return im360::cfg_ddim_step_windows("cfg_ddim_step_windows_ring_rescale", w, x, out, s, true, dtype, stream);
+}
+
+// out = the DPM-Solver++ 2M update (arXiv 2211.01095, algorithm 2) of x on uncond + g (cond - uncond), hist <- x0 (fp32, in place);
+// n elements (n % 8 == 0), uncond / cond / x / out of the same 16-bit dtype; ws == NULL: without the guidance rescale
+extern "C" __attribute__((visibility("default"))) int im360_cfg_multistep_step(const void* uncond, const void* cond, const void* x, void* hist,
+                                   void* out, int64_t n, float guidance, float sqrt_a, float sqrt_b, float cx, float c0, float c1, int mode,
+                                   float phi, const void* ws, int64_t ws_floats, int dtype, void* stream, const void* coef_dev) {
+    const im360::MultistepArgs a{im360::multistep_step_args(guidance, sqrt_a, sqrt_b, mode, phi, ws, ws_floats, coef_dev), cx, c0, c1, hist};
+    return im360::cfg_multistep_step("cfg_multistep_step", uncond, cond, x, out, n, a, dtype, stream);
+}
+
+// the same update on the per-frame blend of nW sliding-window predictions (tables and layout of im360_cfg_ddim_step_windows);
+// wrap = 0: the windows lie on a line, wrap = F: on a ring (preconditions of im360_cfg_ddim_step_windows_ring)
+extern "C" __attribute__((visibility("default"))) int im360_cfg_multistep_step_windows(const void* pred, const void* x, void* hist, void* out,
+                                   const void* start, const void* weight, int nW, int64_t outer, int64_t F, int64_t L, int64_t inner, int64_t wrap,
+                                   float guidance, float sqrt_a, float sqrt_b, float cx, float c0, float c1, int mode, float phi, const void* ws,
+                                   int64_t ws_floats, int dtype, void* stream, const void* coef_dev) {
+    const im360::Windows w{pred, start, weight, nW, wrap == 0 ? 0 : (int)F, outer, F, L, inner};
+    const im360::MultistepArgs a{im360::multistep_step_args(guidance, sqrt_a, sqrt_b, mode, phi, ws, ws_floats, coef_dev), cx, c0, c1, hist};
+    return im360::cfg_multistep_step_windows("cfg_multistep_step_windows", w, wrap, x, out, a, dtype, stream);
 }

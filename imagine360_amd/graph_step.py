@@ -64,6 +64,9 @@ class GraphedDenoiseStep:
         init_pano, init_pers = pano_latent.clone(), pers_latent.clone()
         self.pano_lat = init_pano.clone()
         self.pers_lat = init_pers.clone()
+        # a multistep scheduler's x0 histories, one per branch (None: DDIM).  The warm-up below runs a first-order step, which only
+        # writes them, and so does the first step of every run: no reset after warm-up or capture
+        self.hist = (scheduler.new_history(self.pano_lat), scheduler.new_history(self.pers_lat)) if hasattr(scheduler, "new_history") else None
         self.timestep = torch.zeros(1, dtype=torch.int64, device=dev)
         self.coef = torch.zeros(6 if self.step_kernel else 3, dtype=torch.float32, device=dev)
         self.use_fps = use_fps
@@ -140,12 +143,16 @@ class GraphedDenoiseStep:
         pred_pano, pred_pers = pred_pano.to(ldt), pred_pers.to(ldt)
         kw = dict(eta=self.eta, use_clipped_model_output=self.clipped, guidance_rescale=self.rescale)
         new_pano = self.sch.fused_cfg_step(pred_pano[0:1], pred_pano[1:2], self.g, None, self.pano_lat, coef_dev=self.coef,
-                                           noise=self._noise(self.pano_lat, mdt, 2), **kw)
+                                           noise=self._noise(self.pano_lat, mdt, 2), **kw, **self._history(0))
         new_pers = self.sch.fused_cfg_step(pred_pers[0:1], pred_pers[1:2], self.g, None, self.pers_lat, coef_dev=self.coef,
-                                           noise=self._noise(self.pers_lat, mdt, 3), **kw)
+                                           noise=self._noise(self.pers_lat, mdt, 3), **kw, **self._history(1))
         self._keep(new_pano, new_pers)
         self.pano_lat.copy_(new_pano)
         self.pers_lat.copy_(new_pers)
+
+    def _history(self, branch):
+        """``history=`` of one branch's step call (0 panorama, 1 perspective); nothing with a scheduler that keeps none."""
+        return {} if self.hist is None else dict(history=self.hist[branch])
 
     def _keep(self, new_pano, new_pers):
         """The kept region blended into the two fresh latents, in place (``keep`` only), coefficients from the device."""
@@ -214,9 +221,9 @@ class GraphedWindowedStep(GraphedDenoiseStep):
         kw = dict(coef_dev=self.coef, eta=self.eta, use_clipped_model_output=self.clipped, guidance_rescale=self.rescale,
                   ring=self.plan.loop)
         new_pano = self.sch.fused_cfg_step_windows(self.preds_pano, self.plan.starts_dev, self.plan.weights, self.g, None,
-                                                   self.pano_lat, noise=self._noise(self.pano_lat, mdt, 2), **kw)
+                                                   self.pano_lat, noise=self._noise(self.pano_lat, mdt, 2), **kw, **self._history(0))
         new_pers = self.sch.fused_cfg_step_windows(self.preds_pers, self.plan.starts_dev, self.plan.weights, self.g, None,
-                                                   self.pers_lat, noise=self._noise(self.pers_lat, mdt, 3), **kw)
+                                                   self.pers_lat, noise=self._noise(self.pers_lat, mdt, 3), **kw, **self._history(1))
         self._keep(new_pano, new_pers)
         self.pano_lat.copy_(new_pano)
         self.pers_lat.copy_(new_pers)

@@ -64,6 +64,8 @@ _SIGNATURES = {
     "im360_cfg_rescale_stats_windows_ring": (_INT, [_PTR] * 3 + [_INT] + [_I64] * 4 + [_F32, _PTR, _I64, _INT, _PTR, _PTR]),
     "im360_cfg_ddim_step_windows_ring_rescale": (_INT, [_PTR] * 6 + [_INT] + [_I64] * 4 + [_F32] * 6 + [_INT, _F32, _PTR, _I64, _INT,
                                                                                                        _PTR, _PTR]),
+    "im360_cfg_multistep_step": (_INT, [_PTR] * 5 + [_I64] + [_F32] * 6 + [_INT, _F32, _PTR, _I64, _INT, _PTR, _PTR]),
+    "im360_cfg_multistep_step_windows": (_INT, [_PTR] * 6 + [_INT] + [_I64] * 5 + [_F32] * 6 + [_INT, _F32, _PTR, _I64, _INT, _PTR, _PTR]),
     "im360_noise_latents": (_INT, [_PTR] * 6 + [_I64] * 5 + [_F32, _F32, _INT, _PTR]),
     "im360_keep_latents": (_INT, [_PTR] * 7 + [_I64] * 5 + [_F32, _F32, _INT, _PTR, _PTR]),
     "im360_resize_pano_latent": (_INT, [_PTR] * 2 + [_I64] * 6 + [_INT, _INT, _PTR]),
@@ -987,6 +989,54 @@ def cfg_ddim_step_windows(preds, sample, noise, starts, weights, mode, coefs, co
     rc = getattr(lib(), name)(_p(preds), _p(sample), _p(noise), _p(out), _p(starts), _p(weights), nW, outer, F, L, inner,
                               *(float(v) for v in coefs), int(mode), _dt(sample), _stream(), _p(coef_dev))
     _check(rc, name)
+    return out
+
+
+def _check_multistep(who, sample, hist, mode, coefs, coef_dev):
+    """``hist`` a contiguous float32 tensor of ``sample``'s element count on its device; no mode bit 8; ``coef_dev`` as in the
+    DDIM step wrappers."""
+    if hist is None or hist.dtype != torch.float32 or not hist.is_contiguous() or hist.numel() != sample.numel() or hist.device != sample.device:
+        raise ValueError(f"{who}: history must be a contiguous float32 tensor of the sample's {sample.numel()} elements on its device")
+    if int(mode) & DDIM_CLIPPED_OUTPUT:
+        raise ValueError(f"{who}: mode bit {DDIM_CLIPPED_OUTPUT} (use_clipped_model_output) has no meaning for the multistep update")
+    assert len(coefs) == 6
+    if coef_dev is not None:
+        assert coef_dev.dtype == torch.float32 and coef_dev.numel() == 6 and coef_dev.is_cuda
+
+
+def cfg_multistep_step(uncond, cond, sample, hist, mode, coefs, coef_dev=None, rescale=0.0):
+    """The DPM-Solver++ 2M update (arXiv 2211.01095, algorithm 2) of ``sample`` on uncond + g (cond - uncond), one pass:
+    ``cx * sample + c0 * x0 + c1 * hist`` with x0 the prediction-type conversion (and clamp) of ``cfg_ddim_step``; ``hist`` (float32,
+    like ``sample``) then holds x0, written in place, and is not read when c1 == 0.  ``mode``: DDIM_PRED_MODE | DDIM_CLIP_SAMPLE;
+    ``coefs`` = (guidance, sqrt_a, sqrt_b, cx, c0, c1) (DPMSolverMultistepScheduler.multistep_coefficients); ``coef_dev`` = device
+    float32[6] holding them, read by the kernel instead (graph replay).  ``rescale`` != 0: guidance rescale, the statistics launch of
+    ``cfg_ddim_step`` in front of the step launch."""
+    _dev(uncond, cond, sample, hist)
+    assert uncond.is_contiguous() and cond.is_contiguous() and sample.is_contiguous()
+    assert uncond.shape == cond.shape == sample.shape and uncond.dtype == cond.dtype == sample.dtype
+    _check_multistep("cfg_multistep_step", sample, hist, mode, coefs, coef_dev)
+    out = torch.empty(sample.shape, dtype=sample.dtype, device=sample.device)
+    ws = _rescale_stats(uncond, cond, coefs[0], coef_dev) if rescale != 0.0 else None
+    rc = lib().im360_cfg_multistep_step(_p(uncond), _p(cond), _p(sample), _p(hist), _p(out), sample.numel(), *(float(v) for v in coefs),
+                                        int(mode), float(rescale), _p(ws), 0 if ws is None else ws.numel(), _dt(sample), _stream(),
+                                        _p(coef_dev))
+    _check(rc, "im360_cfg_multistep_step")
+    return out
+
+
+def cfg_multistep_step_windows(preds, sample, hist, starts, weights, mode, coefs, coef_dev=None, rescale=0.0, ring=False):
+    """``cfg_multistep_step`` on the per-frame weighted blend of sliding-window predictions, one pass: ``preds`` / ``starts`` /
+    ``weights`` / ``ring`` as in ``cfg_ddim_step_windows``, ``hist`` float32 in ``sample``'s layout.  ``rescale`` != 0: the
+    statistics launch over the blends in front of the step launch."""
+    _dev(preds, sample, hist, starts, weights)
+    nW, outer, F, L, inner = geometry = _windows_geometry(preds, sample, starts, weights)
+    _check_multistep("cfg_multistep_step_windows", sample, hist, mode, coefs, coef_dev)
+    out = torch.empty(sample.shape, dtype=sample.dtype, device=sample.device)
+    ws = _rescale_stats_windows(preds, sample, starts, weights, geometry, coefs[0], coef_dev, ring) if rescale != 0.0 else None
+    rc = lib().im360_cfg_multistep_step_windows(_p(preds), _p(sample), _p(hist), _p(out), _p(starts), _p(weights), nW, outer, F, L, inner,
+                                                F if ring else 0, *(float(v) for v in coefs), int(mode), float(rescale), _p(ws),
+                                                0 if ws is None else ws.numel(), _dt(sample), _stream(), _p(coef_dev))
+    _check(rc, "im360_cfg_multistep_step_windows")
     return out
 
 

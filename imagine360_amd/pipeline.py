@@ -359,6 +359,13 @@ class AnimationPipeline:
         vb = video_batch
         plan = None
         guidance_rescale = float(guidance_rescale)
+        if hasattr(self.scheduler, "new_history"):
+            if eta > 0:
+                raise ValueError(f"eta={eta} cannot be combined with {type(self.scheduler).__name__} (DPM-Solver++ 2M is the ODE solver; its "
+                                 "SDE variant is not implemented): use DDIMScheduler for stochastic sampling")
+            if frame_shard is not None:
+                raise ValueError(f"frame_shard cannot be combined with {type(self.scheduler).__name__} (the cut of the x0 history to a rank's "
+                                 "frames is not implemented): use DDIMScheduler")
         if guidance_rescale != 0.0 and frame_shard is not None:
             raise ValueError("guidance_rescale cannot be combined with frame_shard (the standard deviations span the frames of all "
                              "ranks and would need an all-reduce inside the step, which is not implemented)")
@@ -413,6 +420,11 @@ class AnimationPipeline:
         else:
             pano_latent, pers_latent = self.init_noise(1, f, H // 8, W // 8, ps // 8, ps // 8, cameras, device, latents_dtype)
             region = None
+        hist = None
+        if hasattr(self.scheduler, "new_history"):
+            # a multistep scheduler: the run's timestep list fixes its coefficients, and each branch's latent owns its x0 history
+            self.scheduler.begin_run(steps_host)
+            hist = (self.scheduler.new_history(pano_latent), self.scheduler.new_history(pers_latent))
         sh = frame_shard
         if sh is not None:
             # every rank drew the whole clip's noise from the same seed: cut to the local frames
@@ -456,7 +468,7 @@ class AnimationPipeline:
                               reference_images_clip_feat_pers=feat_pers, relative_position_tensor=rel, pitchs_tensor=pitch)
                 pano_latent, pers_latent = self._windowed_loop(plan, inputs, cameras, pano_latent, pers_latent, steps_host, ts_dev,
                                                                guidance_scale_text, use_fps_condition, eta, generator, trace,
-                                                               callback, callback_steps, guidance_rescale, region)
+                                                               callback, callback_steps, guidance_rescale, region, hist)
             graphed = None
             import torch.distributed as tdist
             capturable = sh is None or (tdist.is_initialized() and tdist.get_backend(sh.group) == "nccl")     # RCCL all-to-alls are stream ops
@@ -483,8 +495,10 @@ class AnimationPipeline:
                     use_ip_plus_cross_attention=use_ip_plus_cross_attention, fps_tensor_pano=fps_pano, fps_tensor_pers=fps_pers,
                     reference_images_clip_feat_pano=feat_pano, reference_images_clip_feat_pers=feat_pers,
                     relative_position_tensor=rel, pitchs_tensor=pitch)
-                pano_latent = self._cfg_step(pred_pano, guidance_scale_text, t, pano_latent, eta, generator, sh, 2, guidance_rescale)
-                pers_latent = self._cfg_step(pred_pers, guidance_scale_text, t, pers_latent, eta, generator, sh, 3, guidance_rescale)
+                pano_latent = self._cfg_step(pred_pano, guidance_scale_text, t, pano_latent, eta, generator, sh, 2, guidance_rescale,
+                                             **({} if hist is None else dict(history=hist[0])))
+                pers_latent = self._cfg_step(pred_pers, guidance_scale_text, t, pers_latent, eta, generator, sh, 3, guidance_rescale,
+                                             **({} if hist is None else dict(history=hist[1])))
                 if region is not None:
                     region.apply(pano_latent, pers_latent, i)
                 if trace is not None:
@@ -507,20 +521,22 @@ class AnimationPipeline:
             if sh is not None:
                 self.mv_base_model.set_frame_shard(None)      # also when the loop raises: the model must not stay sharded
 
-    def _cfg_step(self, pred, g, t, latent, eta=0.0, generator=None, shard=None, frame_dim=2, guidance_rescale=0.0):
+    def _cfg_step(self, pred, g, t, latent, eta=0.0, generator=None, shard=None, frame_dim=2, guidance_rescale=0.0, **history):
+        """``history`` (``history=``, a multistep scheduler only): the x0 history of this latent, handed on to the scheduler."""
         u, c = pred.to(latent.dtype).chunk(2)          # latents_dtype may differ from the model dtype (the reference promotes)
         if eta > 0:
             z = variance_noise(self.scheduler, latent, pred.dtype, generator, self.rng, shard, frame_dim)
             return self.scheduler.fused_cfg_step(u, c, g, t, latent, eta=eta, noise=z, guidance_rescale=guidance_rescale)
-        return self.scheduler.fused_cfg_step(u, c, g, t, latent, guidance_rescale=guidance_rescale)
+        return self.scheduler.fused_cfg_step(u, c, g, t, latent, guidance_rescale=guidance_rescale, **history)
 
     def _windowed_loop(self, plan, inputs, cameras, pano_latent, pers_latent, steps_host, ts_dev, g, use_fps, eta, generator,
-                       trace, callback, callback_steps, guidance_rescale=0.0, keep=None):
+                       trace, callback, callback_steps, guidance_rescale=0.0, keep=None, hist=None):
         """The denoising loop over sliding temporal context windows: per step one forward per window (slot order), then ONE
         blend + CFG + DDIM kernel per branch, panorama first.  RNG: as len(plan) successive calls of the model, then (eta > 0)
         the whole clip's panorama and perspective variance noise.  Captured in one hipGraph under the conditions of the
         one-block loop (graph_step.GraphedWindowedStep), issued eagerly otherwise.  ``keep`` (KeepRegion): its blend of the whole
-        clip after the two windows kernels of every step."""
+        clip after the two windows kernels of every step.  ``hist``: the (panorama, perspective) x0 histories of a multistep scheduler for the
+        eager loop (the graphed step owns its own)."""
         from .context import ip_cache_slots
         mv, sch = self.mv_base_model, self.scheduler
         with ip_cache_slots(mv, len(plan)):
@@ -541,9 +557,11 @@ class AnimationPipeline:
                 mdt = mv.unet.dtype
                 kw = dict(eta=eta, guidance_rescale=guidance_rescale, ring=plan.loop)
                 z = variance_noise(sch, pano_latent, mdt, generator, self.rng) if eta > 0 else None
-                pano_latent = sch.fused_cfg_step_windows(preds_pano, plan.starts_dev, plan.weights, g, t, pano_latent, noise=z, **kw)
+                pano_latent = sch.fused_cfg_step_windows(preds_pano, plan.starts_dev, plan.weights, g, t, pano_latent, noise=z, **kw,
+                                                         **({} if hist is None else dict(history=hist[0])))
                 z = variance_noise(sch, pers_latent, mdt, generator, self.rng, frame_dim=3) if eta > 0 else None
-                pers_latent = sch.fused_cfg_step_windows(preds_pers, plan.starts_dev, plan.weights, g, t, pers_latent, noise=z, **kw)
+                pers_latent = sch.fused_cfg_step_windows(preds_pers, plan.starts_dev, plan.weights, g, t, pers_latent, noise=z, **kw,
+                                                         **({} if hist is None else dict(history=hist[1])))
                 if keep is not None:
                     keep.apply(pano_latent, pers_latent, i)
                 if trace is not None:

@@ -7,6 +7,9 @@ pipeline is one elementwise HIP kernel (``fused_cfg_step``): the eta = 0 v / eps
 ``cfg_ddim_update``, everything else ``step`` supports (eta > 0, clip_sample, prediction_type="sample",
 use_clipped_model_output) on ``cfg_ddim_step``; with ``guidance_rescale`` (arXiv 2305.08891, section 3.4) a statistics launch
 precedes ``cfg_ddim_step``.
+
+``DPMSolverMultistepScheduler`` (DPM-Solver++ 2M, arXiv 2211.01095) is the second-order sampler on the same tables and timestep grid;
+its update runs on ``cfg_multistep_step`` / ``cfg_multistep_step_windows`` with an fp32 x0 history per latent.
 """
 import math
 from dataclasses import dataclass
@@ -296,3 +299,157 @@ class DDIMScheduler:
         return kernels.cfg_ddim_step_windows(preds.contiguous(), x, noise.to(x.dtype).contiguous() if eta > 0 else None, starts,
                                              weights, self.kernel_mode(use_clipped_model_output), coefs, coef_dev=coef_dev, **_rescale_kw(guidance_rescale),
                                              **_ring_kw(ring))
+
+
+class DPMSolverMultistepScheduler(DDIMScheduler):
+    """DPM-Solver++ 2M (arXiv 2211.01095, algorithm 2: data prediction, multistep, order <= 2) on DDIMScheduler's grid: the same
+    tables, ``set_timesteps``, predecessor ``t - num_train_timesteps // N`` (below 0: ``final_alpha_cumprod``), ``add_noise``,
+    ``get_velocity``, ``noise_coefficients``, ``keep_coefficients``, ``timesteps_for_strength`` and ``kernel_mode``, all inherited.  The
+    eager ``step`` below is the definition; nothing is claimed about bit parity with diffusers' class of the same name.
+
+    With a = alphas_cumprod[t]: alpha = sqrt(a), sigma = sqrt(1 - a), lambda = ln(alpha / sigma); primed values belong to the
+    predecessor of t, lambda_old to the timestep run before t.  Step i of a run's timestep list ``steps``:
+
+        x0  = prediction-type conversion of (model output, x), clamped to [-1, 1] with clip_sample
+        out = cx x + c0 x0 + c1 x0_old,      history <- x0
+        sigma' == 0:    cx = 0, c0 = 1, c1 = 0
+        else h = lambda' - lambda, A = -alpha' expm1(-h), cx = sigma' / sigma
+          first order  (i == 0, i == len(steps) - 1, solver_order == 1):   c0 = A, c1 = 0
+          second order (otherwise), r = (lambda - lambda_old) / h:          c0 = A (1 + 1 / (2 r)), c1 = -A / (2 r)
+
+    The coefficients depend on the run (which timestep came before, first and last step), not on t alone: ``multistep_coefficients(steps,
+    i, guidance)`` is a pure function of both, and ``begin_run(steps)`` tells ``step`` / ``step_coefficients`` / ``fused_cfg_step`` which
+    run a timestep is looked up in (``set_timesteps`` begins the whole schedule).  The x0 history belongs to the latent, not to the
+    scheduler: ``new_history(latent)`` per latent, passed as ``history=``; it is fp32 and updated in place.  A step with c1 == 0 does
+    not read it, so it needs no reset between runs."""
+    order = 1
+
+    def __init__(self, *args, solver_order=2, algorithm_type="dpmsolver++", **kwargs):
+        if solver_order not in (1, 2):
+            raise ValueError(f"solver_order must be 1 or 2, got {solver_order!r}")
+        if algorithm_type != "dpmsolver++":
+            raise ValueError(f"algorithm_type {algorithm_type!r} is not implemented: only 'dpmsolver++' (the ODE solver; no SDE variant)")
+        super().__init__(*args, **kwargs)
+        self.config.update(solver_order=solver_order, algorithm_type=algorithm_type)
+        self._run_steps = None
+
+    @classmethod
+    def from_config(cls, config, **overrides):
+        """``pipe.scheduler = DPMSolverMultistepScheduler.from_config(pipe.scheduler.config)``: the constructor keywords of another
+        scheduler of this module, ``overrides`` on top."""
+        return cls(**{**dict(config), **overrides})
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        super().set_timesteps(num_inference_steps, device=device)
+        self.begin_run(self._timesteps_host)
+
+    def begin_run(self, steps):
+        """The timestep list of the run that follows (the pipeline calls it once it knows it: ``strength`` < 1 shortens it)."""
+        self._run_steps = [int(t) for t in steps]
+
+    def new_history(self, latent):
+        """The x0 history of one latent: zeros, float32, ``latent``'s shape and device.  One per latent that is stepped."""
+        return torch.zeros(latent.shape, dtype=torch.float32, device=latent.device)
+
+    def uses_step_kernel(self, eta=0.0, use_clipped_model_output=False, guidance_rescale=0.0):
+        """Always the six-coefficient kernel."""
+        return True
+
+    def _alpha_sigma_lambda(self, a):
+        alpha, sigma = _sqrt(a), _sqrt(1.0 - a)
+        return alpha, sigma, math.log(alpha / sigma)
+
+    def multistep_coefficients(self, steps, i, guidance=1.0):
+        """(guidance, sqrt(a_t), sqrt(1 - a_t), cx, c0, c1) of step ``i`` of the run's timestep list ``steps`` (see the class), in
+        fp64 from the fp32 ``alphas_cumprod``: the coefficient vector of ``kernels.cfg_multistep_step``.  A pure function of
+        (steps, i)."""
+        i = int(i)
+        if not 0 <= i < len(steps):
+            raise ValueError(f"multistep_coefficients: step {i} is not one of the {len(steps)} steps of the run")
+        a0 = float(self.alphas_cumprod[int(steps[0])])
+        if a0 <= 0.0:
+            raise ValueError(f"alphas_cumprod is 0 at the run's first timestep {int(steps[0])} (a zero-terminal-SNR table entered at its "
+                             f"last index): lambda = ln(alpha / sigma) is not finite there and DPM-Solver++ cannot start; use DDIMScheduler "
+                             f"for this schedule, or a step count whose first timestep lies below the last index")
+        a_t, a_prev = self._alphas(steps[i])
+        alpha, sigma, lam = self._alpha_sigma_lambda(a_t)
+        head = (float(guidance), alpha, sigma)
+        if a_prev >= 1.0:                       # sigma' = 0: the step lands on x0 (h is infinite)
+            return head + (0.0, 1.0, 0.0)
+        alpha_p, sigma_p, lam_p = self._alpha_sigma_lambda(a_prev)
+        h = lam_p - lam
+        A = -alpha_p * math.expm1(-h)
+        cx = sigma_p / sigma
+        if i == 0 or i == len(steps) - 1 or self.config.solver_order == 1:
+            return head + (cx, A, 0.0)
+        lam_old = self._alpha_sigma_lambda(float(self.alphas_cumprod[int(steps[i - 1])]))[2]
+        r = (lam - lam_old) / h
+        return head + (cx, A * (1.0 + 0.5 / r), -A * 0.5 / r)
+
+    def step_coefficients(self, timestep, eta=0.0, guidance=1.0):
+        """``multistep_coefficients`` of the step at ``timestep`` in the run ``begin_run`` named -- what the graphed steps upload.  A
+        timestep the run does not hold (the warm-up of a graphed step under ``strength`` < 1, whose numbers are dropped) gets the
+        first-order vector of that timestep."""
+        if eta != 0.0:
+            raise ValueError("DPMSolverMultistepScheduler has no stochastic variant (eta must be 0): use DDIMScheduler for eta > 0")
+        if self._run_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        t = int(timestep)
+        if t in self._run_steps:
+            return self.multistep_coefficients(self._run_steps, self._run_steps.index(t), guidance)
+        if float(self.alphas_cumprod[t]) <= 0.0:        # (no lambda there; the numbers are dropped: leave x as it is)
+            return (float(guidance), 0.0, 1.0, 1.0, 0.0, 0.0)
+        return self.multistep_coefficients([t], 0, guidance)
+
+    def step(self, model_output, timestep, sample, history=None, eta=0.0, return_dict=True, **kwargs):
+        """The eager definition, in torch ops on the tensors' device and in their dtype (fp64 for a reference): the update of the class
+        comment at ``timestep`` of the current run.  ``history``: this latent's x0 of the step before (``new_history``, or any float
+        tensor like ``sample``), overwritten with this step's x0; it may be None where the step is first order."""
+        _, sa, sb, cx, c0, c1 = self.step_coefficients(timestep, eta)
+        pt = self.config.prediction_type
+        if pt == "epsilon":
+            x0 = (sample - sb * model_output) / sa
+        elif pt == "sample":
+            x0 = model_output
+        elif pt == "v_prediction":
+            x0 = sa * sample - sb * model_output
+        else:
+            raise ValueError(f"prediction_type given as {pt} must be one of `epsilon`, `sample`, or `v_prediction`")
+        if self.config.clip_sample:
+            x0 = torch.clamp(x0, -1, 1)
+        prev = cx * sample + c0 * x0
+        if c1 != 0.0:
+            if history is None:
+                raise ValueError(f"step: the second-order step at timestep {int(timestep)} needs the history of the step before")
+            prev = prev + c1 * history.to(x0.dtype)
+        if history is not None:
+            history.copy_(x0)
+        prev = prev.to(sample.dtype)
+        return DDIMSchedulerOutput(prev_sample=prev, pred_original_sample=x0) if return_dict else (prev,)
+
+    def _kernel_args(self, who, timestep, guidance_scale, coef_dev, history, eta, noise, kwargs):
+        if eta != 0.0 or noise is not None:
+            raise ValueError(f"{who}: DPMSolverMultistepScheduler has no stochastic variant (eta must be 0): use DDIMScheduler for eta > 0")
+        if kwargs.pop("use_clipped_model_output", False):
+            raise ValueError(f"{who}: use_clipped_model_output has no meaning for DPM-Solver++ (the update uses x0 alone)")
+        if kwargs:
+            raise TypeError(f"{who}: unexpected keywords {sorted(kwargs)}")
+        if history is None:
+            raise ValueError(f"{who}: history= is required (scheduler.new_history(latent), one per latent)")
+        return (0.0,) * 6 if coef_dev is not None else self.step_coefficients(timestep, 0.0, guidance_scale)
+
+    def fused_cfg_step(self, pred_uncond, pred_text, guidance_scale, timestep, sample, coef_dev=None, *, history=None, eta=0.0, noise=None,
+                       guidance_rescale=0.0, **kwargs):
+        """CFG combine + the multistep update in one HIP kernel (``kernels.cfg_multistep_step``); ``history``: this latent's
+        ``new_history``, updated in place.  ``coef_dev``: device float32[6] = ``step_coefficients`` read by the kernel (graph replay)."""
+        coefs = self._kernel_args("fused_cfg_step", timestep, guidance_scale, coef_dev, history, eta, noise, kwargs)
+        return kernels.cfg_multistep_step(pred_uncond.contiguous(), pred_text.contiguous(), sample.contiguous(), history, self.kernel_mode(),
+                                          coefs, coef_dev=coef_dev, **_rescale_kw(guidance_rescale))
+
+    def fused_cfg_step_windows(self, preds, starts, weights, guidance_scale, timestep, sample, coef_dev=None, *, history=None, eta=0.0,
+                               noise=None, guidance_rescale=0.0, ring=False, **kwargs):
+        """``fused_cfg_step`` on the blend of sliding temporal context windows (``kernels.cfg_multistep_step_windows``; arguments of
+        ``DDIMScheduler.fused_cfg_step_windows``)."""
+        coefs = self._kernel_args("fused_cfg_step_windows", timestep, guidance_scale, coef_dev, history, eta, noise, kwargs)
+        return kernels.cfg_multistep_step_windows(preds.contiguous(), sample.contiguous(), history, starts, weights, self.kernel_mode(), coefs,
+                                                  coef_dev=coef_dev, **_rescale_kw(guidance_rescale), **_ring_kw(ring))

@@ -340,6 +340,39 @@ int im360_cfg_ddim_step_windows_ring_rescale(const void* pred, const void* x, co
                                              int mode, float phi, const void* ws, int64_t ws_floats, int dtype, void* stream,
                                              const void* coef_dev);
 
+/* ---- DPM-Solver++ 2M (arXiv 2211.01095, algorithm 2: data prediction, multistep, order <= 2) on the CFG combination, one
+ * elementwise pass.  Per element in fp32, with m = uncond + guidance * (cond - uncond) (times r of the guidance rescale when ws is
+ * given) and x0 = the conversion of im360_cfg_ddim_step for mode bits 0-1 (0 epsilon, 1 v_prediction, 2 sample), clamped to
+ * [-1, 1] with bit 2:
+ *   out  = T(cx * x + c0 * x0 + c1 * hist)        one rounding, at the store
+ *   hist = x0                                     fp32, in place, by the thread that read it
+ * cx, c0, c1: the linear form of the update, fp64 host math (DPMSolverMultistepScheduler.multistep_coefficients): first order
+ * cx = sigma'/sigma, c0 = -alpha' expm1(-h), c1 = 0; second order c0 (1 + 1/(2r)), c1 = -c0/(2r) with h, r of the paper.
+ * c1 == 0 means there is no history: hist is then not read (it may hold anything, NaN included) and only written.
+ * uncond / cond / x / out: n elements (n % 8 == 0) of the same 16-bit dtype; hist: device float[n]; all 16-byte aligned.
+ * Mode 3 and mode bit 3 (use_clipped_model_output, which has no meaning here) are refused.
+ * phi, ws, ws_floats: the guidance rescale of im360_cfg_ddim_step_rescale, ws written by im360_cfg_rescale_stats for the same
+ * uncond / cond / n / guidance; ws == NULL selects the kernel without it (phi must then be 0).
+ * coef_dev (optional): device float[6] = (guidance, sqrt_a, sqrt_b, cx, c0, c1) overriding the scalars (hipGraph replay): the
+ * length of im360_cfg_ddim_step's vector, so one buffer and one upload path serve both samplers.
+ * Replaces: nothing in the reference (its pipeline has only DDIM); the CFG combine of pipeline_animation_inference_dual.py:791-800
+ *   followed by algorithm 2 of arXiv 2211.01095. */
+int im360_cfg_multistep_step(const void* uncond, const void* cond, const void* x, void* hist, void* out, int64_t n, float guidance,
+                             float sqrt_a, float sqrt_b, float cx, float c0, float c1, int mode, float phi, const void* ws,
+                             int64_t ws_floats, int dtype, void* stream, const void* coef_dev);
+
+/* im360_cfg_multistep_step on the per-frame blend of sliding temporal context windows: pred, start, weight, nW, outer, F, L, inner
+ * and the blend m of im360_cfg_ddim_step_windows; wrap = 0: the windows lie on a line (preconditions of that entry point), wrap = F:
+ * on a ring of F frames (those of im360_cfg_ddim_step_windows_ring); any other wrap is refused.  x / out [outer, F, inner] 16-bit,
+ * hist device float[outer * F * inner] in the same layout, 4-byte aligned.  16-byte lanes when inner % 8 == 0 and pred, x, hist and
+ * out are 16-byte aligned, a scalar path otherwise.  ws: written by im360_cfg_rescale_stats_windows(_ring) for the same clip, or NULL.
+ * nW = 1, start = {0}, weight all 1, L = F gives im360_cfg_multistep_step's out and hist bit for bit.
+ * Replaces: nothing in the reference (no temporal windows, no multistep solver); arXiv 2211.01095, algorithm 2. */
+int im360_cfg_multistep_step_windows(const void* pred, const void* x, void* hist, void* out, const void* start, const void* weight,
+                                     int nW, int64_t outer, int64_t F, int64_t L, int64_t inner, int64_t wrap, float guidance,
+                                     float sqrt_a, float sqrt_b, float cx, float c0, float c1, int mode, float phi, const void* ws,
+                                     int64_t ws_floats, int dtype, void* stream, const void* coef_dev);
+
 /* ---- start latents of a run that begins from a given clip (AnimationPipeline init_latents / init_video, strength < 1), one launch:
  *   out_pano[c, f, p]    = T(sqrt_a * x0[c, f, p] + sqrt_b * noise[f, c, p])        fp32, one rounding, at the store
  *   out_pers[m, c, f, q] = ok[m, q] ? out_pano[c, f, idx[m, q]] : 0                 the gather of the ROUNDED panorama start, bit for bit

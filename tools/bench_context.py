@@ -6,6 +6,9 @@ synchronise; and the blend + CFG + DDIM kernel alone next to cfg_ddim_step_kerne
 device events, with the bytes each has to move computed from the shapes.  Prints one line of JSON (and writes it to --out).
     python tools/bench_context.py [--steps 3] [--rounds 3] [--kernel-iters 200] [--out profiles/context_windows.json]
     python tools/bench_context.py --kernel-only       # skip the two whole steps
+    python tools/bench_context.py --sampler dpmpp2m   # any of the modes with scheduler.DPMSolverMultistepScheduler (DPM-Solver++ 2M) instead of
+                                                      # DDIM: the captured steps own their x0 histories, and the two kernels timed alone are
+                                                      # cfg_multistep_step_windows / cfg_multistep_step at a second-order timestep
     python tools/bench_context.py --loop [--passes 2] # the looping clip: the ring plan's captured step next to the linear plan's (same F, L,
                                                       # overlap; ms per step and per window), and the ring entry point of the blend kernel next to
                                                       # the linear one on the SAME non-wrapping tables and on the ring's own; every measurement is
@@ -39,7 +42,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from imagine360_amd import configs, kernels, synthetic  # noqa: E402
 from imagine360_amd.context import WindowPlan, coverage, ip_cache_slots  # noqa: E402
-from imagine360_amd.scheduler import DDIMScheduler  # noqa: E402
+from imagine360_amd.scheduler import DDIMScheduler, DPMSolverMultistepScheduler  # noqa: E402
 
 FRAMES, LENGTH, OVERLAP = 48, 16, 4
 PANO_HW, PERS_HW, PERS_PX = (64, 128), (32, 32), 256
@@ -67,6 +70,11 @@ def time_kernels(sch, plan, sample, iters, rounds=5, ring_plan=None):
     u, c = (torch.randn(sample.shape, device=sample.device).to(sample.dtype) for _ in range(2))
     fns = dict(windows=lambda: kernels.cfg_ddim_step_windows(preds, sample, None, plan.starts_dev, plan.weights, mode, coefs),
                plain=lambda: kernels.cfg_ddim_step(u, c, sample, None, mode, coefs))
+    if hasattr(sch, "new_history"):               # --sampler dpmpp2m: a second-order step (history read and written)
+        assert ring_plan is None, "--sampler dpmpp2m times the linear and the plain kernel"
+        hist = sch.new_history(sample)
+        fns = dict(windows=lambda: kernels.cfg_multistep_step_windows(preds, sample, hist, plan.starts_dev, plan.weights, mode, coefs),
+                   plain=lambda: kernels.cfg_multistep_step(u, c, sample, hist, mode, coefs))
     if ring_plan is not None:
         assert len(ring_plan) == len(plan) and ring_plan.length == plan.length        # the same prediction buffer serves all three
         fns = dict(linear=fns["windows"],
@@ -308,7 +316,7 @@ def hires_bench(args, sch, dev, dt):
     mv = configs.build_mv_model(1, device=dev, dtype=dt, xformers=True)
     mv.dual_stream, mv.warp_streams = True, True
     vae = configs.build_vae(1, device=dev, dtype=dt)
-    pipe = AnimationPipeline(vae, None, None, mv.unet, mv.pano_unet, mv, DDIMScheduler(**configs.NOISE_SCHEDULER_KWARGS), None, "SAM").to(dev)
+    pipe = AnimationPipeline(vae, None, None, mv.unet, mv.pano_unet, mv, type(sch)(**configs.NOISE_SCHEDULER_KWARGS), None, "SAM").to(dev)
     pipe._no_progress = True
     vbs = {hw: synthetic.video_batch(frames=frames, pano_hw=(hw[0] * 8, hw[1] * 8), seed=1) for hw in (small, big)}
     cond = synthetic.conditioning(frames=max(frames, 16), seed=1)
@@ -369,7 +377,7 @@ def strength_bench(args, sch, dev, dt):
     mv = configs.build_mv_model(1, device=dev, dtype=dt, xformers=True)
     mv.dual_stream, mv.warp_streams = True, True
     vae = configs.build_vae(1, device=dev, dtype=dt)
-    pipe = AnimationPipeline(vae, None, None, mv.unet, mv.pano_unet, mv, DDIMScheduler(**configs.NOISE_SCHEDULER_KWARGS), None, "SAM").to(dev)
+    pipe = AnimationPipeline(vae, None, None, mv.unet, mv.pano_unet, mv, type(sch)(**configs.NOISE_SCHEDULER_KWARGS), None, "SAM").to(dev)
     pipe._no_progress = True
     vb = synthetic.video_batch(frames=frames, pano_hw=(PANO_HW[0] * 8, PANO_HW[1] * 8), seed=1)
     cond = synthetic.conditioning(frames=max(frames, 16), seed=1)
@@ -443,13 +451,14 @@ def main():
     ap.add_argument("--init-scale", type=int, default=None,
                     help="with --strength: the hi-res pass -- a first call at 1/N of --pano-hw, a second call at --pano-hw from its latent -- next to one call from pure noise at --pano-hw")
     ap.add_argument("--pano-hw", type=int, nargs=2, default=[128, 256], metavar=("H", "W"), help="--init-scale: latent size of the full-size run (default: cfg5)")
+    ap.add_argument("--sampler", choices=["ddim", "dpmpp2m"], default="ddim", help="the scheduler of every step and call (dpmpp2m: DPM-Solver++ 2M)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_context.py measures on the MI355X; there is nothing to time without one"
     torch.set_grad_enabled(False)
     kernels.lib()
     dev, dt = torch.device("cuda", 0), torch.bfloat16
-    sch = DDIMScheduler(**configs.NOISE_SCHEDULER_KWARGS)
+    sch = (DPMSolverMultistepScheduler if args.sampler == "dpmpp2m" else DDIMScheduler)(**configs.NOISE_SCHEDULER_KWARGS)
     sch.set_timesteps(25)
     ts_host = [int(t) for t in sch._timesteps_host]
     if args.init_scale is not None:
@@ -461,7 +470,7 @@ def main():
         return emit(loop_bench(args, sch, dev, dt, ts_host), args.out)
     plan = WindowPlan(FRAMES, LENGTH, OVERLAP, "pyramid", dev)
     res = dict(tool="bench_context", frames=FRAMES, context_frames=LENGTH, context_overlap=OVERLAP, windows=plan.starts,
-               pano_hw=PANO_HW, pers_hw=PERS_HW, dtype="bfloat16", device=torch.cuda.get_device_name(0))
+               pano_hw=PANO_HW, pers_hw=PERS_HW, dtype="bfloat16", device=torch.cuda.get_device_name(0), sampler=args.sampler)
 
     pers = torch.randn(1, 20, 4, FRAMES, *PERS_HW, device=dev).to(dt)
     nbytes = kernel_bytes(pers, plan)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Per-kernel micro-benchmarks at BASELINE cfg2 shapes (run on the MI355X):
 
-    python tools/bench_kernels.py [attn] [conv] [temporal] [ln] [gn] [--iters N]
+    python tools/bench_kernels.py [attn] [conv] [temporal] [ln] [gn] [sampler_step] [--iters N]
 
 Prints achieved TFLOP/s (MFMA kernels, vs 2500 dense bf16) or GB/s (HBM kernels, vs 8000) per shape.
 Usable under `rocprofv3 --pmc ...` for counters of one kernel class.
@@ -445,6 +445,34 @@ def bench_xattn(iters):
         K.tuning_set("attn_x", 3)
         d = ((outs[1] - outs[0]).norm() / outs[0].norm()).item()
         print(f"xattn {name:8s} M={B * Nq:7d} H={H:2d}: " + " | ".join(row) + f" | rel diff vs generic {d:.2e}, wide == narrow stores: {bool((outs[1] == outs[2]).all())}, ring == registers: {bool((outs[1] == outs[3]).all())}")
+
+
+def bench_sampler_step(iters):
+    """The fused CFG + scheduler-update launches on the two latents of cfg2 (16 frames; panorama 64 x 128, 20 views of 32 x 32): the DDIM
+    step kernel next to the DPM-Solver++ 2M one (first order: the history is only written; second order: read and written), device events,
+    with the bytes each launch has to move."""
+    from imagine360_amd import configs
+    from imagine360_amd.scheduler import DDIMScheduler, DPMSolverMultistepScheduler
+    ddim, dpm = DDIMScheduler(**configs.NOISE_SCHEDULER_KWARGS), DPMSolverMultistepScheduler(**configs.NOISE_SCHEDULER_KWARGS)
+    ddim.set_timesteps(25), dpm.set_timesteps(25)
+    t = ddim._timesteps_host[8]
+    steps = dpm._timesteps_host
+    for name, shape in (("pano", (1, 4, 16, 64, 128)), ("pers", (1, 20, 4, 16, 32, 32))):
+        u, c, x = rn(*shape), rn(*shape), rn(*shape)
+        h = torch.zeros(shape, dtype=torch.float32, device=DEV)
+        n = x.numel()
+        mode = ddim.kernel_mode()
+        cd = ddim.step_coefficients(t, 0.0, 7.5)
+        c1, c2 = dpm.multistep_coefficients(steps, 0, 7.5), dpm.multistep_coefficients(steps, 8, 7.5)
+        rows = [("cfg_ddim_step", lambda: K.cfg_ddim_step(u, c, x, None, mode, cd), 8 * n),
+                ("cfg_multistep_step order 1", lambda: K.cfg_multistep_step(u, c, x, h, mode, c1), 12 * n),
+                ("cfg_multistep_step order 2", lambda: K.cfg_multistep_step(u, c, x, h, mode, c2), 16 * n)]
+        base = None
+        for label, fn, by in rows:
+            ts = sorted(timeit(fn, iters) for _ in range(5))
+            base = base or ts[0]
+            print(f"sampler_step {name} {n:8d} elements  {label:28s}: {ts[0] * 1e6:7.2f} us min {ts[2] * 1e6:7.2f} us median  "
+                  f"{by / 1e6:6.2f} MB  {by / ts[0] / 1e9:6.0f} GB/s  {ts[0] / base:4.2f}x cfg_ddim_step")
 
 
 if __name__ == "__main__":
