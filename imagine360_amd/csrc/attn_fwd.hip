@@ -874,58 +874,81 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(RAG2 &
     if constexpr (QDMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-// Rejected / ablation variants (knobs attn_dbg, attn_hl, attn_hg, attn_ds, attn_w3 = 2) are compiled only into `make ablate`
-// builds (-DIM360_ABLATE; im360_build_flags() bit 0): in the shipped library those knobs read as 0.
-#ifdef IM360_ABLATE
-#define IM360_ABL_KNOB(k) knob(k)
-#else
-#define IM360_ABL_KNOB(k) 0
-#endif
+// ---- host side: the instantiations by name ------------------------------------------------------------------------------
+// A launch site names a variant; attn_kernel spells attn_fwd_kernel's flags out once, in the kernel's parameter order.
+struct AttnVariant {
+    static constexpr bool bias = false, two_set = false, packed = false, bias_lds = false, dot_sums = false, single_tile = false;
+    static constexpr bool head_groups = false, three_waves = false;
+    static constexpr int abl = 0;
+    static constexpr bool four_waves_only = false;       // the library has no one- / two-wave form of the variant
+};
+template <bool HAS_BIAS> struct Plain : AttnVariant { static constexpr bool bias = HAS_BIAS; };
+struct PackedBias : AttnVariant { static constexpr bool bias = true, packed = true; };                     // d = 32, fp16 bias matrices (WarpAttn)
+struct SingleTile : AttnVariant { static constexpr bool single_tile = true; };                             // d = 64, all keys in one LDS tile
+struct ThreeWaves : AttnVariant { static constexpr bool three_waves = true, four_waves_only = true; };     // d = 64, three waves per SIMD
+struct TwoSet : AttnVariant { static constexpr bool two_set = true; };                                     // d = 64, two key / value sets, two passes
+template <typename T, int D, int NW, int QB, typename V>
+constexpr auto attn_kernel = attn_fwd_kernel<T, D, NW, QB, V::bias, V::two_set, V::packed, V::bias_lds, V::dot_sums, V::single_tile, V::abl, V::head_groups, V::three_waves>;
 
+// the resident two-set kernel: the model's shape (77 + 64 keys: five real 16-key chunks, second set unmasked), the general instance, and
+// the model's shape on twelve-wave workgroups with the queries through LDS rings; WIDE = 16-byte stores
+template <typename T, bool WIDE> constexpr auto xattn_model_kernel = xattn_resident_kernel<T, 3, 5, 2, false, WIDE>;
+template <typename T, bool WIDE> constexpr auto xattn_general_kernel = xattn_resident_kernel<T, 3, 6, 2, true, WIDE>;
+template <typename T> constexpr auto xattn_ring_kernel = xattn_resident_kernel<T, 3, 5, 2, false, true, 12, true>;
+
+// waves per workgroup: one 32-query block each
+static inline int attn_nw(int Nq) { return Nq <= 32 ? 1 : (Nq <= 64 ? 2 : 4); }
+
+// One launch of variant V at QB query blocks per wave: run-time nw in {1, 2, 4} -> NW and the block size.  Two blocks per wave, and the
+// variants marked four_waves_only, exist for four-wave workgroups alone: nothing else is instantiated for them and another nw is refused.
+template <typename T, int D, int QB, typename V>
+static int launch_variant(const AttnParams& p, dim3 grid, int nw, hipStream_t stream) {
+    auto launch = [&](auto n) {
+        constexpr int NW = decltype(n)::value;
+        hipLaunchKernelGGL((attn_kernel<T, D, NW, QB, V>), grid, dim3(NW * 64), 0, stream, p);
+    };
+    bool found;
+    if constexpr (QB == 2 || V::four_waves_only) found = with_const<4>(nw, launch);
+    else found = with_const<1, 2, 4>(nw, launch);
+    if (!found) {
+        im360_set_error("attn_fwd: this kernel has no %d-wave form", nw);
+        return IM360_ERR_UNSUPPORTED;
+    }
+    return im360_launch_status();
+}
+
+// ---- rejected / ablation variants (`make ablate`, -DIM360_ABLATE; knobs attn_dbg, attn_hl, attn_hg, attn_ds, attn_w3 = 2): they live in
+//      attn_ablate.hip and see this file's kernels and launch_variant.  launch_attn_b asks that file's ablate_*() in front of its shipped
+//      paths: constant "not taken" in the default build
+#define IM360_ATTN_FWD_INCLUDES_ABLATE 1
+#include "attn_ablate.hip"
+
+// One key / value set.  The path is chosen once, in this order: packed bias (d = 32) -> pipelined (attn_pipe.hip) -> single tile ->
+// three waves per SIMD -> plain.
 template <typename T, int D, bool HAS_BIAS>
 static int launch_attn_b(AttnParams p, hipStream_t stream) {
-    const int nw = p.Nq <= 32 ? 1 : (p.Nq <= 64 ? 2 : 4);
+    const int nw = attn_nw(p.Nq);
     // Query blocks per wave.  Two blocks share each K fragment read and halve the K/V staging per query.  Measured
     // (tools/bench_kernels.py attn_variants): WarpAttn level 1 (d = 32 + bias, 222 VGPRs, no scratch) 1.62 vs 1.87 ms,
     // panorama level-0 self-attention (d = 64, 48 B of scratch) 2.75 vs 3.10 ms = 1.0 PF/s, perspective level 0 1.09 vs
     // 1.19 ms; a tie on small grids, where one block per wave keeps more workgroups in flight.  Knob attn_qb: 0 = this
     // rule, 1 / 2 = force.
     const int qb_env = knob(KNOB_ATTN_QB);       // tuning override
-    int qb = 1;
-    if (nw == 4 && (qb_env == 2 || (qb_env == 0 && (long)p.B * p.H * ((p.Nq + 255) / 256) >= 1024))) qb = 2;
+    const bool two_blocks = nw == 4 && (qb_env == 2 || (qb_env == 0 && (long)p.B * p.H * ((p.Nq + 255) / 256) >= 1024));
     // Round 3: at d = 64 without a bias, ONE block per wave at THREE waves per SIMD (148 registers, no scratch; three 43 KB
     // workgroups per CU) beats the two-block form on every self-attention shape of the step: panorama level 0 2.99 -> 2.95 ms,
     // perspective level 0 1.10 -> 1.07, level 1 0.414 -> 0.397 / 0.218 -> 0.209, panorama level 2 0.072 -> 0.064
     // (bench_kernels.py attn_w3; one block at two waves per SIMD: 3.14 / 1.19).  Knob attn_w3 0 restores the rule above.
-    const bool w3 = !HAS_BIAS && D == 64 && nw == 4 && qb_env != 2 && knob(KNOB_ATTN_W3) != 0 && IM360_ABL_KNOB(KNOB_ATTN_DBG) == 0 && !(qb_env == 1 && IM360_ABL_KNOB(KNOB_ATTN_DS));
-    if (w3) qb = 1;
+    const bool w3 = !HAS_BIAS && D == 64 && nw == 4 && qb_env != 2 && knob(KNOB_ATTN_W3) != 0 && !ablate_no_w3(qb_env);
+    const int qb = (two_blocks && !w3) ? 2 : 1;
     p.nqt = (p.Nq + 32 * nw * qb - 1) / (32 * nw * qb);
-    const long nblk = (long)p.B * p.H * p.nqt;
-    if (nblk > 0x7fffffffL) {
-        im360_set_error("attn_fwd: %ld workgroups exceed the grid limit", nblk);
-        return IM360_ERR_ARG;
-    }
-    dim3 grid((unsigned)nblk, 1, 1);
+    dim3 grid;
+    int rc = attn_grid("attn_fwd", (long)p.B * p.H * p.nqt, grid);
+    if (rc) return rc;
     if constexpr (HAS_BIAS && D == 32) {
         if (p.bias_packed) {
-            if (nw == 1) hipLaunchKernelGGL((attn_fwd_kernel<T, D, 1, 1, true, false, true>), grid, dim3(64), 0, stream, p);
-            else if (nw == 2) hipLaunchKernelGGL((attn_fwd_kernel<T, D, 2, 1, true, false, true>), grid, dim3(128), 0, stream, p);
-#ifdef IM360_ABLATE
-            else if (qb == 1 && knob(KNOB_ATTN_W3) == 2) hipLaunchKernelGGL((attn_fwd_kernel<T, D, 4, 1, true, false, true, false, false, false, 0, false, true>), grid, dim3(256), 0, stream, p);      // A/B (attn_qb 1 + attn_w3 2): WarpAttn with one block per wave at three waves per SIMD -- 1.13 ms against 0.98 for the two-block form (which shares every K fragment and mask prefetch between its blocks) and 1.25 at two waves: off
-#endif
-            else if (qb == 1) hipLaunchKernelGGL((attn_fwd_kernel<T, D, 4, 1, true, false, true>), grid, dim3(256), 0, stream, p);
-#ifdef IM360_ABLATE
-            else if (knob(KNOB_ATTN_HL) == 2) hipLaunchKernelGGL((attn_fwd_kernel<T, D, 4, 2, true, false, true, true>), grid, dim3(256), 0, stream, p);      // A/B: mask rows through the wave's LDS patch (measured 6 % slower: the divergent fragment loads are not the limiter)
-            else if (knob(KNOB_ATTN_HG) && ((long)p.B * p.H) % 4 == 0 && (long)p.B * p.H * ((p.Nq + 63) / 64) / 4 <= 0x7fffffffL) {
-                // head groups: four (batch, head) pairs per workgroup over the same 64 query rows
-                dim3 hgrid((unsigned)((long)p.B * p.H / 4 * ((p.Nq + 63) / 64)), 1, 1);
-                hipLaunchKernelGGL((attn_fwd_kernel<T, D, 4, 2, true, false, true, false, false, false, 0, true>), hgrid, dim3(256), 0, stream, p);
-            }
-            else if (knob(KNOB_ATTN_DS)) hipLaunchKernelGGL((attn_fwd_kernel<T, D, 4, 2, true, false, true, false, true>), grid, dim3(256), 0, stream, p);
-#endif
-            else hipLaunchKernelGGL((attn_fwd_kernel<T, D, 4, 2, true, false, true>), grid, dim3(256), 0, stream, p);
-            IM360_CHECK_LAUNCH();
-            return IM360_OK;
+            if (nw == 4 && ablate_packed<T>(p, grid, qb, stream, rc)) return rc;
+            return qb == 2 ? launch_variant<T, D, 2, PackedBias>(p, grid, nw, stream) : launch_variant<T, D, 1, PackedBias>(p, grid, nw, stream);
         }
     }
     if (p.bias_packed) {
@@ -934,123 +957,113 @@ static int launch_attn_b(AttnParams p, hipStream_t stream) {
     }
     if constexpr (!HAS_BIAS && D == 64) {
         // software-pipelined kernel (attn_pipe.hip; knob attn_pipe): the self-attention shapes with whole 64-key tiles
-        if (nw == 4 && IM360_ABL_KNOB(KNOB_ATTN_DBG) == 0) {
-            const int rc = launch_attn_pipe(p, std::is_same<T, __bf16>::value ? 0 : 1, stream);
+        if (nw == 4 && !ablate_no_pipe()) {
+            rc = launch_attn_pipe(p, std::is_same<T, __bf16>::value ? 0 : 1, stream);
             if (rc != 1) return rc;
         }
+        if (p.Nk <= KVB && qb == 1 && knob(KNOB_ATTN_ONE)) return launch_variant<T, D, 1, SingleTile>(p, grid, nw, stream);
+        if (w3) return launch_variant<T, D, 1, ThreeWaves>(p, grid, nw, stream);
     }
-    if constexpr (!HAS_BIAS && D == 64) {
-        if (p.Nk <= KVB && qb == 1 && knob(KNOB_ATTN_ONE)) {
-            if (nw == 1) hipLaunchKernelGGL((attn_fwd_kernel<T, D, 1, 1, false, false, false, false, false, true>), grid, dim3(64), 0, stream, p);
-            else if (nw == 2) hipLaunchKernelGGL((attn_fwd_kernel<T, D, 2, 1, false, false, false, false, false, true>), grid, dim3(128), 0, stream, p);
-            else hipLaunchKernelGGL((attn_fwd_kernel<T, D, 4, 1, false, false, false, false, false, true>), grid, dim3(256), 0, stream, p);
-            IM360_CHECK_LAUNCH();
-            return IM360_OK;
-        }
-    }
-    if constexpr (!HAS_BIAS && D == 64) {
-        if (w3 && !(p.Nk <= KVB && knob(KNOB_ATTN_ONE))) {
-            hipLaunchKernelGGL((attn_fwd_kernel<T, D, 4, 1, false, false, false, false, false, false, 0, false, true>), grid, dim3(256), 0, stream, p);
-            IM360_CHECK_LAUNCH();
-            return IM360_OK;
-        }
-    }
-    if (nw == 1) hipLaunchKernelGGL((attn_fwd_kernel<T, D, 1, 1, HAS_BIAS>), grid, dim3(64), 0, stream, p);
-    else if (nw == 2) hipLaunchKernelGGL((attn_fwd_kernel<T, D, 2, 1, HAS_BIAS>), grid, dim3(128), 0, stream, p);
-#ifdef IM360_ABLATE
-    else if (qb == 1 && knob(KNOB_ATTN_DS)) hipLaunchKernelGGL((attn_fwd_kernel<T, D, 4, 1, HAS_BIAS, false, false, false, true>), grid, dim3(256), 0, stream, p);
-#endif
-    else if (qb == 1) hipLaunchKernelGGL((attn_fwd_kernel<T, D, 4, 1, HAS_BIAS>), grid, dim3(256), 0, stream, p);
-#ifdef IM360_ABLATE
-    else if (!HAS_BIAS && D == 64 && knob(KNOB_ATTN_DBG)) {
-        if constexpr (!HAS_BIAS && D == 64) {
-            switch (knob(KNOB_ATTN_DBG)) {
-                case 1: hipLaunchKernelGGL((attn_fwd_kernel<T, D, 4, 2, false, false, false, false, false, false, 1>), grid, dim3(256), 0, stream, p); break;
-                case 2: hipLaunchKernelGGL((attn_fwd_kernel<T, D, 4, 2, false, false, false, false, false, false, 2>), grid, dim3(256), 0, stream, p); break;
-                case 4: hipLaunchKernelGGL((attn_fwd_kernel<T, D, 4, 2, false, false, false, false, false, false, 4>), grid, dim3(256), 0, stream, p); break;
-                case 6: hipLaunchKernelGGL((attn_fwd_kernel<T, D, 4, 2, false, false, false, false, false, false, 6>), grid, dim3(256), 0, stream, p); break;
-                case 7: hipLaunchKernelGGL((attn_fwd_kernel<T, D, 4, 2, false, false, false, false, false, false, 7>), grid, dim3(256), 0, stream, p); break;
-                case 8: hipLaunchKernelGGL((attn_fwd_kernel<T, D, 4, 2, false, false, false, false, false, false, 8>), grid, dim3(256), 0, stream, p); break;
-                default: hipLaunchKernelGGL((attn_fwd_kernel<T, D, 4, 2, false, false, false, false, false, false, 15>), grid, dim3(256), 0, stream, p); break;
-            }
-        }
-    }
-    else if (knob(KNOB_ATTN_DS)) hipLaunchKernelGGL((attn_fwd_kernel<T, D, 4, 2, HAS_BIAS, false, false, false, true>), grid, dim3(256), 0, stream, p);
-#endif
-    else hipLaunchKernelGGL((attn_fwd_kernel<T, D, 4, 2, HAS_BIAS>), grid, dim3(256), 0, stream, p);
-    IM360_CHECK_LAUNCH();
-    return IM360_OK;
+    if (nw == 4 && ablate_plain<T, D, HAS_BIAS>(p, grid, qb, stream, rc)) return rc;
+    return qb == 2 ? launch_variant<T, D, 2, Plain<HAS_BIAS>>(p, grid, nw, stream) : launch_variant<T, D, 1, Plain<HAS_BIAS>>(p, grid, nw, stream);
 }
 
+// Two key / value sets, both resident in LDS (xattn_resident_kernel; head dim 64).  Returns IM360_OK, an error, or 1 when the shape is not one
+// it takes (the caller then falls back to the generic two-pass kernel).
+// Knob attn_x: 1 = default, 2 = the same with 8-byte stores, 0 = the generic two-pass kernel
+template <typename T>
+static int launch_xattn_resident(AttnParams q, hipStream_t stream) {
+    const int xk = knob(KNOB_ATTN_X);
+    if (!(xk && q.Nk > 64 && q.Nk <= 96 && q.Nk2 > 32 && q.Nk2 <= 64 && (q.o_rs % 8) == 0 && (q.o_bs % 8) == 0 &&
+          ((uintptr_t)q.out % 16) == 0 && q.B % q.kv_group == 0 && q.Nq % 32 == 0))
+        return 1;
+    q.x_nqb = (q.Nq + 31) / 32;
+    q.x_bpp = q.kv_group * q.x_nqb;
+    q.x_total = (long)(q.B / q.kv_group) * q.H * q.x_bpp;
+    // the model's shape (77 + 64 keys: five real 16-key chunks, second set unmasked) or the general instance
+    const bool model_shape = q.Nk <= 80 && q.Nk2 == 64;
+    // knob 3: twelve-wave workgroups (one per CU) whose waves fetch their query blocks through private LDS rings
+    // (global_load_lds, two blocks ahead); needs 16-byte aligned query rows
+    const bool ring = xk == 3 && model_shape && (q.q_rs % 8) == 0 && (q.q_bs % 8) == 0 && ((uintptr_t)q.q % 16) == 0 && q.x_total >= 12 * 256;
+    // up to 48 query blocks (12 per wave) per four-wave workgroup -- the pair's 36 KB of K / V are then staged for 384 KB
+    // of Q / O, with enough workgroups left for the dispatcher to level the tail -- and no fewer than 8 on small problems,
+    // which would otherwise leave CUs idle (K / V come from the L2 there); the ring variant: 12 blocks per wave likewise
+    long per = q.x_total / 1024;
+    per = per < 8 ? 8 : (per > 48 ? 48 : per);
+    long g = (q.x_total + per - 1) / per;
+    if (ring) {
+        // one workgroup per CU: a whole number of rounds of <= 144 blocks (12 per wave) each
+        // (the CU count itself; conv3x3.hip's persistent_grid() keeps another value, rounded down to whole XCDs and private to that file)
+        static const int ncu = [] {
+            int dev = 0, n = 0;
+            if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 256;
+            return n > 0 ? n : 256;
+        }();
+        g = (long)ncu * ((q.x_total + 144L * ncu - 1) / (144L * ncu));
+    }
+    dim3 xgrid;
+    if (const int rc = attn_grid("attn_fwd2", g < 1 ? 1 : g, xgrid)) return rc;
+    if (ring) {
+        hipLaunchKernelGGL((xattn_ring_kernel<T>), xgrid, dim3(768), 0, stream, q);
+    } else {
+        with_bool(xk != 2, [&](auto wide) {
+            constexpr bool WIDE = decltype(wide)::value;
+            if (model_shape) hipLaunchKernelGGL((xattn_model_kernel<T, WIDE>), xgrid, dim3(256), 0, stream, q);
+            else hipLaunchKernelGGL((xattn_general_kernel<T, WIDE>), xgrid, dim3(256), 0, stream, q);
+        });
+    }
+    return im360_launch_status();
+}
+
+// two sets: resident, else the generic two-pass kernel; one set: with / without a bias
 template <typename T, int D>
 static int launch_attn(const AttnParams& p, hipStream_t stream) {
-    if (p.k2) {
-        if constexpr (D == 64) {
-            AttnParams q = p;
-            // both sets resident in LDS (knob attn_x: 1 = default, 2 = the same with 8-byte stores, 0 = the generic two-pass kernel)
-            const int xk = knob(KNOB_ATTN_X);
-            if (xk && q.Nk > 64 && q.Nk <= 96 && q.Nk2 > 32 && q.Nk2 <= 64 && (q.o_rs % 8) == 0 && (q.o_bs % 8) == 0 &&
-                ((uintptr_t)q.out % 16) == 0 && q.B % q.kv_group == 0 && q.Nq % 32 == 0) {
-                q.x_nqb = (q.Nq + 31) / 32;
-                q.x_bpp = q.kv_group * q.x_nqb;
-                q.x_total = (long)(q.B / q.kv_group) * q.H * q.x_bpp;
-                // the model's shape (77 + 64 keys: five real 16-key chunks, second set unmasked) or the general instance
-                const bool model_shape = q.Nk <= 80 && q.Nk2 == 64;
-                // knob 3: twelve-wave workgroups (one per CU) whose waves fetch their query blocks through private LDS rings
-                // (global_load_lds, two blocks ahead); needs 16-byte aligned query rows
-                const bool ring = xk == 3 && model_shape && (q.q_rs % 8) == 0 && (q.q_bs % 8) == 0 && ((uintptr_t)q.q % 16) == 0 && q.x_total >= 12 * 256;
-                // up to 48 query blocks (12 per wave) per four-wave workgroup -- the pair's 36 KB of K / V are then staged for 384 KB
-                // of Q / O, with enough workgroups left for the dispatcher to level the tail -- and no fewer than 8 on small problems,
-                // which would otherwise leave CUs idle (K / V come from the L2 there); the ring variant: 12 blocks per wave likewise
-                long per = q.x_total / 1024;
-                per = per < 8 ? 8 : (per > 48 ? 48 : per);
-                long g = (q.x_total + per - 1) / per;
-                if (ring) {
-                    // one workgroup per CU: a whole number of rounds of <= 144 blocks (12 per wave) each
-                    static const int ncu = [] {
-                        int dev = 0, n = 0;
-                        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 256;
-                        return n > 0 ? n : 256;
-                    }();
-                    g = (long)ncu * ((q.x_total + 144L * ncu - 1) / (144L * ncu));
-                }
-                if (g < 1) g = 1;
-                if (g > 0x7fffffffL) {
-                    im360_set_error("attn_fwd2: %ld workgroups exceed the grid limit", g);
-                    return IM360_ERR_ARG;
-                }
-                dim3 xgrid((unsigned)g, 1, 1);
-                if (ring) {
-                    hipLaunchKernelGGL((xattn_resident_kernel<T, 3, 5, 2, false, true, 12, true>), xgrid, dim3(768), 0, stream, q);
-                } else if (xk == 2) {
-                    if (model_shape) hipLaunchKernelGGL((xattn_resident_kernel<T, 3, 5, 2, false, false>), xgrid, dim3(256), 0, stream, q);
-                    else hipLaunchKernelGGL((xattn_resident_kernel<T, 3, 6, 2, true, false>), xgrid, dim3(256), 0, stream, q);
-                } else {
-                    if (model_shape) hipLaunchKernelGGL((xattn_resident_kernel<T, 3, 5, 2, false, true>), xgrid, dim3(256), 0, stream, q);
-                    else hipLaunchKernelGGL((xattn_resident_kernel<T, 3, 6, 2, true, true>), xgrid, dim3(256), 0, stream, q);
-                }
-                IM360_CHECK_LAUNCH();
-                return IM360_OK;
-            }
-            const int nw = q.Nq <= 32 ? 1 : (q.Nq <= 64 ? 2 : 4);
-            q.nqt = (q.Nq + 32 * nw - 1) / (32 * nw);
-            const long nblk = (long)q.B * q.H * q.nqt;
-            if (nblk > 0x7fffffffL) {
-                im360_set_error("attn_fwd: %ld workgroups exceed the grid limit", nblk);
-                return IM360_ERR_ARG;
-            }
-            dim3 grid((unsigned)nblk, 1, 1);
-            if (nw == 1) hipLaunchKernelGGL((attn_fwd_kernel<T, 64, 1, 1, false, true>), grid, dim3(64), 0, stream, q);
-            else if (nw == 2) hipLaunchKernelGGL((attn_fwd_kernel<T, 64, 2, 1, false, true>), grid, dim3(128), 0, stream, q);
-            else hipLaunchKernelGGL((attn_fwd_kernel<T, 64, 4, 1, false, true>), grid, dim3(256), 0, stream, q);
-            IM360_CHECK_LAUNCH();
-            return IM360_OK;
-        } else {
-            im360_set_error("attn_fwd2: two key/value sets need head dim 64");
-            return IM360_ERR_UNSUPPORTED;
-        }
+    if (!p.k2) return p.bias ? launch_attn_b<T, D, true>(p, stream) : launch_attn_b<T, D, false>(p, stream);
+    if constexpr (D == 64) {
+        int rc = launch_xattn_resident<T>(p, stream);
+        if (rc != 1) return rc;
+        AttnParams q = p;
+        const int nw = attn_nw(q.Nq);
+        q.nqt = (q.Nq + 32 * nw - 1) / (32 * nw);
+        dim3 grid;
+        if ((rc = attn_grid("attn_fwd", (long)q.B * q.H * q.nqt, grid))) return rc;
+        return launch_variant<T, 64, 1, TwoSet>(q, grid, nw, stream);
+    } else {
+        im360_set_error("attn_fwd2: two key/value sets need head dim 64");
+        return IM360_ERR_UNSUPPORTED;
     }
-    return p.bias ? launch_attn_b<T, D, true>(p, stream) : launch_attn_b<T, D, false>(p, stream);
+}
+
+// ---- entry points: what im360_attn_fwd and im360_attn_fwd2 check and fill alike --------------------------------------------
+struct AttnSet { const void* k; const void* v; int64_t Nk, k_bs, k_rs, v_bs, v_rs; };       // one key / value set as the ABI passes it
+// `x2` = im360_attn_fwd2's second set (nullptr: im360_attn_fwd): it joins the pointer, size, stride and alignment rules
+static int attn_common(AttnParams& p, const char* who, const void* q, const AttnSet& s, const AttnSet* x2, void* out,
+                       int64_t B, int64_t H, int64_t Nq, int64_t D, int64_t q_bs, int64_t q_rs, int64_t o_bs, int64_t o_rs,
+                       int64_t kv_group, float scale, float out_scale) {
+    IM360_CHECK_ARG(q && s.k && s.v && (!x2 || (x2->k && x2->v)) && out, "%s: null pointer", who);
+    if (x2) IM360_CHECK_ARG(B > 0 && H > 0 && Nq > 0 && s.Nk > 0 && x2->Nk > 0, "%s: empty problem", who);
+    else IM360_CHECK_ARG(B > 0 && H > 0 && Nq > 0 && s.Nk > 0, "%s: empty problem B=%ld H=%ld Nq=%ld Nk=%ld", who, (long)B, (long)H, (long)Nq, (long)s.Nk);
+    IM360_CHECK_ARG(kv_group >= 1, "%s: kv_group must be >= 1", who);
+    IM360_CHECK_ARG(D == 64 || (!x2 && D == 32), "%s: head dim %ld unsupported (%s)", who, (long)D, x2 ? "64" : "32, 64");
+    IM360_CHECK_ARG(B * H <= 0x7fffffffL, "%s: B*H too large", who);
+    auto rows16 = [](const AttnSet& a) { return (a.k_rs % 8) == 0 && (a.v_rs % 8) == 0 && (a.k_bs % 8) == 0 && (a.v_bs % 8) == 0; };
+    IM360_CHECK_ARG((q_rs % 8) == 0 && (q_bs % 8) == 0 && rows16(s) && (!x2 || rows16(*x2)) && (o_rs % 4) == 0 && (o_bs % 4) == 0,
+                    "%s: strides must keep 16-byte (q,k,v) / 8-byte (out) alignment", who);
+    auto base16 = [](const AttnSet& a) { return ((uintptr_t)a.k % 16) == 0 && ((uintptr_t)a.v % 16) == 0; };
+    IM360_CHECK_ARG(((uintptr_t)q % 16) == 0 && base16(s) && (!x2 || base16(*x2)) && ((uintptr_t)out % 8) == 0, "%s: misaligned base pointer", who);
+    p.q = q; p.k = s.k; p.v = s.v; p.out = out;
+    p.B = (int)B; p.H = (int)H; p.Nq = (int)Nq; p.Nk = (int)s.Nk; p.kv_group = (int)kv_group;
+    p.q_bs = q_bs; p.q_rs = q_rs; p.k_bs = s.k_bs; p.k_rs = s.k_rs; p.v_bs = s.v_bs; p.v_rs = s.v_rs; p.o_bs = o_bs; p.o_rs = o_rs;
+    p.scale_log2 = scale * LOG2E; p.out_scale = out_scale;
+    if (x2) { p.k2 = x2->k; p.v2 = x2->v; p.Nk2 = (int)x2->Nk; p.k2_bs = x2->k_bs; p.k2_rs = x2->k_rs; p.v2_bs = x2->v_bs; p.v2_rs = x2->v_rs; }
+    return IM360_OK;
+}
+// with_dtype with these two entry points' own wording
+template <typename F> static int with_attn_dtype(int dtype, const char* who, F&& f) {
+    if (dtype == 0) return f(TypeTag<__bf16>{});
+    if (dtype == 1) return f(TypeTag<_Float16>{});
+    im360_set_error("%s: dtype %d unsupported (0=bf16, 1=f16)", who, dtype);
+    return IM360_ERR_UNSUPPORTED;
 }
 
 }  // namespace im360
@@ -1063,17 +1076,8 @@ extern "C" __attribute__((visibility("default"))) int im360_attn_fwd(const void*
                               const void* bias_alt, const void* bias_sel,
                               const void* bias_blocks, const void* bias_blocks_alt, int64_t blocks_rs) {
     using namespace im360;
-    IM360_CHECK_ARG(q && k && v && out, "attn_fwd: null pointer");
-    IM360_CHECK_ARG(B > 0 && H > 0 && Nq > 0 && Nk > 0, "attn_fwd: empty problem B=%ld H=%ld Nq=%ld Nk=%ld",
-                    (long)B, (long)H, (long)Nq, (long)Nk);
-    IM360_CHECK_ARG(kv_group >= 1, "attn_fwd: kv_group must be >= 1");
-    IM360_CHECK_ARG(D == 32 || D == 64, "attn_fwd: head dim %ld unsupported (32, 64)", (long)D);
-    IM360_CHECK_ARG(B * H <= 0x7fffffffL, "attn_fwd: B*H too large");
-    IM360_CHECK_ARG((q_rs % 8) == 0 && (k_rs % 8) == 0 && (v_rs % 8) == 0 && (o_rs % 4) == 0 &&
-                    (q_bs % 8) == 0 && (k_bs % 8) == 0 && (v_bs % 8) == 0 && (o_bs % 4) == 0,
-                    "attn_fwd: strides must keep 16-byte (q,k,v) / 8-byte (out) alignment");
-    IM360_CHECK_ARG(((uintptr_t)q % 16) == 0 && ((uintptr_t)k % 16) == 0 && ((uintptr_t)v % 16) == 0 &&
-                    ((uintptr_t)out % 8) == 0, "attn_fwd: misaligned base pointer");
+    AttnParams p;
+    if (const int rc = attn_common(p, "attn_fwd", q, AttnSet{k, v, Nk, k_bs, k_rs, v_bs, v_rs}, nullptr, out, B, H, Nq, D, q_bs, q_rs, o_bs, o_rs, kv_group, scale, out_scale)) return rc;
     const int bias_packed = (dtype & 0x100) ? 1 : 0;       // dtype + 256: packed fp16 bias matrices (see the header)
     dtype &= 0xff;
     if (bias) {
@@ -1083,25 +1087,17 @@ extern "C" __attribute__((visibility("default"))) int im360_attn_fwd(const void*
                         "attn_fwd: packed bias needs Nk %% 8 == 0 and 16-byte aligned rows");
     }
     IM360_CHECK_ARG(bias || !bias_packed, "attn_fwd: packed-bias flag without a bias");
-    AttnParams p;
-    p.q = q; p.k = k; p.v = v; p.bias = bias; p.out = out;
-    p.bias_alt = bias_alt; p.bias_sel = (const int*)bias_sel;
     IM360_CHECK_ARG(!bias_sel || (bias && bias_alt && ((uintptr_t)bias_alt % 8) == 0), "attn_fwd: bias_sel needs bias and an aligned bias_alt");
     IM360_CHECK_ARG(!bias_blocks || (bias_packed && blocks_rs * 32 * 32 >= Nk && ((uintptr_t)bias_blocks % 4) == 0 && (!bias_alt || bias_blocks_alt)),
                     "attn_fwd: a block map needs a packed bias, ceil(Nk / 1024) <= blocks_rs words per row and one map per bias matrix");
+    p.bias = bias; p.bias_alt = bias_alt; p.bias_sel = (const int*)bias_sel; p.bias_rs = bias_rs;
     p.bias_blocks = (const uint32_t*)bias_blocks; p.bias_blocks_alt = (const uint32_t*)bias_blocks_alt; p.blocks_rs = (int)blocks_rs;
-    p.B = (int)B; p.H = (int)H; p.Nq = (int)Nq; p.Nk = (int)Nk; p.kv_group = (int)kv_group;
-    p.q_bs = q_bs; p.q_rs = q_rs; p.k_bs = k_bs; p.k_rs = k_rs; p.v_bs = v_bs; p.v_rs = v_rs;
-    p.o_bs = o_bs; p.o_rs = o_rs; p.bias_rs = bias_rs;
-    p.scale_log2 = scale * LOG2E; p.out_scale = out_scale; p.accumulate = accumulate; p.bias_packed = bias_packed;
-    p.k2 = nullptr; p.v2 = nullptr; p.Nk2 = 0; p.k2_bs = p.k2_rs = p.v2_bs = p.v2_rs = 0; p.out_scale2 = 0.f;
-    p.x_nqb = p.x_bpp = 0; p.x_total = 0;
-    hipStream_t s = (hipStream_t)stream;
+    p.accumulate = accumulate; p.bias_packed = bias_packed;
     ProfScope prof(bias ? PROF_ATTN_WARP : PROF_ATTN, stream);
-    if (dtype == 0) return D == 64 ? launch_attn<__bf16, 64>(p, s) : launch_attn<__bf16, 32>(p, s);
-    if (dtype == 1) return D == 64 ? launch_attn<_Float16, 64>(p, s) : launch_attn<_Float16, 32>(p, s);
-    im360_set_error("attn_fwd: dtype %d unsupported (0=bf16, 1=f16)", dtype);
-    return IM360_ERR_UNSUPPORTED;
+    return with_attn_dtype(dtype, "attn_fwd", [&](auto t) {
+        typedef typename decltype(t)::type T;
+        return D == 64 ? launch_attn<T, 64>(p, (hipStream_t)stream) : launch_attn<T, 32>(p, (hipStream_t)stream);
+    });
 }
 
 // Two key / value sets for the same queries in ONE launch: out = out_scale * softmax(q k^T scale) v + out_scale2 *
@@ -1112,28 +1108,10 @@ extern "C" __attribute__((visibility("default"))) int im360_attn_fwd2(const void
                                int64_t k2_bs, int64_t k2_rs, int64_t v2_bs, int64_t v2_rs, int64_t o_bs, int64_t o_rs,
                                int64_t kv_group, float scale, float out_scale, float out_scale2, int dtype, void* stream) {
     using namespace im360;
-    IM360_CHECK_ARG(q && k && v && k2 && v2 && out, "attn_fwd2: null pointer");
-    IM360_CHECK_ARG(B > 0 && H > 0 && Nq > 0 && Nk > 0 && Nk2 > 0, "attn_fwd2: empty problem");
-    IM360_CHECK_ARG(kv_group >= 1, "attn_fwd2: kv_group must be >= 1");
-    IM360_CHECK_ARG(D == 64, "attn_fwd2: head dim %ld unsupported (64)", (long)D);
-    IM360_CHECK_ARG(B * H <= 0x7fffffffL, "attn_fwd2: B*H too large");
-    IM360_CHECK_ARG((q_rs % 8) == 0 && (k_rs % 8) == 0 && (v_rs % 8) == 0 && (k2_rs % 8) == 0 && (v2_rs % 8) == 0 && (o_rs % 4) == 0 &&
-                    (q_bs % 8) == 0 && (k_bs % 8) == 0 && (v_bs % 8) == 0 && (k2_bs % 8) == 0 && (v2_bs % 8) == 0 && (o_bs % 4) == 0,
-                    "attn_fwd2: strides must keep 16-byte (q,k,v) / 8-byte (out) alignment");
-    IM360_CHECK_ARG(((uintptr_t)q % 16) == 0 && ((uintptr_t)k % 16) == 0 && ((uintptr_t)v % 16) == 0 && ((uintptr_t)k2 % 16) == 0 &&
-                    ((uintptr_t)v2 % 16) == 0 && ((uintptr_t)out % 8) == 0, "attn_fwd2: misaligned base pointer");
     AttnParams p;
-    p.q = q; p.k = k; p.v = v; p.bias = nullptr; p.out = out; p.bias_alt = nullptr; p.bias_sel = nullptr;
-    p.B = (int)B; p.H = (int)H; p.Nq = (int)Nq; p.Nk = (int)Nk; p.kv_group = (int)kv_group;
-    p.q_bs = q_bs; p.q_rs = q_rs; p.k_bs = k_bs; p.k_rs = k_rs; p.v_bs = v_bs; p.v_rs = v_rs;
-    p.o_bs = o_bs; p.o_rs = o_rs; p.bias_rs = 0;
-    p.scale_log2 = scale * LOG2E; p.out_scale = out_scale; p.accumulate = 0; p.bias_packed = 0;
-    p.k2 = k2; p.v2 = v2; p.Nk2 = (int)Nk2; p.k2_bs = k2_bs; p.k2_rs = k2_rs; p.v2_bs = v2_bs; p.v2_rs = v2_rs; p.out_scale2 = out_scale2;
-    p.x_nqb = p.x_bpp = 0; p.x_total = 0;
-    hipStream_t s = (hipStream_t)stream;
+    const AttnSet second{k2, v2, Nk2, k2_bs, k2_rs, v2_bs, v2_rs};
+    if (const int rc = attn_common(p, "attn_fwd2", q, AttnSet{k, v, Nk, k_bs, k_rs, v_bs, v_rs}, &second, out, B, H, Nq, D, q_bs, q_rs, o_bs, o_rs, kv_group, scale, out_scale)) return rc;
+    p.out_scale2 = out_scale2;
     ProfScope prof(PROF_ATTN_X2, stream);
-    if (dtype == 0) return launch_attn<__bf16, 64>(p, s);
-    if (dtype == 1) return launch_attn<_Float16, 64>(p, s);
-    im360_set_error("attn_fwd2: dtype %d unsupported (0=bf16, 1=f16)", dtype);
-    return IM360_ERR_UNSUPPORTED;
+    return with_attn_dtype(dtype, "attn_fwd2", [&](auto t) { return launch_attn<typename decltype(t)::type, 64>(p, (hipStream_t)stream); });
 }

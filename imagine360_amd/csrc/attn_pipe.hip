@@ -405,82 +405,69 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
     }
 }
 
+// ---- host side -----------------------------------------------------------------------------------------------------------
+// Knob attn_pipe: 0 = off; otherwise bits 0-2 = 1 + schedule, bits 3 / 6 = eight- / twelve-wave workgroups (default four),
+// bits 4-5 = read-ahead - 2, bits 8-11 = ablation build (IM360_ABLATE only).
+struct PipeKnob {
+    int raw;
+    bool on() const { return raw > 0 && (raw & 7) != 0; }
+    int sched() const { return (raw & 7) - 1; }
+    int nw() const { return (raw & 64) ? 12 : ((raw & 8) ? 8 : 4); }
+    int ahead() const { return 2 + ((raw >> 4) & 3); }
+    int abl() const { return (raw >> 8) & 15; }
+};
+static inline PipeKnob pipe_knob(const AttnParams& p) {
+    const int kb = knob(KNOB_ATTN_PIPE);
+    // -1 (default): the rule measured on MI355X (profiles/r04_attn_pipe.log) -- eight-wave workgroups, schedule 1, for long
+    // sequences (the panorama branch's levels 0 / 1: -8 % / -3 %); shorter ones (<= 1024 keys: 16 tiles, where a workgroup's
+    // prologue and the last tile's drain weigh more) stay on attn_fwd_kernel's three waves per SIMD
+    return PipeKnob{kb < 0 ? ((p.Nq >= 2048 && p.Nk >= 2048) ? 10 : 0) : kb};
+}
+
+// The shipped kernels: (schedule, read-ahead) pairs per workgroup size.  Twelve waves = three per SIMD in ONE workgroup per CU (a K / V tile
+// staged once for 384 query rows) at three waves per EU; four and eight waves at two.
+constexpr int pipe_pair(int sched, int ahead) { return sched * 8 + ahead; }
+template <int NW, typename F> static bool with_pipe_pair(int sched, int ahead, F&& f) {
+    if constexpr (NW == 12) return with_const<pipe_pair(0, 2), pipe_pair(1, 2), pipe_pair(0, 3)>(pipe_pair(sched, ahead), f);
+    else return with_const<pipe_pair(0, 2), pipe_pair(1, 2), pipe_pair(2, 2), pipe_pair(3, 2), pipe_pair(0, 3), pipe_pair(1, 3), pipe_pair(0, 4)>(pipe_pair(sched, ahead), f);
+}
+template <typename T, int NW, int SCHED, int AHEAD> constexpr auto pipe_kernel = attn_pipe_kernel<T, NW, SCHED, AHEAD, 0, NW == 12 ? 3 : 2>;
+
+// ---- ablation builds of the kernel (`make ablate`, knob bits 8-11): attn_ablate.hip's ablate_pipe(), constant "not taken" in the default build
+#define IM360_ATTN_PIPE_INCLUDES_ABLATE 1
+#include "attn_ablate.hip"
+
 template <typename T, int NW>
-int launch_nw(const AttnParams& p, hipStream_t stream, int sched, int ahead, int abl) {
+int launch_nw(const AttnParams& p, hipStream_t stream, const PipeKnob& kn) {
     AttnParams q = p;
     q.nqt = (q.Nq + 32 * NW - 1) / (32 * NW);
-    const long nblk = (long)q.B * q.H * q.nqt;
-    if (nblk > 0x7fffffffL) {
-        im360_set_error("attn_pipe: %ld workgroups exceed the grid limit", nblk);
-        return IM360_ERR_ARG;
-    }
-    dim3 grid((unsigned)nblk, 1, 1), block(NW * 64);
-#define IM360_PIPE_LAUNCH(S, A, B) hipLaunchKernelGGL((attn_pipe_kernel<T, NW, S, A, B>), grid, block, 0, stream, q)
-#ifdef IM360_ABLATE
-    if (abl && NW != 12) {
-        switch (abl) {
-            case 1: IM360_PIPE_LAUNCH(0, 2, 65 + 32 + 16 + 256); break;      // MFMA + V reads + waits only
-            case 2: IM360_PIPE_LAUNCH(0, 2, 65 + 32 + 16 + 512); break;      // MFMA + K reads + waits only
-            case 3: IM360_PIPE_LAUNCH(0, 2, 65 + 32 + 16 + 1024); break;     // MFMA + all reads at lane-linear addresses
-            case 4: IM360_PIPE_LAUNCH(0, 2, 1024); break;                    // everything, reads at lane-linear addresses
-            case 5: IM360_PIPE_LAUNCH(0, 2, 65 + 32 + 16 + 8); break;        // MFMA only
-            case 6: IM360_PIPE_LAUNCH(0, 2, 6 + 32 + 16); break;      // VALU + reads + waits only
-            case 7: IM360_PIPE_LAUNCH(0, 2, 128); break;              // reads issued, never waited for
-            case 8: IM360_PIPE_LAUNCH(0, 2, 128 + 32); break;         // ... and no staging
-            case 9: IM360_PIPE_LAUNCH(0, 2, 32 + 16); break;          // reads and waits, no staging, no barrier
-            case 10: IM360_PIPE_LAUNCH(0, 2, 65); break;
-            case 11: IM360_PIPE_LAUNCH(0, 2, 65 + 32 + 16); break;    // MFMA + reads + waits only
-            default: IM360_PIPE_LAUNCH(0, 2, 65 + 128 + 32 + 16); break;   // MFMA + reads, no waits
-        }
-        IM360_CHECK_LAUNCH();
-        return IM360_OK;
-    }
-#endif
-    if constexpr (NW == 12) {
-        // twelve waves = three per SIMD in ONE workgroup per CU (a K / V tile staged once for 384 query rows)
-        if (ahead == 3) hipLaunchKernelGGL((attn_pipe_kernel<T, NW, 0, 3, 0, 3>), grid, block, 0, stream, q);
-        else if (sched == 1) hipLaunchKernelGGL((attn_pipe_kernel<T, NW, 1, 2, 0, 3>), grid, block, 0, stream, q);
-        else hipLaunchKernelGGL((attn_pipe_kernel<T, NW, 0, 2, 0, 3>), grid, block, 0, stream, q);
-    } else if (ahead == 3) {
-        switch (sched) {
-            case 1: IM360_PIPE_LAUNCH(1, 3, 0); break;
-            default: IM360_PIPE_LAUNCH(0, 3, 0); break;
-        }
-    } else if (ahead == 4) {
-        IM360_PIPE_LAUNCH(0, 4, 0);
-    } else {
-        switch (sched) {
-            case 1: IM360_PIPE_LAUNCH(1, 2, 0); break;
-            case 2: IM360_PIPE_LAUNCH(2, 2, 0); break;
-            case 3: IM360_PIPE_LAUNCH(3, 2, 0); break;
-            default: IM360_PIPE_LAUNCH(0, 2, 0); break;
-        }
-    }
-#undef IM360_PIPE_LAUNCH
-    IM360_CHECK_LAUNCH();
-    return IM360_OK;
+    dim3 grid, block(NW * 64);
+    int rc = attn_grid("attn_pipe", (long)q.B * q.H * q.nqt, grid);
+    if (rc) return rc;
+    if (ablate_pipe<T, NW>(q, grid, block, kn.abl(), stream, rc)) return rc;
+    auto launch = [&](auto pc) {
+        constexpr int SCHED = decltype(pc)::value / 8, AHEAD = decltype(pc)::value % 8;
+        hipLaunchKernelGGL((pipe_kernel<T, NW, SCHED, AHEAD>), grid, block, 0, stream, q);
+    };
+    // a pair that is not shipped runs its read-ahead on schedule 0; no kernel at that read-ahead: its schedule at read-ahead 2, else (0, 2)
+    const int s = kn.sched(), a = kn.ahead();
+    const bool found = with_pipe_pair<NW>(s, a, launch) || with_pipe_pair<NW>(0, a, launch) || with_pipe_pair<NW>(s, 2, launch) || with_pipe_pair<NW>(0, 2, launch);
+    (void)found;
+    return im360_launch_status();
 }
 
 }  // namespace
 
 // Shapes taken: head dim 64 (the caller's template), no bias, one key / value set, Nk a multiple of 64 and >= 128, Nq >= 128.
-// Knob attn_pipe: 0 = off; otherwise bits 0-2 = 1 + schedule, bits 3 / 6 = eight- / twelve-wave workgroups (default four),
-// bits 4-5 = read-ahead - 2, bits 8-11 = ablation build (IM360_ABLATE only).
 int launch_attn_pipe(const AttnParams& p, int dtype, hipStream_t stream) {
-    int kb = knob(KNOB_ATTN_PIPE);
-    // -1 (default): the rule measured on MI355X (profiles/r04_attn_pipe.log) -- eight-wave workgroups, schedule 1, for long
-    // sequences (the panorama branch's levels 0 / 1: -8 % / -3 %); shorter ones (<= 1024 keys: 16 tiles, where a workgroup's
-    // prologue and the last tile's drain weigh more) stay on attn_fwd_kernel's three waves per SIMD
-    if (kb < 0) kb = (p.Nq >= 2048 && p.Nk >= 2048) ? 10 : 0;
-    if (kb <= 0 || (kb & 7) == 0 || p.bias || p.k2 || (p.Nk % KVB) != 0 || p.Nk < 2 * KVB || p.Nq < 128) return 1;
-    const int sched = (kb & 7) - 1, nw = (kb & 64) ? 12 : ((kb & 8) ? 8 : 4), ahead = 2 + ((kb >> 4) & 3), abl = (kb >> 8) & 15;
-    if (sched >= NSCHED || ahead > 4) return 1;
-    if (dtype == 0) {
-        if (nw == 12) return launch_nw<__bf16, 12>(p, stream, sched, ahead, abl);
-        return nw == 8 ? launch_nw<__bf16, 8>(p, stream, sched, ahead, abl) : launch_nw<__bf16, 4>(p, stream, sched, ahead, abl);
-    }
-    if (nw == 12) return launch_nw<_Float16, 12>(p, stream, sched, ahead, abl);
-    return nw == 8 ? launch_nw<_Float16, 8>(p, stream, sched, ahead, abl) : launch_nw<_Float16, 4>(p, stream, sched, ahead, abl);
+    const PipeKnob kn = pipe_knob(p);
+    if (!kn.on() || p.bias || p.k2 || (p.Nk % KVB) != 0 || p.Nk < 2 * KVB || p.Nq < 128) return 1;
+    if (kn.sched() >= NSCHED || kn.ahead() > 4) return 1;
+    return with_dtype(dtype, "attn_pipe", [&](auto t) {
+        int rc = 1;
+        with_const<4, 8, 12>(kn.nw(), [&](auto n) { rc = launch_nw<typename decltype(t)::type, decltype(n)::value>(p, stream, kn); });
+        return rc;
+    });
 }
 
 }  // namespace im360

@@ -312,9 +312,10 @@ __global__ __launch_bounds__(256) void temporal_attn_mfma_long_kernel(TAttnParam
     }
 }
 
+// ---- host side -----------------------------------------------------------------------------------------------------------
+// the scalar fallback; npix = B * P
 template <typename T, int FMAX>
-static void launch_tattn_v(TAttnParams p, hipStream_t stream) {
-    const long npix = p.total / ((long)p.F * p.heads);                 // B * P
+static void launch_tattn_v(TAttnParams p, long npix, hipStream_t stream) {
     int hpb = p.heads;                                                  // heads per block: keep one pixel's K|V <= 48 KiB
     while (hpb > 1 && (hpb % 2) == 0 && ((long)p.F * 2 * hpb * p.d * sizeof(T) > 48 * 1024 || p.F * hpb > 512)) hpb /= 2;
     const long bytes_per_pix = (long)p.F * 2 * hpb * p.d * sizeof(T);
@@ -328,46 +329,32 @@ static void launch_tattn_v(TAttnParams p, hipStream_t stream) {
     hipLaunchKernelGGL((temporal_attn_lds_kernel<T, FMAX>), grid, dim3(threads), (size_t)(ppb * bytes_per_pix), stream, p, ppb, hpb);
 }
 
+// The MFMA kernels' workgroup: `nr` frame rows of (3 * hpb * d + 8) elements (+ 64 bytes) in LDS, the heads per workgroup halved until the rows
+// fit `budget` bytes (or no further halving is possible: the caller checks lds)
+struct TattnRows { int hpb; size_t lds; };
+template <typename T>
+static TattnRows tattn_rows(const TAttnParams& p, int nr, size_t budget) {
+    auto bytes = [&](int hpb) { return (size_t)nr * (3 * hpb * p.d + 8) * sizeof(T) + 64; };
+    int hpb = p.heads;
+    while (hpb > 1 && (hpb % 2) == 0 && bytes(hpb) > budget) hpb /= 2;
+    return TattnRows{hpb, bytes(hpb)};
+}
+
 template <typename T>
 static int launch_tattn(const TAttnParams& p, hipStream_t stream) {
-    const int scalar_env = knob(KNOB_TATTN_SCALAR);   // tuning override
-    if (p.F <= 16 && !scalar_env) {
-        int hpb = p.heads;                               // heads per workgroup: ~32 KB of LDS rows (3 * hpb * d <= 1248 channels)
-        while (hpb > 1 && (hpb % 2) == 0 && hpb * p.d > 416) hpb /= 2;
-        const size_t lds = (size_t)16 * (3 * hpb * p.d + 8) * sizeof(T) + 64;
-        if (lds <= 64 * 1024) {
-            const long npix = p.total / ((long)p.F * p.heads);
-            dim3 grid((unsigned)npix, (unsigned)(p.heads / hpb));
-            switch (knob(KNOB_TATTN_NT) & 3) {
-                case 1: hipLaunchKernelGGL((temporal_attn_mfma_kernel<T, 1>), grid, dim3(256), lds, stream, p, hpb); break;
-                case 2: hipLaunchKernelGGL((temporal_attn_mfma_kernel<T, 2>), grid, dim3(256), lds, stream, p, hpb); break;
-                case 3: hipLaunchKernelGGL((temporal_attn_mfma_kernel<T, 3>), grid, dim3(256), lds, stream, p, hpb); break;
-                default: hipLaunchKernelGGL((temporal_attn_mfma_kernel<T, 0>), grid, dim3(256), lds, stream, p, hpb); break;
-            }
-            IM360_CHECK_LAUNCH();
-            return IM360_OK;
-        }
+    const long npix = p.total / ((long)p.F * p.heads);                 // B * P
+    const int ft = (p.F + 15) / 16;                                    // 16-frame tiles: 1 = temporal_attn_mfma_kernel, 2 - 4 = the long kernel
+    // up to 16 frames: ~32 KB of LDS rows (3 * hpb * d <= 1248 channels); more: whatever fits 64 KB
+    const size_t budget = ft == 1 ? (size_t)16 * (1248 + 8) * sizeof(T) + 64 : (size_t)64 * 1024;
+    const TattnRows r = tattn_rows<T>(p, ft * 16, budget);
+    if (!knob(KNOB_TATTN_SCALAR) && r.lds <= 64 * 1024) {             // (knob tattn_scalar: tuning override)
+        const dim3 grid((unsigned)npix, (unsigned)(p.heads / r.hpb));
+        if (ft == 1) with_const<0, 1, 2, 3>(knob(KNOB_TATTN_NT) & 3, [&](auto nt) { hipLaunchKernelGGL((temporal_attn_mfma_kernel<T, decltype(nt)::value>), grid, dim3(256), r.lds, stream, p, r.hpb); });
+        else with_const<2, 3, 4>(ft, [&](auto f) { hipLaunchKernelGGL((temporal_attn_mfma_long_kernel<T, decltype(f)::value>), grid, dim3(256), r.lds, stream, p, r.hpb); });
+        return im360_launch_status();
     }
-    if (p.F > 16 && !scalar_env) {
-        const int ft = (p.F + 15) / 16, nr = ft * 16;
-        int hpb = p.heads;                               // heads per workgroup: nr rows of (3 * hpb * d + 8) elements in <= 64 KB
-        while (hpb > 1 && (hpb % 2) == 0 && (size_t)nr * (3 * hpb * p.d + 8) * sizeof(T) + 64 > 64 * 1024) hpb /= 2;
-        const size_t lds = (size_t)nr * (3 * hpb * p.d + 8) * sizeof(T) + 64;
-        if (lds <= 64 * 1024) {
-            const long npix = p.total / ((long)p.F * p.heads);
-            dim3 grid((unsigned)npix, (unsigned)(p.heads / hpb));
-            if (ft == 2) hipLaunchKernelGGL((temporal_attn_mfma_long_kernel<T, 2>), grid, dim3(256), lds, stream, p, hpb);
-            else if (ft == 3) hipLaunchKernelGGL((temporal_attn_mfma_long_kernel<T, 3>), grid, dim3(256), lds, stream, p, hpb);
-            else hipLaunchKernelGGL((temporal_attn_mfma_long_kernel<T, 4>), grid, dim3(256), lds, stream, p, hpb);
-            IM360_CHECK_LAUNCH();
-            return IM360_OK;
-        }
-    }
-    if (p.F <= 16) launch_tattn_v<T, 16>(p, stream);
-    else if (p.F <= 32) launch_tattn_v<T, 32>(p, stream);
-    else launch_tattn_v<T, 64>(p, stream);
-    IM360_CHECK_LAUNCH();
-    return IM360_OK;
+    with_const<16, 32, 64>(p.F <= 16 ? 16 : (p.F <= 32 ? 32 : 64), [&](auto fmax) { launch_tattn_v<T, decltype(fmax)::value>(p, npix, stream); });
+    return im360_launch_status();
 }
 
 }  // namespace im360
@@ -394,10 +381,6 @@ extern "C" __attribute__((visibility("default"))) int im360_temporal_attn_fwd(co
     p.o_fs = o_fs; p.o_ps = o_ps; p.o_bs = o_bs;
     p.scale_log2 = scale * 1.4426950408889634f;
     IM360_CHECK_ARG(F * 2 * d * 2 <= 48 * 1024, "temporal_attn_fwd: one head's K|V rows (%ld frames x %ld) exceed the LDS budget", (long)F, (long)d);
-    hipStream_t s = (hipStream_t)stream;
     ProfScope prof(PROF_TEMPORAL, stream);
-    if (dtype == 0) return launch_tattn<__bf16>(p, s);
-    if (dtype == 1) return launch_tattn<_Float16>(p, s);
-    im360_set_error("temporal_attn_fwd: dtype %d unsupported", dtype);
-    return IM360_ERR_UNSUPPORTED;
+    return with_dtype(dtype, "temporal_attn_fwd", [&](auto t) { return launch_tattn<typename decltype(t)::type>(p, (hipStream_t)stream); });
 }
