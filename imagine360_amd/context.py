@@ -71,6 +71,25 @@ def coverage(frames, length, starts, loop=False):
     return cov
 
 
+def keyframe_frames(f, F, loop=False):
+    """The frames of a clip retimed from ``f`` to ``F`` frames (``pano_geometry.retime_pano_latent``) that ARE source frames (t == 0),
+    ascending: the j with j (f - 1) divisible by max(F - 1, 1) on an open clip, with j f divisible by F on a ring (``loop``).  The
+    even frames for F = 2 f - 1 (open) and F = 2 f (ring); the first and the last frame alone when f - 1 and F - 1 share no factor."""
+    f, F = int(f), int(F)
+    if not 1 <= f <= F:
+        raise ValueError(f"keyframe_frames: needs 1 <= f <= F, got f={f}, F={F}")
+    num, den = (f, F) if loop else (f - 1, max(F - 1, 1))
+    return [j for j in range(F) if (j * num) % den == 0]
+
+
+def keyframe_mask(f, F, loop=False):
+    """A ``regenerate_mask`` [1, F, 1, 1, 1] (float32; ``prepare_regenerate_mask`` resizes it to the latent) for a frame-interpolation
+    pass: 0 (keep) at ``keyframe_frames(f, F, loop)``, 1 (regenerate) at the frames in between."""
+    m = torch.ones(1, int(F), 1, 1, 1, dtype=torch.float32)
+    m[0, keyframe_frames(f, F, loop)] = 0.0
+    return m
+
+
 class WindowPlan:
     """The windows of one clip: ``starts`` (host ints), ``length``, the device tables the blend kernel reads, and the per-window
     model inputs.  ``inputs``: the keyword tensors of MultiViewBaseModel.forward for the WHOLE clip.  ``loop``: the windows of a

@@ -22,20 +22,11 @@
 // into the same lines, and the launch runs once per pipeline call; no LDS staging.
 #include "common.h"
 #include "fma_f32.h"
+#include "resample_weights.h"
 
 namespace im360 {
 
 constexpr int kResizeRows = 8;                   // output rows per workgroup: 32 units per row at W = 256, V = 8 -> 256 threads busy
-
-// a value the compiler cannot look through: what is computed from it is not merged with how it was computed
-__device__ __forceinline__ float opaque(float v) {
-    asm("" : "+v"(v));
-    return v;
-}
-
-// torch's cubic_convolution1 (|x| <= 1) and cubic_convolution2 (1 < |x| < 2) with A = -0.75
-__device__ __forceinline__ float keys_near(float x) { return fma_f32(opaque(fma_f32(1.25f, x, -2.25f) * x), x, 1.0f); }
-__device__ __forceinline__ float keys_far(float x) { return fma_f32(fma_f32(fma_f32(-0.75f, x, 3.75f), x, -6.0f), x, 3.0f); }
 
 // NT = 2 (bilinear) / 4 (bicubic) taps of output index o along an axis of n_in -> n_out samples: the first tap (unwrapped, unclamped)
 // and the weights
@@ -47,17 +38,8 @@ template <int NT> __device__ __forceinline__ int resize_taps(int o, int n_in, in
     // division (for 2 n_out < 2^24, any latent: both integers are exact in fp32 and the fp64 quotient is never within its own error
     // of an fp32 tie; beyond that t may be one fp32 ulp off, still the same value at every site)
     const float t = opaque((float)((double)(num - i0 * den) / (double)den));
-    if constexpr (NT == 2) {
-        wt[0] = opaque(1.0f - t);
-        wt[1] = t;
-        return (int)i0;
-    } else {
-        wt[0] = keys_far(opaque(t + 1.0f));
-        wt[1] = keys_near(t);
-        wt[2] = keys_near(opaque(1.0f - t));
-        wt[3] = keys_far(opaque(2.0f - t));
-        return (int)i0 - 1;
-    }
+    tap_weights<NT>(t, wt);                                  // (resample_weights.h, shared with retime_latents.hip)
+    return NT == 2 ? (int)i0 : (int)i0 - 1;
 }
 
 template <typename T> __device__ __forceinline__ float resize_load(const uint16_t* p) { return to_f32(__builtin_bit_cast(T, *p)); }

@@ -69,6 +69,7 @@ _SIGNATURES = {
     "im360_noise_latents": (_INT, [_PTR] * 6 + [_I64] * 5 + [_F32, _F32, _INT, _PTR]),
     "im360_keep_latents": (_INT, [_PTR] * 7 + [_I64] * 5 + [_F32, _F32, _INT, _PTR, _PTR]),
     "im360_resize_pano_latent": (_INT, [_PTR] * 2 + [_I64] * 6 + [_INT, _INT, _PTR]),
+    "im360_retime_pano_latent": (_INT, [_PTR] * 2 + [_I64] * 4 + [_INT, _INT, _INT, _PTR]),
     "im360_layernorm": (_INT, [_PTR] * 6 + [_I64] * 5 + [_F32, _INT, _PTR]),
     "im360_geglu": (_INT, [_PTR] * 2 + [_I64] * 2 + [_INT, _PTR]),
     "im360_linear_geglu": (_INT, [_PTR] * 4 + [_I64] * 3 + [_INT, _PTR]),
@@ -1143,6 +1144,36 @@ def resize_pano_latent(x, H, W, mode="bicubic"):
     out = torch.empty((1, C, F, H, W), dtype=x.dtype, device=x.device)
     rc = lib().im360_resize_pano_latent(_p(x), _p(out), C, F, h, w, H, W, RESIZE_MODES[mode], dt, _stream())
     _check(rc, "im360_resize_pano_latent")
+    return out
+
+
+RETIME_MODES = {"linear": 0, "cubic": 1}
+
+
+def retime_pano_latent(x, F, mode="linear", loop=False):
+    """A clean panorama latent resampled along its frame axis, one launch: ``x`` 16-bit [1, C, f, h, w] -> [1, C, F, h, w] with
+    ``F >= f`` (no temporal antialiasing filter: shrinking is refused).  Output frame j samples source time i0 + t from integers --
+    j (f - 1) / max(F - 1, 1) on an open clip (endpoint-aligned), j f / F on a ring (``loop``) -- ``mode`` "linear" (taps i0, i0 + 1) or
+    "cubic" (taps i0 - 1 .. i0 + 2, Keys, A = -0.75); tap frames clamp on an open clip and wrap on a ring; fp32, one rounding.  A frame
+    with t == 0 is a copy of its source frame, bit for bit.  The definition is ``pano_geometry.retime_pano_latent``."""
+    _dev(x)
+    dt = _dt(x)
+    if mode not in RETIME_MODES:
+        raise ValueError(f"retime_pano_latent: mode must be one of {sorted(RETIME_MODES)}, got {mode!r}")
+    if x.dim() != 5 or x.shape[0] != 1:
+        raise ValueError(f"retime_pano_latent: x must be [1, C, f, h, w], got {list(x.shape)}")
+    _, C, f, h, w = x.shape
+    if not isinstance(F, int) or isinstance(F, bool):
+        raise TypeError(f"retime_pano_latent: F must be an int, got {F!r}")
+    if min(C, f, h, w) < 1:
+        raise ValueError(f"retime_pano_latent: x must not be empty, got {list(x.shape)}")
+    if F < f:
+        raise ValueError(f"retime_pano_latent: {f} -> {F} frames shrinks (there is no temporal antialiasing filter; F >= f)")
+    if not x.is_contiguous():
+        raise ValueError("retime_pano_latent: x must be contiguous")
+    out = torch.empty((1, C, F, h, w), dtype=x.dtype, device=x.device)
+    rc = lib().im360_retime_pano_latent(_p(x), _p(out), C, f, F, h * w, RETIME_MODES[mode], int(bool(loop)), dt, _stream())
+    _check(rc, "im360_retime_pano_latent")
     return out
 
 

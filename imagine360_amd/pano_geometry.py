@@ -216,6 +216,17 @@ def nearest_e2p_index(eh, ew, ph, pw, cameras):
 RESIZE_MODES = ("bilinear", "bicubic")
 
 
+def _tap_weights(t, cubic):
+    """Weights [taps, ...] of a sample at fraction ``t`` in [0, 1) behind tap i0: linear, taps i0, i0 + 1 with (1 - t, t); cubic, taps
+    i0 - 1 .. i0 + 2 with the Keys kernel, A = -0.75.  Shared by the spatial resize and the retiming."""
+    if not cubic:
+        return torch.stack([1 - t, t])
+    A = -0.75                                            # torch's upsample_bicubic2d: cubic_convolution1 / cubic_convolution2
+    near = lambda x: ((A + 2) * x - (A + 3)) * x * x + 1
+    far = lambda x: ((A * x - 5 * A) * x + 8 * A) * x - 4 * A
+    return torch.stack([far(t + 1), near(t), near(1 - t), far(2 - t)])
+
+
 def _resize_taps(n_in, n_out, mode, dtype, device):
     """Taps of the ``n_out`` samples of an axis of ``n_in``: (first tap [n_out] int64, unwrapped and unclamped; weights [taps, n_out]).
     Half-pixel centres from integers: sample ``o`` sits at ((2 o + 1) n_in - n_out) / (2 n_out) = i0 + t, 0 <= t < 1; no float
@@ -224,12 +235,7 @@ def _resize_taps(n_in, n_out, mode, dtype, device):
     num = (2 * o + 1) * n_in - n_out
     i0 = torch.div(num, 2 * n_out, rounding_mode="floor")
     t = (num - i0 * 2 * n_out).to(dtype) / (2 * n_out)
-    if mode == "bilinear":
-        return i0, torch.stack([1 - t, t])
-    A = -0.75                                            # torch's upsample_bicubic2d: cubic_convolution1 / cubic_convolution2
-    near = lambda x: ((A + 2) * x - (A + 3)) * x * x + 1
-    far = lambda x: ((A * x - 5 * A) * x + 8 * A) * x - 4 * A
-    return i0 - 1, torch.stack([far(t + 1), near(t), near(1 - t), far(2 - t)])
+    return (i0, _tap_weights(t, False)) if mode == "bilinear" else (i0 - 1, _tap_weights(t, True))
 
 
 def resize_pano_latent(x, H, W, mode="bicubic"):
@@ -258,3 +264,49 @@ def resize_pano_latent(x, H, W, mode="bicubic"):
     r0, wy = _resize_taps(h, H, mode, wdt, x.device)
     wy = wy.to(x.dtype)[:, :, None]
     return blend([x[..., (r0 + k).clamp(0, h - 1), :] for k in range(wy.shape[0])], wy)                    # [..., H, W]
+
+
+# ------------------------------------------------------------------------------- retiming a panorama latent
+RETIME_MODES = ("linear", "cubic")
+
+
+def _retime_taps(f, F, mode, loop, dtype, device):
+    """Taps of the ``F`` output frames of a clip of ``f``: (first tap [F] int64, unclamped and unwrapped; weights [taps, F]; keyframe flag
+    [F], t == 0).  Output frame j samples source time num / den = i0 + t from integers: an open clip is endpoint-aligned (num =
+    j (f - 1), den = max(F - 1, 1)), a ring is not (num = j f, den = F: frame F would be frame 0 again)."""
+    j = torch.arange(F, dtype=torch.int64, device=device)
+    num, den = (j * f, F) if loop else (j * (f - 1), max(F - 1, 1))
+    i0 = torch.div(num, den, rounding_mode="floor")
+    rem = num - i0 * den
+    cubic = mode == "cubic"
+    return (i0 - 1 if cubic else i0), _tap_weights(rem.to(dtype) / den, cubic), rem == 0
+
+
+def retime_pano_latent(x, F, mode="linear", loop=False):
+    """``x`` [..., f, h, w] -> [..., F, h, w], ``F >= f``: a clip resampled along its frame axis so that source frames land exactly on
+    output frames.  The eager definition of ``kernels.retime_pano_latent``, in torch ops on any device, blending in ``x``'s dtype (the
+    weights are formed in float32 for a 16-bit ``x``).  Output frame j samples source time i0 + t, from integers: an open clip
+    (``loop=False``) is endpoint-aligned, num = j (f - 1) over den = max(F - 1, 1) -- frame 0 is frame 0 and frame F - 1 is frame f - 1,
+    torch's ``align_corners=True``; a ring (``loop=True``) has num = j f over den = F, frame F being frame 0 again.  "linear": taps
+    i0, i0 + 1 with weights (1 - t, t); "cubic": taps i0 - 1 .. i0 + 2, Keys kernel with A = -0.75 (the polynomials of
+    ``resize_pano_latent``).  Tap frames clamp to [0, f - 1] on an open clip and wrap (mod f) on a ring.  A sum is w0 a0 + w1 a1 + ...
+    in this order.  A frame with t == 0 is a COPY of source frame i0 -- NaNs and the sign of zero included -- and no weighted sum is
+    formed there: with F = 2 f - 1 (open) or F = 2 f (ring) the even output frames are the source frames."""
+    if mode not in RETIME_MODES:
+        raise ValueError(f"retime_pano_latent: mode must be one of {sorted(RETIME_MODES)}, got {mode!r}")
+    if not isinstance(F, int) or isinstance(F, bool):
+        raise TypeError(f"retime_pano_latent: F must be an int, got {F!r}")
+    if x.dim() < 3:
+        raise ValueError(f"retime_pano_latent: x must be [..., f, h, w], got {list(x.shape)}")
+    f = x.shape[-3]
+    if F < f or f < 1:
+        raise ValueError(f"retime_pano_latent: {f} -> {F} frames shrinks (there is no temporal antialiasing filter; F >= f >= 1)")
+    wdt = x.dtype if x.dtype in (torch.float32, torch.float64) else torch.float32
+    t0, wt, key = _retime_taps(f, F, mode, bool(loop), wdt, x.device)
+    wt = wt.to(x.dtype)[:, :, None, None]
+    frame = (lambda tap: tap % f) if loop else (lambda tap: tap.clamp(0, f - 1))
+    acc = wt[0] * x[..., frame(t0), :, :]
+    for k in range(1, wt.shape[0]):
+        acc = acc + wt[k] * x[..., frame(t0 + k), :, :]
+    i0 = t0 + 1 if mode == "cubic" else t0
+    return torch.where(key[:, None, None], x[..., i0.clamp(0, f - 1), :, :], acc)

@@ -24,6 +24,9 @@ surface, rebuilt for the MI355X:
   * a hi-res pass (``init_latents`` / ``init_video`` SMALLER than the run, ``init_resize``): the clean latent of a clip generated at the
     trained size is upscaled once, as the equirectangular image it is (longitude wraps, latitude clamps), in ONE kernel
     (``kernels.resize_pano_latent``) in front of everything above, which then sees a clean latent of the run's size.
+  * a frame-interpolation pass (``init_latents`` / ``init_video`` with FEWER FRAMES than the run, ``init_retime``): the clean latent of
+    a clip generated at a coarse frame stride is retimed once along its frame axis -- source frames land exactly on output frames; a
+    looping clip is a ring -- in ONE kernel (``kernels.retime_pano_latent``) in front of the upscale.
 
 CLIP text encoding and SAM feature extraction are outside the hot path: the
 pipeline uses ``text_encoder``/``tokenizer``/``image_encoder`` when given, and also accepts precomputed
@@ -192,15 +195,25 @@ class AnimationPipeline:
         lat = torch.cat([self.vae.encode(x[i:i + chunk], min(chunk, b * f - i)).latent_dist.mode() for i in range(0, b * f, chunk)])
         return lat.reshape(b, f, *lat.shape[1:]).permute(0, 2, 1, 3, 4) * VAE_SCALE
 
-    def resize_init(self, x0, video_length, equi_h, equi_w, device, latents_dtype=torch.float16, init_resize="bicubic"):
-        """The clean init latent ``x0`` [1, 4, F, h, w] at the size of the run: itself when ``(h, w) == (equi_h, equi_w)`` -- no launch,
-        no copy -- and otherwise upscaled once (``kernels.resize_pano_latent``: half-pixel centres, ``init_resize`` "bicubic" or
-        "bilinear", columns wrap, rows clamp) in ``latents_dtype`` on ``device``.  ``ValueError``: another frame count, or an init that
-        is larger than the run in either dimension (there is no antialiasing filter)."""
-        if x0.dim() != 5 or tuple(x0.shape[:3]) != (1, 4, video_length) or x0.shape[3] > equi_h or x0.shape[4] > equi_w:
+    def resize_init(self, x0, video_length, equi_h, equi_w, device, latents_dtype=torch.float16, init_resize="bicubic", init_retime=None,
+                    loop=False):
+        """The clean init latent ``x0`` [1, 4, f, h, w] at the frame count and size of the run: itself when ``(f, h, w) == (video_length,
+        equi_h, equi_w)`` -- no launch, no copy.  Otherwise, in ``latents_dtype`` on ``device``: with ``f < video_length`` and
+        ``init_retime`` given ("linear" or "cubic"; None, the default: another frame count is refused as ever) retimed once at its
+        own (small) size (``kernels.retime_pano_latent``: source frames land on output frames;
+        ``loop``: the frames are a ring), then, with another size, upscaled once (``kernels.resize_pano_latent``: half-pixel centres,
+        ``init_resize`` "bicubic" or "bilinear", columns wrap, rows clamp).  An init that differs in both is rounded to
+        ``latents_dtype`` twice, once by each kernel.  ``ValueError``: more frames than the run (there is no temporal antialiasing
+        filter), fewer without ``init_retime``, or an init that is larger than the run in either dimension (there is no spatial
+        filter either)."""
+        frames_ok = x0.dim() == 5 and (x0.shape[2] == video_length or (init_retime is not None and 1 <= x0.shape[2] < video_length))
+        if not frames_ok or tuple(x0.shape[:2]) != (1, 4) or x0.shape[3] > equi_h or x0.shape[4] > equi_w:
             raise ValueError(f"the init latent must be [1, 4, {video_length}, {equi_h}, {equi_w}] or smaller in its last two dimensions "
                              f"(a clean panorama latent, multiplied by VAE_SCALE, such as pipe.last_latents[0]; a smaller one is "
-                             f"upscaled, init_resize), got {tuple(x0.shape)}")
+                             f"upscaled, init_resize) or, with init_retime='linear' or 'cubic', with fewer frames (retimed to the run's frame count), got "
+                             f"{tuple(x0.shape)}")
+        if x0.shape[2] != video_length:
+            x0 = kernels.retime_pano_latent(x0.to(device=device, dtype=latents_dtype).contiguous(), video_length, init_retime, bool(loop))
         if tuple(x0.shape[3:]) == (equi_h, equi_w):
             return x0
         return kernels.resize_pano_latent(x0.to(device=device, dtype=latents_dtype).contiguous(), equi_h, equi_w, init_resize)
@@ -311,7 +324,8 @@ class AnimationPipeline:
                  video_batch=None, use_outpaint=False, use_ip_plus_cross_attention=False, use_fps_condition=False,
                  ip_plus_condition="image", prompt_embeds=None, sam_features=None, trace=None, frame_shard=None,
                  context_frames=None, context_overlap=4, context_weights="pyramid", guidance_rescale=0.0, context_loop=False,
-                 init_latents=None, init_video=None, strength=1.0, regenerate_mask=None, init_resize="bicubic", **kwargs):
+                 init_latents=None, init_video=None, strength=1.0, regenerate_mask=None, init_resize="bicubic", init_retime=None,
+                 **kwargs):
         """``frame_shard`` (imagine360_amd.dist.FrameShard): this rank denoises a contiguous chunk of the frames (BASELINE
         configs 4 / 5); all ranks must be called with the same seeds and inputs.  Noise is drawn for the whole clip and
         cut, the VAE encodes / the loop runs / the VAE decodes only the local frames, the motion modules exchange tokens
@@ -354,7 +368,20 @@ class AnimationPipeline:
         ``last_latents[0]`` is the UPSCALED clean latent bit for bit), both graphed steps, context windows, ``context_loop``, ``eta`` and
         ``guidance_rescale`` run as for an init of the run's size and the RNG order is unchanged.  Generate at the trained size, then
         call again with a ``video_batch`` of twice the size, ``init_latents=pipe.last_latents[0]`` and ``strength`` around 0.5.  An init
-        of the run's size never reaches the new code; a larger one, or another frame count, raises ``ValueError``."""
+        of the run's size never reaches the new code; a larger one raises ``ValueError``.
+        ``init_retime`` (None: off, an init with another frame count raises as it always did; "linear", or "cubic"): the
+        frame-interpolation pass.  With it ``init_latents`` may be [1, 4, f, h, w] with ``f <= video_length`` and ``init_video`` [1, f, 3, 8h, 8w] (encoded at its own frame count and size, no RNG draw): a clip of fewer
+        frames is retimed once to the run's frame count before anything else sees it (``kernels.retime_pano_latent``, one launch, at
+        the init's own size and in front of the upscale when both apply -- two roundings to ``latents_dtype`` then).  Output frame j
+        samples source time j (f - 1) / (F - 1): endpoint-aligned, so source frames land exactly on output frames (the even ones for
+        ``video_length = 2 f - 1``) and are copied there bit for bit; with ``context_loop`` the frames are a ring, j f / F, and the
+        in-betweens after the last source frame blend towards the first (the even frames for ``video_length = 2 f``).  Generate 16
+        frames at a coarse frame stride, then call again with a ``video_batch`` of the finer stride, ``context_frames=16``,
+        ``init_latents=pipe.last_latents[0]``, ``init_retime="linear"`` and ``strength`` around 0.5: the windows inherit the coarse clip's global motion.
+        ``regenerate_mask=context.keyframe_mask(f, video_length, loop)`` pins the source frames and denoises only the in-betweens.
+        The conditioning ``video_batch`` is the caller's, at the run's frame count.  Everything after the retime runs as for an init
+        of the run's frame count, the RNG order is unchanged, and such an init never reaches the new code; an init with MORE
+        frames than the run raises ``ValueError`` (there is no temporal antialiasing filter)."""
         device = self.device
         vb = video_batch
         plan = None
@@ -375,6 +402,8 @@ class AnimationPipeline:
             raise ValueError("give at most one of init_latents and init_video")
         if init_resize not in G.RESIZE_MODES:
             raise ValueError(f"init_resize must be one of {sorted(G.RESIZE_MODES)}, got {init_resize!r}")
+        if init_retime is not None and init_retime not in G.RETIME_MODES:
+            raise ValueError(f"init_retime must be None or one of {sorted(G.RETIME_MODES)}, got {init_retime!r}")
         has_init = init_latents is not None or init_video is not None
         if regenerate_mask is not None and not has_init:
             raise ValueError("regenerate_mask needs init_latents or init_video (the clip whose unmasked part is kept)")
@@ -412,7 +441,8 @@ class AnimationPipeline:
         if has_init:
             # the encode draws nothing, so it may come first: the panorama noise is then drawn where init_noise draws it
             x0 = init_latents if init_latents is not None else self.encode_init_video(init_video.to(device))
-            x0 = self.resize_init(x0, f, H // 8, W // 8, device, latents_dtype, init_resize)     # (itself at the run's size)
+            x0 = self.resize_init(x0, f, H // 8, W // 8, device, latents_dtype, init_resize, init_retime,
+                                  loop=bool(context_loop))                                       # (itself at the run's frame count and size)
             keep_mask = None if regenerate_mask is None else self.prepare_regenerate_mask(regenerate_mask, f, H // 8, W // 8, device)
             pano_latent, pers_latent, steps_host, *region = self.init_from_clip(x0, strength, f, H // 8, W // 8, ps // 8, ps // 8, cameras,
                                                                                 device, latents_dtype, regenerate_mask=keep_mask)

@@ -430,6 +430,23 @@ int im360_keep_latents(void* pano, void* pers, const void* x0, const float* nois
 int im360_resize_pano_latent(const void* x, void* out, int64_t C, int64_t F, int64_t h, int64_t w, int64_t H, int64_t W, int mode,
                              int dtype, void* stream);
 
+/* ---- retiming a clean panorama latent (AnimationPipeline.resize_init: init_latents / init_video with fewer frames than the run,
+ * init_retime), one launch: x [C, f, hw] -> out [C, F, hw], F >= f, one 16-bit dtype; mode 0 linear, 1 cubic; loop 0 open clip, 1 ring.
+ *   out[c, j, p] = T(sum_k wt[j][k] * x[c, frame(j, k), p])                                    fp32, one rounding
+ * Output frame j samples source time i0 + t from integers: num = j (f - 1), den = max(F - 1, 1) on an open clip (endpoint-aligned:
+ * frame 0 -> frame 0, frame F - 1 -> frame f - 1), num = j f, den = F on a ring (frame F would be frame 0 again); i0 = num / den,
+ * t = float(num - i0 den) / float(den), one rounding.  Linear: taps i0, i0 + 1, weights (1 - t, t); cubic: taps i0 - 1 .. i0 + 2, Keys
+ * kernel, A = -0.75 (the weights of im360_resize_pano_latent).  Tap frames clamp to [0, f - 1] on an open clip and wrap (mod f) on a
+ * ring.  A frame with t == 0 is a copy of source frame i0, bit for bit (NaNs, the sign of zero); F == f returns the input's bits.
+ * One workgroup per (channel, output frame, 4096 plane elements); eight elements per unit, one 16-byte load per tap and one 16-byte
+ * store when hw % 8 == 0 and both pointers are 16-byte aligned, a scalar path otherwise, the same bits on both; no LDS, no atomics.
+ * Refused: a null pointer, a size <= 0, f / F / C * F / hw + 4096 >= 2^31, C * F * ceil(hw / 4096) >= 2^24 workgroups (a launch holds
+ * fewer than 2^32 threads), a pointer off 2 bytes, x == out, F < f (no temporal antialiasing filter), an unknown mode, loop or dtype.
+ * Replaces: nothing in the reference (it generates its 16 frames in one pass); F.interpolate(..., align_corners=True) along the frame
+ *   axis, made aware of the loop point of a looping clip. */
+int im360_retime_pano_latent(const void* x, void* out, int64_t C, int64_t f, int64_t F, int64_t hw, int mode, int loop, int dtype,
+                             void* stream);
+
 /* y[r] = LayerNorm(x[r] + pre[r % pre_period]) * gamma + beta + post[(r / post_div) % post_mod] on token rows
  * [rows, C]; pre / post are optional [*, C] tables (the WarpAttn spherical PE added before norm1, the motion
  * module's frame PE added after the norm).

@@ -29,7 +29,14 @@ device events, with the bytes each has to move computed from the shapes.  Prints
                                                       # at this strength, next to ONE call from pure noise at the full size, alternated --rounds times
                                                       # after one warm-up of every shape; and kernels.resize_pano_latent at these sizes, both modes, next
                                                       # to the eager definition pano_geometry.resize_pano_latent on the GPU.  --pano-hw: the latent size
-                                                      # of the full-size run (default 128 256: BASELINE cfg5, 1024 x 2048 pixels)"""
+                                                      # of the full-size run (default 128 256: BASELINE cfg5, 1024 x 2048 pixels)
+    python tools/bench_context.py --init-frames 16 --frames 31 --strength 0.5 [--loop] [--num-steps 20]
+                                                      # the frame-interpolation pass: a first pipeline call from pure noise with --init-frames frames
+                                                      # plus a second call with --frames frames from its latent (init_latents with fewer frames than
+                                                      # the run: kernels.retime_pano_latent; context windows of 16, --loop: on a ring) at this strength,
+                                                      # next to ONE call from pure noise with --frames frames, alternated --rounds times after one
+                                                      # warm-up of every shape; and kernels.retime_pano_latent at the cfg2 latent size, both modes,
+                                                      # next to the eager definition pano_geometry.retime_pano_latent on the GPU"""
 import argparse
 import json
 import os
@@ -298,6 +305,102 @@ def time_resize(small_hw, big_hw, frames, dev, dt, iters, rounds=5):
     return res
 
 
+def time_retime(f, frames, hw, loop, dev, dt, iters, rounds=5):
+    """Device-event time of ``kernels.retime_pano_latent`` and of the eager definition ``pano_geometry.retime_pano_latent`` on the GPU,
+    both modes (alternated round by round, ``iters`` back-to-back calls each, allocation of the result included), the spread over the
+    rounds, and the bytes the launch has to move (a keyframe reads one frame, a linear in-between two, a cubic one four)."""
+    from imagine360_amd import pano_geometry as G
+    from imagine360_amd.context import keyframe_frames
+    x = (1.5 * torch.randn(1, 4, f, *hw, device=dev)).to(dt)
+    keys = len(keyframe_frames(f, frames, loop))
+    plane = 4 * hw[0] * hw[1] * 2
+    res = dict(x=list(x.shape), out=[1, 4, frames, *hw], loop=bool(loop), keyframes=keys, iters=iters, rounds=rounds)
+    for mode, taps in zip(G.RETIME_MODES, (2, 4)):
+        fns = dict(kernel=lambda: kernels.retime_pano_latent(x, frames, mode, loop), eager=lambda: G.retime_pano_latent(x, frames, mode, loop))
+        ref = G.retime_pano_latent(x.double(), frames, mode, loop)
+        diff = {k: float((fn().double() - ref).abs().max()) for k, fn in fns.items()}
+        times = {k: [] for k in fns}
+        for r in range(rounds + 1):
+            for name, fn in fns.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                for _ in range(iters):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                if r:                                   # round 0 warms both up
+                    times[name].append(e0.elapsed_time(e1) / iters * 1e3)
+        res[mode] = {k: dict(us_min=min(v), us_median=statistics.median(v), us_max=max(v), max_abs_diff_from_fp64=diff[k]) for k, v in times.items()}
+        res[mode]["eager_over_kernel"] = res[mode]["eager"]["us_min"] / res[mode]["kernel"]["us_min"]
+        res[mode]["bytes"] = plane * (frames + keys + taps * (frames - keys))
+        res[mode]["gb_per_s_kernel"] = res[mode]["bytes"] / (res[mode]["kernel"]["us_min"] * 1e-6) / 1e9
+    res["note"] = ("event time over back-to-back calls; the eager definition blends in bf16 (several roundings), the kernel in fp32 (one); "
+                   "the working set fits the Infinity Cache, and at this size the launch is latency-bound")
+    return res
+
+
+def retime_bench(args, sch, dev, dt):
+    """--init-frames f: the two-pass run (f frames from pure noise, then --frames frames from its latent at --strength, in windows of 16
+    when --frames > 16) next to one run from pure noise with --frames frames; whole pipeline calls (encode, loop, decode), host clock
+    around a call that ends in a device synchronise."""
+    import random
+
+    from imagine360_amd.pipeline import AnimationPipeline
+    f, frames = args.init_frames, args.frames
+    assert 1 <= f <= frames, f"--init-frames {f} must be at most --frames {frames}"
+    res = dict(tool="bench_context --init-frames", init_frames=f, strength=args.strength, frames=frames, num_inference_steps=args.num_steps,
+               pano_hw=PANO_HW, dtype="bfloat16", device=torch.cuda.get_device_name(0))
+    res["retime_pano_latent"] = time_retime(f, frames, PANO_HW, args.loop, dev, dt, args.kernel_iters)
+    if args.kernel_only:
+        return res
+    mv = configs.build_mv_model(1, device=dev, dtype=dt, xformers=True)
+    mv.dual_stream, mv.warp_streams = True, True
+    vae = configs.build_vae(1, device=dev, dtype=dt)
+    pipe = AnimationPipeline(vae, None, None, mv.unet, mv.pano_unet, mv, type(sch)(**configs.NOISE_SCHEDULER_KWARGS), None, "SAM").to(dev)
+    pipe._no_progress = True
+    vbs = {n: synthetic.video_batch(frames=n, pano_hw=(PANO_HW[0] * 8, PANO_HW[1] * 8), seed=1) for n in (f, frames)}
+    cond = synthetic.conditioning(frames=max(frames, 16), seed=1)
+    windows = {n: (dict(context_frames=LENGTH, context_overlap=OVERLAP, context_loop=args.loop) if n > LENGTH else {}) for n in (f, frames)}
+    res["windows"] = windows[frames]
+
+    def call(n, **kw):
+        torch.manual_seed(21)
+        random.seed(21)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        vid = pipe("synthetic", num_inference_steps=args.num_steps, guidance_scale_text=7.5, negative_prompt="", latents_dtype=dt,
+                   video_batch=vbs[n], use_outpaint=True, use_ip_plus_cross_attention=True, use_fps_condition=True, ip_plus_condition="video",
+                   prompt_embeds=(cond["text_pano"], cond["text_pers"]), sam_features=(cond["sam_pano"], cond["sam_pers"]), **windows[n], **kw).videos
+        torch.cuda.synchronize()
+        assert vid.shape[2] == n
+        return (time.perf_counter() - t0) * 1e3, bool(torch.isfinite(vid).all())
+
+    def two_pass():
+        a, ok_a = call(f)
+        b, ok_b = call(frames, init_latents=pipe.last_latents[0], strength=args.strength, init_retime="linear")
+        return dict(first_pass_ms=a, second_pass_ms=b, total_ms=a + b), ok_a and ok_b
+
+    sch.set_timesteps(args.num_steps)
+    res["steps"] = dict(first_pass=args.num_steps, second_pass=len(sch.timesteps_for_strength(args.strength)[1]), direct=args.num_steps)
+    warm, fin = two_pass()                                  # warms every shape of both frame counts up
+    res["warm_up"] = dict(two_pass=warm, direct_ms=call(frames)[0])
+    print("warm-up done", file=sys.stderr, flush=True)
+    runs = dict(two_pass=[], direct=[])
+    for _ in range(args.rounds):
+        t, ok = two_pass()
+        runs["two_pass"].append(t)
+        ms, ok2 = call(frames)
+        runs["direct"].append(ms)
+        fin = fin and ok and ok2
+    res["two_pass"] = dict(calls=runs["two_pass"], total_ms_min=min(r["total_ms"] for r in runs["two_pass"]),
+                           total_ms_max=max(r["total_ms"] for r in runs["two_pass"]))
+    res["direct"] = dict(call_ms=runs["direct"], call_ms_min=min(runs["direct"]), call_ms_max=max(runs["direct"]))
+    res["two_pass_over_direct"] = res["two_pass"]["total_ms_min"] / res["direct"]["call_ms_min"]
+    res["finite"] = fin
+    return res
+
+
 def hires_bench(args, sch, dev, dt):
     """--init-scale N: the two-pass run (1 / N of the size from pure noise, then the full size from its latent at --strength) next to one
     run from pure noise at the full size; whole pipeline calls (encode, loop, decode), host clock around a call that ends in a device
@@ -450,6 +553,8 @@ def main():
                     help="--strength: keep part of the clip (pipeline regenerate_mask) and time that call next to the call without the mask")
     ap.add_argument("--init-scale", type=int, default=None,
                     help="with --strength: the hi-res pass -- a first call at 1/N of --pano-hw, a second call at --pano-hw from its latent -- next to one call from pure noise at --pano-hw")
+    ap.add_argument("--init-frames", type=int, default=None,
+                    help="with --strength: the frame-interpolation pass -- a first call with this many frames, a second call with --frames frames from its latent -- next to one call from pure noise with --frames frames")
     ap.add_argument("--pano-hw", type=int, nargs=2, default=[128, 256], metavar=("H", "W"), help="--init-scale: latent size of the full-size run (default: cfg5)")
     ap.add_argument("--sampler", choices=["ddim", "dpmpp2m"], default="ddim", help="the scheduler of every step and call (dpmpp2m: DPM-Solver++ 2M)")
     ap.add_argument("--out", default=None)
@@ -461,6 +566,9 @@ def main():
     sch = (DPMSolverMultistepScheduler if args.sampler == "dpmpp2m" else DDIMScheduler)(**configs.NOISE_SCHEDULER_KWARGS)
     sch.set_timesteps(25)
     ts_host = [int(t) for t in sch._timesteps_host]
+    if args.init_frames is not None:
+        assert args.strength is not None and args.init_scale is None, "--init-frames f goes with --strength (and not with --init-scale)"
+        return emit(retime_bench(args, sch, dev, dt), args.out)
     if args.init_scale is not None:
         assert args.strength is not None and args.init_scale >= 1, "--init-scale N (>= 1) goes with --strength"
         return emit(hires_bench(args, sch, dev, dt), args.out)
