@@ -187,6 +187,13 @@ class GraphedDenoiseStep:
         self.graph.replay()
         return self.pano_lat, self.pers_lat
 
+    def restart(self, pano_latent, pers_latent):
+        """Another run of the schedule on the captured step (pipeline ``free_init_iters``): the given start latents are copied into the
+        static ones -- no new capture, no warm-up.  ``step`` returns the static buffers, so a caller that keeps a result clones it
+        first.  A multistep scheduler's histories need no reset: the first step of a run is first order and only writes them."""
+        self.pano_lat.copy_(pano_latent)
+        self.pers_lat.copy_(pers_latent)
+
 
 class GraphedWindowedStep(GraphedDenoiseStep):
     """One denoising step over sliding temporal context windows (imagine360_amd.context) in ONE hipGraph: the forwards of all

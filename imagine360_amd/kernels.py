@@ -70,6 +70,7 @@ _SIGNATURES = {
     "im360_keep_latents": (_INT, [_PTR] * 7 + [_I64] * 5 + [_F32, _F32, _INT, _PTR, _PTR]),
     "im360_resize_pano_latent": (_INT, [_PTR] * 2 + [_I64] * 6 + [_INT, _INT, _PTR]),
     "im360_retime_pano_latent": (_INT, [_PTR] * 2 + [_I64] * 4 + [_INT, _INT, _INT, _PTR]),
+    "im360_free_init_noise": (_INT, [_PTR] * 8 + [_I64] * 5 + [_F32] * 3 + [_INT, _PTR]),
     "im360_layernorm": (_INT, [_PTR] * 6 + [_I64] * 5 + [_F32, _INT, _PTR]),
     "im360_geglu": (_INT, [_PTR] * 2 + [_I64] * 2 + [_INT, _PTR]),
     "im360_linear_geglu": (_INT, [_PTR] * 4 + [_I64] * 3 + [_INT, _PTR]),
@@ -1174,6 +1175,42 @@ def retime_pano_latent(x, F, mode="linear", loop=False):
     out = torch.empty((1, C, F, h, w), dtype=x.dtype, device=x.device)
     rc = lib().im360_retime_pano_latent(_p(x), _p(out), C, f, F, h * w, RETIME_MODES[mode], int(bool(loop)), dt, _stream())
     _check(rc, "im360_retime_pano_latent")
+    return out
+
+
+def free_init_noise(x0, n1, n2, Lf, Lh, Lw, sa, sb):
+    """FreeInit's effective noise (arXiv 2312.07537), three launches: ``x0`` 16-bit [1, 4, F, h, w] (the clean clip), ``n1`` / ``n2`` float32
+    [1, F, 4, h, w] (the noise the clip was generated from, a fresh draw) -> ``n_eff`` float32 [1, F, 4, h, w] with
+    ``sa x0 + sb n_eff = n2 + L (sa x0 + sb n1 - n2)``, L = ``Lf`` (x) ``Lh`` (x) ``Lw``: float32 [F, F], [h, h], [w, w]
+    (``pano_geometry.free_init_operator`` in fp64, rounded once).  fp32 fma chains, deterministic; identity operators return ``n1``'s
+    bits.  ``sb`` must be positive (pure signal has no noise to replace); 1 / sb is formed in fp64 here.  The definition is
+    ``pano_geometry.free_init_noise``."""
+    _dev(x0, n1, n2, Lf, Lh, Lw)
+    dt = _dt(x0)
+    if x0.dim() != 5 or x0.shape[0] != 1:
+        raise ValueError(f"free_init_noise: x0 must be [1, C, F, h, w], got {list(x0.shape)}")
+    _, C, F, h, w = x0.shape
+    if min(C, F, h, w) < 1:
+        raise ValueError(f"free_init_noise: x0 must not be empty, got {list(x0.shape)}")
+    for name, n in (("n1", n1), ("n2", n2)):
+        if n.dtype != torch.float32 or tuple(n.shape) != (1, F, C, h, w):
+            raise ValueError(f"free_init_noise: {name} must be float32 [1, {F}, {C}, {h}, {w}], got {n.dtype} {list(n.shape)}")
+    for name, L, n in (("Lf", Lf, F), ("Lh", Lh, h), ("Lw", Lw, w)):
+        if L.dtype != torch.float32 or tuple(L.shape) != (n, n):
+            raise ValueError(f"free_init_noise: {name} must be float32 [{n}, {n}], got {L.dtype} {list(L.shape)}")
+    for name, t in (("x0", x0), ("n1", n1), ("n2", n2), ("Lf", Lf), ("Lh", Lh), ("Lw", Lw)):
+        if t.device != x0.device:
+            raise ValueError(f"free_init_noise: {name} is on {t.device}, x0 on {x0.device}")
+        if not t.is_contiguous():
+            raise ValueError(f"free_init_noise: {name} must be contiguous")
+    sa, sb = float(sa), float(sb)
+    if not sb > 0.0:
+        raise ValueError(f"free_init_noise: sb={sb} must be positive (pure signal has no noise to replace)")
+    out = torch.empty((1, F, C, h, w), dtype=torch.float32, device=x0.device)
+    ws = torch.empty(2 * out.numel(), dtype=torch.float32, device=x0.device)
+    rc = lib().im360_free_init_noise(_p(x0), _p(n1), _p(n2), _p(Lf), _p(Lh), _p(Lw), _p(out), _p(ws), ws.numel(), C, F, h, w, sa, sb,
+                                     1.0 / sb, dt, _stream())
+    _check(rc, "im360_free_init_noise")
     return out
 
 

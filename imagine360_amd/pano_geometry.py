@@ -310,3 +310,66 @@ def retime_pano_latent(x, F, mode="linear", loop=False):
         acc = acc + wt[k] * x[..., frame(t0 + k), :, :]
     i0 = t0 + 1 if mode == "cubic" else t0
     return torch.where(key[:, None, None], x[..., i0.clamp(0, f - 1), :, :], acc)
+
+
+# ------------------------------------------------------------------------------- FreeInit: the low-pass of a panorama clip
+def free_init_operator(n, d, periodic):
+    """The Gaussian low-pass of FreeInit (arXiv 2312.07537; diffusers' ``free_init_utils``) along ONE axis of ``n`` samples, as a dense
+    [n, n] float64 matrix (row i: the weights of output i), with the boundary that axis has.  FreeInit's gain is exp(-D^2 / (2 d_s^2))
+    with D^2 = ((d_s / d_t) t)^2 + y^2 + x^2 in normalised frequency (fraction of Nyquist): a product of three 1-D gains, so the filter
+    is three such operators -- ``d`` = d_s along h and w, d_t along the frames.  Only this Gaussian filter is offered: diffusers'
+    Butterworth and ideal masks are not separable and would need a true 3-D transform.
+    With g_N(k) = exp(-(2 k / N)^2 / (2 d^2)) over the signed integer frequencies k of ``torch.fft.fftfreq(N, 1 / N)``:
+      ``periodic=True`` (longitude: the +-180 degree seam; the frames of a looping clip): the circular convolution
+        L[i, j] = (1 / n) sum_k g_n(k) cos(2 pi k (i - j) / n);
+      ``periodic=False`` (latitude: the poles; the frames of an open clip): the half-sample mirror extension to a ring of 2 n samples
+        (x_0 .. x_{n-1}, x_{n-1} .. x_0), filtered there and cropped,
+        L[i, j] = c(i - j) + c(i + j + 1),  c(m) = (1 / 2n) sum_k g_2n(k) cos(2 pi k m / 2n)
+      -- ``fftn`` would wrap a pole into the other pole and the last frame into the first.
+    ``n = 1`` gives [[1]].  Both kinds are symmetric and their rows sum to 1 (a constant clip passes unchanged), checked for n = 1 .. 64;
+    d -> infinity gives the identity, d -> 0 the mean.  For even ``n`` on all three axes with ``periodic=True`` everywhere the operator
+    equals diffusers' fftshift . Gaussian mask . ifftshift round trip (4e-16 at (16, 8, 16)); for odd ``n`` diffusers' mask is
+    asymmetric in +-k and its result is not real: the symmetric gain above is the definition here."""
+    if not isinstance(n, int) or isinstance(n, bool) or n < 1:
+        raise ValueError(f"free_init_operator: n must be a positive int, got {n!r}")
+    d = float(d)
+    if not d > 0.0:
+        raise ValueError(f"free_init_operator: d={d} must be positive (the cut-off as a fraction of Nyquist)")
+    N = n if periodic else 2 * n
+    k = torch.fft.fftfreq(N, 1.0 / N, dtype=torch.float64).round().to(torch.int64)
+    g = torch.exp(-(2.0 * k.double() / N) ** 2 / (2.0 * d * d))
+
+    def c(m):                                            # [..] int64 -> (1 / N) sum_k g(k) cos(2 pi k m / N), the angle reduced in integers
+        ang = (k * m[..., None]) % N
+        return (g * torch.cos(2.0 * math.pi * ang.double() / N)).sum(-1) / N
+
+    i = torch.arange(n, dtype=torch.int64)
+    diff, summ = i[:, None] - i[None, :], i[:, None] + i[None, :] + 1
+    return c(diff) if periodic else c(diff) + c(summ)
+
+
+def free_init_noise(x0, n1, n2, sa, sb, Lf, Lh, Lw):
+    """FreeInit's EFFECTIVE NOISE, the eager definition of ``kernels.free_init_noise`` in torch ops on any device:
+
+        d     = sa x0 + sb n1 - n2                  the noised clip minus the fresh noise
+        y     = (Lf (x) Lh (x) Lw) d                along w, then h, then the frames
+        n_eff = n1 + (y - d) / sb                   <=>  sa x0 + sb n_eff = n2 + L (sa x0 + sb n1 - n2) = LPF(noised clip) + HPF(n2)
+
+    ``x0`` [1, 4, F, h, w] (the clean clip, 16-bit in the pipeline); ``n1`` (the noise the clip was generated from), ``n2`` (a fresh
+    draw) and the result [1, F, 4, h, w], the layout ``pano_noise_and_index`` draws in, in ``n1``'s dtype (float32; float64 for the
+    tests); the operators [F, F], [h, h], [w, w] from ``free_init_operator``, cast to that dtype.  A noise rather than a start latent
+    is returned so that ``kernels.noise_latents``, the perspective gather and the graphed steps run unchanged on it and both branches
+    begin from the same numbers.  ``sb <= 0`` is refused (pure signal has no noise to replace).  Only the Gaussian filter is offered:
+    Butterworth and ideal masks are not separable."""
+    if not float(sb) > 0.0:
+        raise ValueError(f"free_init_noise: sb={float(sb)} must be positive (pure signal has no noise to replace)")
+    if x0.dim() != 5 or n1.dim() != 5 or tuple(n1.shape) != (x0.shape[0], x0.shape[2], x0.shape[1], *x0.shape[3:]) or n2.shape != n1.shape:
+        raise ValueError(f"free_init_noise: x0 [1, C, F, h, w] and n1, n2 [1, F, C, h, w] expected, got {list(x0.shape)}, {list(n1.shape)}, "
+                         f"{list(n2.shape)}")
+    wdt = n1.dtype
+    Lf, Lh, Lw = (L.to(device=n1.device, dtype=wdt) for L in (Lf, Lh, Lw))
+    d = sa * x0.permute(0, 2, 1, 3, 4).to(wdt) + sb * n1 - n2.to(wdt)
+    y = torch.matmul(d, Lw.t())
+    y = torch.matmul(Lh, y)
+    y = torch.einsum("ij,bjchw->bichw", Lf, y)
+    return n1 + (y - d) / sb

@@ -27,6 +27,10 @@ surface, rebuilt for the MI355X:
   * a frame-interpolation pass (``init_latents`` / ``init_video`` with FEWER FRAMES than the run, ``init_retime``): the clean latent of
     a clip generated at a coarse frame stride is retimed once along its frame axis -- source frames land exactly on output frames; a
     looping clip is a ring -- in ONE kernel (``kernels.retime_pano_latent``) in front of the upscale.
+  * FreeInit passes (``free_init_iters`` > 1, arXiv 2312.07537): the whole schedule is run again from the previous pass's clean clip,
+    noised back to the first timestep with an EFFECTIVE noise that keeps the low spatio-temporal frequencies of the noised clip and takes
+    the high ones from a fresh draw (``kernels.free_init_noise``: three launches, each axis filtered with its own boundary -- longitude
+    periodic, latitude mirrored, frames periodic only on a looping clip); the captured step graph is replayed across the passes.
 
 CLIP text encoding and SAM feature extraction are outside the hot path: the
 pipeline uses ``text_encoder``/``tokenizer``/``image_encoder`` when given, and also accepts precomputed
@@ -181,6 +185,11 @@ class AnimationPipeline:
         start from consistent noise (pipeline...dual.py:361-387).  The index maps are frame-invariant and
         built once instead of 16 x 20 host-side map builds."""
         pano, idx, ok = self.pano_noise_and_index(bs, video_length, equi_h, equi_w, pers_h, pers_w, cameras, device)
+        return self.latents_from_noise(pano, idx, ok, latents_dtype)
+
+    def latents_from_noise(self, pano, idx, ok, latents_dtype=torch.float16):
+        """The second half of ``init_noise``: both start latents from the panorama noise and the tables of ``pano_noise_and_index``."""
+        bs, video_length, _, _, equi_h, equi_w = pano.shape
         flat = pano.squeeze(2).reshape(bs, video_length, 4, equi_h * equi_w)
         pers = flat[..., idx.reshape(-1)].reshape(bs, video_length, 4, *idx.shape) * ok   # b f c m h w
         return (pano.squeeze(2).permute(0, 2, 1, 3, 4).contiguous().to(latents_dtype),
@@ -325,7 +334,7 @@ class AnimationPipeline:
                  ip_plus_condition="image", prompt_embeds=None, sam_features=None, trace=None, frame_shard=None,
                  context_frames=None, context_overlap=4, context_weights="pyramid", guidance_rescale=0.0, context_loop=False,
                  init_latents=None, init_video=None, strength=1.0, regenerate_mask=None, init_resize="bicubic", init_retime=None,
-                 **kwargs):
+                 free_init_iters=1, free_init_d_s=0.25, free_init_d_t=0.25, **kwargs):
         """``frame_shard`` (imagine360_amd.dist.FrameShard): this rank denoises a contiguous chunk of the frames (BASELINE
         configs 4 / 5); all ranks must be called with the same seeds and inputs.  Noise is drawn for the whole clip and
         cut, the VAE encodes / the loop runs / the VAE decodes only the local frames, the motion modules exchange tokens
@@ -381,7 +390,25 @@ class AnimationPipeline:
         ``regenerate_mask=context.keyframe_mask(f, video_length, loop)`` pins the source frames and denoises only the in-betweens.
         The conditioning ``video_batch`` is the caller's, at the run's frame count.  Everything after the retime runs as for an init
         of the run's frame count, the RNG order is unchanged, and such an init never reaches the new code; an init with MORE
-        frames than the run raises ``ValueError`` (there is no temporal antialiasing filter)."""
+        frames than the run raises ``ValueError`` (there is no temporal antialiasing filter).
+        ``free_init_iters`` (1: off, the call without the keyword bit for bit), ``free_init_d_s`` / ``free_init_d_t``: FreeInit (arXiv
+        2312.07537; diffusers' ``enable_free_init``, Gaussian filter).  The count is of passes IN TOTAL.  Pass 0 is the call from pure
+        noise; its fp32 panorama noise n1 is kept as drawn.  Pass k >= 1 clones the clean panorama latent of pass k - 1, draws a fresh
+        panorama noise n2 (one ``_randn((1, F, 1, 4, h, w))`` at the head of the pass, then the per-step draws of any run), forms the
+        effective noise ``kernels.free_init_noise(x0, n1, n2, Lf, Lh, Lw, sa, sb)`` with ``(sa, sb) =
+        scheduler.noise_coefficients(steps[0])`` -- ``sa x0 + sb n_eff`` is the low-pass of the clip noised with n1 plus the high-pass of
+        n2 -- makes both start latents from it with ``kernels.noise_latents`` on the tables of pass 0, and runs the whole schedule
+        again.  The clip is noised to the FIRST TIMESTEP OF THE RUN, not to ``num_train_timesteps - 1`` as in diffusers: with the shipped
+        zero-terminal-SNR betas t = 999 is pure noise and would erase the clip.  The low-pass is three dense operators
+        (``pano_geometry.free_init_operator``), cut-off ``free_init_d_s`` along h and w and ``free_init_d_t`` along the frames (fractions
+        of Nyquist): w periodic (the +-180 degree seam), h mirrored (the poles), the frames periodic with ``context_loop`` and mirrored
+        otherwise.  The conditioning (masked latents and their posterior draws, text, SAM, masks) is built once and shared; a captured
+        step graph is restarted (``GraphedDenoiseStep.restart``), not captured again; ``trace`` / ``callback`` see every pass, step
+        indices restart per pass; context windows, ``context_loop``, ``eta``, ``guidance_rescale``, a multistep scheduler and
+        ``rng="host"`` work across passes.  ``pipe.free_init_passes``: the clean panorama latent of every pass (one clone each; with
+        ``free_init_iters=1`` the one of ``last_latents``); only the last pass is decoded.  Refused (``ValueError``): ``init_latents`` /
+        ``init_video`` / ``strength != 1`` / ``regenerate_mask`` (FreeInit re-noises its own result from pure noise), ``frame_shard``,
+        ``free_init_iters < 1``.  Whether the passes improve a clip can only be judged with trained weights."""
         device = self.device
         vb = video_batch
         plan = None
@@ -405,6 +432,19 @@ class AnimationPipeline:
         if init_retime is not None and init_retime not in G.RETIME_MODES:
             raise ValueError(f"init_retime must be None or one of {sorted(G.RETIME_MODES)}, got {init_retime!r}")
         has_init = init_latents is not None or init_video is not None
+        if not isinstance(free_init_iters, int) or isinstance(free_init_iters, bool) or free_init_iters < 1:
+            raise ValueError(f"free_init_iters counts the passes in total and must be an int >= 1, got {free_init_iters!r}")
+        if free_init_iters > 1:
+            if has_init or regenerate_mask is not None or float(strength) != 1.0:
+                raise ValueError("free_init_iters > 1 cannot be combined with init_latents / init_video / strength != 1 / regenerate_mask "
+                                 "(FreeInit re-noises the result of its own first pass, which starts from pure noise and runs the whole "
+                                 "schedule)")
+            if frame_shard is not None:
+                raise ValueError("free_init_iters > 1 cannot be combined with frame_shard (the filter along the frames spans the frames of "
+                                 "all ranks and would need a gather between the passes, which is not implemented)")
+            if not (float(free_init_d_s) > 0.0 and float(free_init_d_t) > 0.0):
+                raise ValueError(f"free_init_d_s={free_init_d_s} and free_init_d_t={free_init_d_t} must be positive (cut-offs as fractions of "
+                                 "Nyquist)")
         if regenerate_mask is not None and not has_init:
             raise ValueError("regenerate_mask needs init_latents or init_video (the clip whose unmasked part is kept)")
         if regenerate_mask is not None and frame_shard is not None:
@@ -447,9 +487,31 @@ class AnimationPipeline:
             pano_latent, pers_latent, steps_host, *region = self.init_from_clip(x0, strength, f, H // 8, W // 8, ps // 8, ps // 8, cameras,
                                                                                 device, latents_dtype, regenerate_mask=keep_mask)
             region = region[0] if region else None             # (KeepRegion)
+        elif free_init_iters > 1:
+            # pass 0 is init_noise, its two halves called here so that the panorama noise is kept in fp32 as drawn
+            noise1, fi_idx, fi_ok = self.pano_noise_and_index(1, f, H // 8, W // 8, ps // 8, ps // 8, cameras, device)
+            pano_latent, pers_latent = self.latents_from_noise(noise1, fi_idx, fi_ok, latents_dtype)
+            region = None
         else:
             pano_latent, pers_latent = self.init_noise(1, f, H // 8, W // 8, ps // 8, ps // 8, cameras, device, latents_dtype)
             region = None
+        next_pass, passes = None, []
+        if free_init_iters > 1:
+            noise1, fi_idx, fi_ok = noise1.squeeze(2), fi_idx.to(torch.int32), fi_ok.to(torch.uint8)
+            fi_ops = [G.free_init_operator(n, d, per).to(torch.float32).to(device)
+                      for n, d, per in ((f, free_init_d_t, bool(context_loop)), (H // 8, free_init_d_s, False), (W // 8, free_init_d_s, True))]
+
+            def next_pass(pano_now, pers_now):
+                """Behind the last step of a pass: its clean panorama latent is kept; None after the last pass, else the two start
+                latents of the next one."""
+                x0 = pano_now.clone()                      # (a graphed step returns its static buffers)
+                passes.append(x0)
+                if len(passes) >= free_init_iters:
+                    return None
+                noise2 = self._randn((1, f, 1, 4, H // 8, W // 8), device).squeeze(2)
+                sqrt_a, sqrt_b = self.scheduler.noise_coefficients(steps_host[0])
+                n_eff = kernels.free_init_noise(x0, noise1, noise2, *fi_ops, sqrt_a, sqrt_b)
+                return kernels.noise_latents(x0, n_eff, fi_idx, fi_ok, sqrt_a, sqrt_b)
         hist = None
         if hasattr(self.scheduler, "new_history"):
             # a multistep scheduler: the run's timestep list fixes its coefficients, and each branch's latent owns its x0 history
@@ -498,7 +560,7 @@ class AnimationPipeline:
                               reference_images_clip_feat_pers=feat_pers, relative_position_tensor=rel, pitchs_tensor=pitch)
                 pano_latent, pers_latent = self._windowed_loop(plan, inputs, cameras, pano_latent, pers_latent, steps_host, ts_dev,
                                                                guidance_scale_text, use_fps_condition, eta, generator, trace,
-                                                               callback, callback_steps, guidance_rescale, region, hist)
+                                                               callback, callback_steps, guidance_rescale, region, hist, next_pass)
             graphed = None
             import torch.distributed as tdist
             capturable = sh is None or (tdist.is_initialized() and tdist.get_backend(sh.group) == "nccl")     # RCCL all-to-alls are stream ops
@@ -513,28 +575,37 @@ class AnimationPipeline:
                     stoch["keep"] = region
                 graphed = GraphedDenoiseStep(self.mv_base_model, self.scheduler, inputs, cameras, pano_latent, pers_latent,
                                              guidance_scale_text, use_fps=use_fps_condition, warmup=1, guidance_rescale=guidance_rescale, **stoch)       # one eager step fills every cache
-            for i, t in enumerate(self.progress_bar(steps_host) if plan is None else ()):
+            while plan is None:                 # one round per pass: once without free_init_iters
+                for i, t in enumerate(self.progress_bar(steps_host)):
+                    if graphed is not None:
+                        pano_latent, pers_latent = graphed.step(t)
+                        continue
+                    in_pano[:, :4] = pano_latent
+                    in_pers[:, :, :4] = pers_latent
+                    pred_pers, pred_pano = self.mv_base_model(
+                        latents=in_pers, pano_latent=in_pano, timestep=ts_dev[i], prompt_embd=text_pers,
+                        pano_prompt_embd=text_pano, cameras=cameras, use_fps_condition=use_fps_condition,
+                        use_ip_plus_cross_attention=use_ip_plus_cross_attention, fps_tensor_pano=fps_pano, fps_tensor_pers=fps_pers,
+                        reference_images_clip_feat_pano=feat_pano, reference_images_clip_feat_pers=feat_pers,
+                        relative_position_tensor=rel, pitchs_tensor=pitch)
+                    pano_latent = self._cfg_step(pred_pano, guidance_scale_text, t, pano_latent, eta, generator, sh, 2, guidance_rescale,
+                                                 **({} if hist is None else dict(history=hist[0])))
+                    pers_latent = self._cfg_step(pred_pers, guidance_scale_text, t, pers_latent, eta, generator, sh, 3, guidance_rescale,
+                                                 **({} if hist is None else dict(history=hist[1])))
+                    if region is not None:
+                        region.apply(pano_latent, pers_latent, i)
+                    if trace is not None:
+                        trace.append(pano_latent.clone())
+                    if callback is not None and i % callback_steps == 0:
+                        callback(i, t, pano_latent)
+                # (FreeInit) the start latents of the next pass; a captured step is restarted, a multistep history needs no reset (the
+                # first step of a run is first order and only writes it)
+                start = None if next_pass is None else next_pass(pano_latent, pers_latent)
+                if start is None:
+                    break
                 if graphed is not None:
-                    pano_latent, pers_latent = graphed.step(t)
-                    continue
-                in_pano[:, :4] = pano_latent
-                in_pers[:, :, :4] = pers_latent
-                pred_pers, pred_pano = self.mv_base_model(
-                    latents=in_pers, pano_latent=in_pano, timestep=ts_dev[i], prompt_embd=text_pers,
-                    pano_prompt_embd=text_pano, cameras=cameras, use_fps_condition=use_fps_condition,
-                    use_ip_plus_cross_attention=use_ip_plus_cross_attention, fps_tensor_pano=fps_pano, fps_tensor_pers=fps_pers,
-                    reference_images_clip_feat_pano=feat_pano, reference_images_clip_feat_pers=feat_pers,
-                    relative_position_tensor=rel, pitchs_tensor=pitch)
-                pano_latent = self._cfg_step(pred_pano, guidance_scale_text, t, pano_latent, eta, generator, sh, 2, guidance_rescale,
-                                             **({} if hist is None else dict(history=hist[0])))
-                pers_latent = self._cfg_step(pred_pers, guidance_scale_text, t, pers_latent, eta, generator, sh, 3, guidance_rescale,
-                                             **({} if hist is None else dict(history=hist[1])))
-                if region is not None:
-                    region.apply(pano_latent, pers_latent, i)
-                if trace is not None:
-                    trace.append(pano_latent.clone())
-                if callback is not None and i % callback_steps == 0:
-                    callback(i, t, pano_latent)
+                    graphed.restart(*start)
+                pano_latent, pers_latent = start
 
             video = self.decode_latents(self.padding_pano(pano_latent, latent=True))
             video = self.unpadding_pano(video)
@@ -546,6 +617,7 @@ class AnimationPipeline:
             if output_type == "tensor":
                 video = torch.from_numpy(np.ascontiguousarray(video))
             self.last_latents = (pano_latent, pers_latent)
+            self.free_init_passes = passes if free_init_iters > 1 else [pano_latent]
             return AnimationPipelineOutput(videos=video) if return_dict else video
         finally:
             if sh is not None:
@@ -560,13 +632,14 @@ class AnimationPipeline:
         return self.scheduler.fused_cfg_step(u, c, g, t, latent, guidance_rescale=guidance_rescale, **history)
 
     def _windowed_loop(self, plan, inputs, cameras, pano_latent, pers_latent, steps_host, ts_dev, g, use_fps, eta, generator,
-                       trace, callback, callback_steps, guidance_rescale=0.0, keep=None, hist=None):
+                       trace, callback, callback_steps, guidance_rescale=0.0, keep=None, hist=None, next_pass=None):
         """The denoising loop over sliding temporal context windows: per step one forward per window (slot order), then ONE
         blend + CFG + DDIM kernel per branch, panorama first.  RNG: as len(plan) successive calls of the model, then (eta > 0)
         the whole clip's panorama and perspective variance noise.  Captured in one hipGraph under the conditions of the
         one-block loop (graph_step.GraphedWindowedStep), issued eagerly otherwise.  ``keep`` (KeepRegion): its blend of the whole
         clip after the two windows kernels of every step.  ``hist``: the (panorama, perspective) x0 histories of a multistep scheduler for the
-        eager loop (the graphed step owns its own)."""
+        eager loop (the graphed step owns its own).  ``next_pass`` (FreeInit): called with the two latents behind the last step; None ends the
+        loop, else it returns the start latents of another run of the whole schedule (the captured step is restarted, not captured again)."""
         from .context import ip_cache_slots
         mv, sch = self.mv_base_model, self.scheduler
         with ip_cache_slots(mv, len(plan)):
@@ -575,27 +648,35 @@ class AnimationPipeline:
                 graphed = GraphedWindowedStep(mv, sch, inputs, cameras, pano_latent, pers_latent, g, plan, use_fps=use_fps, warmup=1,
                                               eta=eta, generator=generator, guidance_rescale=guidance_rescale,
                                               **({} if keep is None else dict(keep=keep)))
-                for t in self.progress_bar(steps_host):
-                    pano_latent, pers_latent = graphed.step(t)
-                return pano_latent, pers_latent
+                while True:
+                    for t in self.progress_bar(steps_host):
+                        pano_latent, pers_latent = graphed.step(t)
+                    start = None if next_pass is None else next_pass(pano_latent, pers_latent)
+                    if start is None:
+                        return pano_latent, pers_latent
+                    graphed.restart(*start)
             static = plan.static_inputs(inputs)
             preds_pers, preds_pano = plan.pred_buffers(pano_latent, pers_latent)
-            for i, t in enumerate(self.progress_bar(steps_host)):
-                inputs["pano_latent"][:, :4] = pano_latent
-                inputs["latents"][:, :, :4] = pers_latent
-                plan.forward(mv, inputs, static, cameras, ts_dev[i], use_fps, preds_pers, preds_pano)
-                mdt = mv.unet.dtype
-                kw = dict(eta=eta, guidance_rescale=guidance_rescale, ring=plan.loop)
-                z = variance_noise(sch, pano_latent, mdt, generator, self.rng) if eta > 0 else None
-                pano_latent = sch.fused_cfg_step_windows(preds_pano, plan.starts_dev, plan.weights, g, t, pano_latent, noise=z, **kw,
-                                                         **({} if hist is None else dict(history=hist[0])))
-                z = variance_noise(sch, pers_latent, mdt, generator, self.rng, frame_dim=3) if eta > 0 else None
-                pers_latent = sch.fused_cfg_step_windows(preds_pers, plan.starts_dev, plan.weights, g, t, pers_latent, noise=z, **kw,
-                                                         **({} if hist is None else dict(history=hist[1])))
-                if keep is not None:
-                    keep.apply(pano_latent, pers_latent, i)
-                if trace is not None:
-                    trace.append(pano_latent.clone())
-                if callback is not None and i % callback_steps == 0:
-                    callback(i, t, pano_latent)
-        return pano_latent, pers_latent
+            while True:
+                for i, t in enumerate(self.progress_bar(steps_host)):
+                    inputs["pano_latent"][:, :4] = pano_latent
+                    inputs["latents"][:, :, :4] = pers_latent
+                    plan.forward(mv, inputs, static, cameras, ts_dev[i], use_fps, preds_pers, preds_pano)
+                    mdt = mv.unet.dtype
+                    kw = dict(eta=eta, guidance_rescale=guidance_rescale, ring=plan.loop)
+                    z = variance_noise(sch, pano_latent, mdt, generator, self.rng) if eta > 0 else None
+                    pano_latent = sch.fused_cfg_step_windows(preds_pano, plan.starts_dev, plan.weights, g, t, pano_latent, noise=z, **kw,
+                                                             **({} if hist is None else dict(history=hist[0])))
+                    z = variance_noise(sch, pers_latent, mdt, generator, self.rng, frame_dim=3) if eta > 0 else None
+                    pers_latent = sch.fused_cfg_step_windows(preds_pers, plan.starts_dev, plan.weights, g, t, pers_latent, noise=z, **kw,
+                                                             **({} if hist is None else dict(history=hist[1])))
+                    if keep is not None:
+                        keep.apply(pano_latent, pers_latent, i)
+                    if trace is not None:
+                        trace.append(pano_latent.clone())
+                    if callback is not None and i % callback_steps == 0:
+                        callback(i, t, pano_latent)
+                start = None if next_pass is None else next_pass(pano_latent, pers_latent)
+                if start is None:
+                    return pano_latent, pers_latent
+                pano_latent, pers_latent = start

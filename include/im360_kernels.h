@@ -447,6 +447,25 @@ int im360_resize_pano_latent(const void* x, void* out, int64_t C, int64_t F, int
 int im360_retime_pano_latent(const void* x, void* out, int64_t C, int64_t f, int64_t F, int64_t hw, int mode, int loop, int dtype,
                              void* stream);
 
+/* ---- FreeInit's re-noising (AnimationPipeline free_init_iters > 1; arXiv 2312.07537, diffusers' free_init_utils: _get_free_init_freq_filter
+ * / _apply_freq_filter), three launches: the EFFECTIVE NOISE n_eff under which sa x0 + sb n_eff = n2 + L (sa x0 + sb n1 - n2), i.e. the
+ * low-pass of the noised clip plus the high-pass of the fresh noise n2, L = Lf (x) Lh (x) Lw.
+ *   d = fma(sa, x0, fma(sb, n1, -n2));   y = L d (along w, then h, then F);   out = fma(y - d, inv_sb, n1)                   all fp32
+ * x0 [C, F, H W] of one 16-bit dtype (the clean clip); n1, n2, out fp32 [F, C, H W]; Lf [F, F], Lh [H, H], Lw [W, W] fp32, row i the
+ * weights of output i (pano_geometry.free_init_operator in fp64, rounded once; dense, so each axis has its own boundary: periodic
+ * longitude, mirrored latitude, frames periodic on a looping clip and mirrored otherwise -- fftn would wrap all three); ws: fp32
+ * workspace of ws_elems >= 2 C F H W elements; inv_sb = 1 / sb formed in fp64 by the caller.
+ * Every dot product is one fp32 fma chain from 0 over j = 0 .. n - 1; no atomics, deterministic; identity operators give out == n1 bit
+ * for bit.  Launch 1 forms d on the fly (64 x 64 slabs in LDS, lane = row); launches 2 and 3 read columns from global memory (lane =
+ * column, no LDS), launch 3 forms d again and writes out: no elementwise launch, no whole plane in LDS.  Four elements per unit (16-byte
+ * fp32 accesses, 8-byte loads of x0) when W % 4 == 0 and the pointers are aligned for it, a scalar path otherwise, the same bits on both.
+ * Refused: a null pointer, a size <= 0, C F H W >= 2^31, a workspace that is too small, sb <= 0 or inv_sb <= 0, a misaligned pointer
+ * (2 bytes for x0, 4 for fp32), out or ws overlapping each other or an input, 2^24 workgroups in a launch, an unknown dtype.
+ * Replaces: nothing in the reference (one pass from white noise); diffusers' fftn -> fftshift -> Gaussian mask -> ifftn round trip. */
+int im360_free_init_noise(const void* x0, const float* n1, const float* n2, const float* Lf, const float* Lh, const float* Lw, float* out,
+                          float* ws, int64_t ws_elems, int64_t C, int64_t F, int64_t H, int64_t W, float sa, float sb, float inv_sb,
+                          int dtype, void* stream);
+
 /* y[r] = LayerNorm(x[r] + pre[r % pre_period]) * gamma + beta + post[(r / post_div) % post_mod] on token rows
  * [rows, C]; pre / post are optional [*, C] tables (the WarpAttn spherical PE added before norm1, the motion
  * module's frame PE added after the norm).

@@ -36,7 +36,12 @@ device events, with the bytes each has to move computed from the shapes.  Prints
                                                       # the run: kernels.retime_pano_latent; context windows of 16, --loop: on a ring) at this strength,
                                                       # next to ONE call from pure noise with --frames frames, alternated --rounds times after one
                                                       # warm-up of every shape; and kernels.retime_pano_latent at the cfg2 latent size, both modes,
-                                                      # next to the eager definition pano_geometry.retime_pano_latent on the GPU"""
+                                                      # next to the eager definition pano_geometry.retime_pano_latent on the GPU
+    python tools/bench_context.py --free-init 3 [--frames 16] [--num-steps 25] [--loop]
+                                                      # FreeInit passes: whole pipeline calls with free_init_iters = N next to the call without it,
+                                                      # alternated --rounds times after one warm-up of each (context windows of 16 when --frames > 16,
+                                                      # --loop: on a ring, the frame axis of the filter periodic); and kernels.free_init_noise at the
+                                                      # size of that clip next to the eager definition pano_geometry.free_init_noise on the GPU"""
 import argparse
 import json
 import os
@@ -401,6 +406,84 @@ def retime_bench(args, sch, dev, dt):
     return res
 
 
+def time_free_init(frames, hw, loop, sch, dev, dt, iters, rounds=5):
+    """Device-event time of ``kernels.free_init_noise`` (three launches; its result and workspace allocated per call) next to the eager
+    definition on the GPU, alternated round by round after a warm-up round; min / median / max."""
+    from imagine360_amd import pano_geometry as G
+    x0 = torch.randn(1, 4, frames, *hw, device=dev).to(dt)
+    n1, n2 = (torch.randn(1, frames, 4, *hw, device=dev) for _ in range(2))
+    ops = [G.free_init_operator(n, 0.25, per).to(torch.float32).to(dev) for n, per in ((frames, bool(loop)), (hw[0], False), (hw[1], True))]
+    sa, sb = sch.noise_coefficients(sch._timesteps_host[0])
+    fns = dict(kernel=lambda: kernels.free_init_noise(x0, n1, n2, *ops, sa, sb), eager=lambda: G.free_init_noise(x0, n1, n2, sa, sb, *ops))
+    times = {k: [] for k in fns}
+    for r in range(rounds + 1):
+        for k, fn in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(iters):
+                fn()
+            b.record()
+            torch.cuda.synchronize()
+            if r:
+                times[k].append(a.elapsed_time(b) / iters * 1e3)
+    n = n1.numel()
+    out = {k: dict(us_min=min(v), us_median=statistics.median(v), us_max=max(v)) for k, v in times.items()}
+    out.update(tensor=list(n1.shape), ring=bool(loop), sa=sa, sb=sb, fma_per_call=n * (frames + hw[0] + hw[1]),
+               max_abs_diff_vs_eager=float((fns["kernel"]() - fns["eager"]()).abs().max()),
+               note="three launches; the working set (2 MB per fp32 tensor at cfg2) is cache-resident")
+    return out
+
+
+def free_init_bench(args, sch, dev, dt):
+    """--free-init N: whole pipeline calls (encode, capture, N passes of the loop, decode of the last) next to the plain call; host clock
+    around a call that ends in a device synchronise."""
+    import random
+
+    from imagine360_amd.pipeline import AnimationPipeline
+    frames, n = args.frames, args.free_init
+    assert n >= 2, "--free-init N counts the passes in total: N >= 2"
+    res = dict(tool="bench_context --free-init", free_init_iters=n, frames=frames, num_inference_steps=args.num_steps, pano_hw=PANO_HW,
+               dtype="bfloat16", device=torch.cuda.get_device_name(0), sampler=args.sampler)
+    sch.set_timesteps(args.num_steps)
+    res["free_init_noise"] = time_free_init(frames, PANO_HW, args.loop, sch, dev, dt, args.kernel_iters)
+    if args.kernel_only:
+        return res
+    mv = configs.build_mv_model(1, device=dev, dtype=dt, xformers=True)
+    mv.dual_stream, mv.warp_streams = True, True
+    vae = configs.build_vae(1, device=dev, dtype=dt)
+    pipe = AnimationPipeline(vae, None, None, mv.unet, mv.pano_unet, mv, type(sch)(**configs.NOISE_SCHEDULER_KWARGS), None, "SAM").to(dev)
+    pipe._no_progress = True
+    vb = synthetic.video_batch(frames=frames, pano_hw=(PANO_HW[0] * 8, PANO_HW[1] * 8), seed=1)
+    cond = synthetic.conditioning(frames=max(frames, 16), seed=1)
+    windows = dict(context_frames=LENGTH, context_overlap=OVERLAP, context_loop=args.loop) if frames > LENGTH else {}
+    res["windows"] = windows
+
+    def call(**kw):
+        torch.manual_seed(21)
+        random.seed(21)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        vid = pipe("synthetic", num_inference_steps=args.num_steps, guidance_scale_text=7.5, negative_prompt="", latents_dtype=dt,
+                   video_batch=vb, use_outpaint=True, use_ip_plus_cross_attention=True, use_fps_condition=True, ip_plus_condition="video",
+                   prompt_embeds=(cond["text_pano"], cond["text_pers"]), sam_features=(cond["sam_pano"], cond["sam_pers"]), **windows, **kw).videos
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, bool(torch.isfinite(vid).all())
+
+    res["warm_up"] = dict(plain_ms=call()[0], free_init_ms=call(free_init_iters=n)[0])
+    print("warm-up done", file=sys.stderr, flush=True)
+    runs, fin = dict(plain=[], free_init=[]), True
+    for _ in range(args.rounds):
+        for k, kw in (("plain", {}), ("free_init", dict(free_init_iters=n))):
+            ms, ok = call(**kw)
+            runs[k].append(ms)
+            fin = fin and ok
+    res["plain"] = dict(call_ms=runs["plain"], call_ms_min=min(runs["plain"]))
+    res["free_init"] = dict(call_ms=runs["free_init"], call_ms_min=min(runs["free_init"]))
+    res["ms_per_extra_pass"] = (res["free_init"]["call_ms_min"] - res["plain"]["call_ms_min"]) / (n - 1)
+    res["finite"] = fin
+    return res
+
+
 def hires_bench(args, sch, dev, dt):
     """--init-scale N: the two-pass run (1 / N of the size from pure noise, then the full size from its latent at --strength) next to one
     run from pure noise at the full size; whole pipeline calls (encode, loop, decode), host clock around a call that ends in a device
@@ -555,6 +638,8 @@ def main():
                     help="with --strength: the hi-res pass -- a first call at 1/N of --pano-hw, a second call at --pano-hw from its latent -- next to one call from pure noise at --pano-hw")
     ap.add_argument("--init-frames", type=int, default=None,
                     help="with --strength: the frame-interpolation pass -- a first call with this many frames, a second call with --frames frames from its latent -- next to one call from pure noise with --frames frames")
+    ap.add_argument("--free-init", type=int, default=None,
+                    help="FreeInit: pipeline calls with free_init_iters = N next to the plain call (--frames, --num-steps, --loop), and the filter kernel against its eager definition")
     ap.add_argument("--pano-hw", type=int, nargs=2, default=[128, 256], metavar=("H", "W"), help="--init-scale: latent size of the full-size run (default: cfg5)")
     ap.add_argument("--sampler", choices=["ddim", "dpmpp2m"], default="ddim", help="the scheduler of every step and call (dpmpp2m: DPM-Solver++ 2M)")
     ap.add_argument("--out", default=None)
@@ -566,6 +651,9 @@ def main():
     sch = (DPMSolverMultistepScheduler if args.sampler == "dpmpp2m" else DDIMScheduler)(**configs.NOISE_SCHEDULER_KWARGS)
     sch.set_timesteps(25)
     ts_host = [int(t) for t in sch._timesteps_host]
+    if args.free_init is not None:
+        assert args.strength is None and args.init_scale is None and args.init_frames is None, "--free-init N goes alone (FreeInit starts from pure noise)"
+        return emit(free_init_bench(args, sch, dev, dt), args.out)
     if args.init_frames is not None:
         assert args.strength is not None and args.init_scale is None, "--init-frames f goes with --strength (and not with --init-scale)"
         return emit(retime_bench(args, sch, dev, dt), args.out)

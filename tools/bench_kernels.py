@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Per-kernel micro-benchmarks at BASELINE cfg2 shapes (run on the MI355X):
 
-    python tools/bench_kernels.py [attn] [conv] [temporal] [ln] [gn] [sampler_step] [--iters N]
+    python tools/bench_kernels.py [attn] [conv] [temporal] [ln] [gn] [sampler_step] [free_init_noise] [--iters N]
 
 Prints achieved TFLOP/s (MFMA kernels, vs 2500 dense bf16) or GB/s (HBM kernels, vs 8000) per shape.
 Usable under `rocprofv3 --pmc ...` for counters of one kernel class.
@@ -473,6 +473,36 @@ def bench_sampler_step(iters):
             base = base or ts[0]
             print(f"sampler_step {name} {n:8d} elements  {label:28s}: {ts[0] * 1e6:7.2f} us min {ts[2] * 1e6:7.2f} us median  "
                   f"{by / 1e6:6.2f} MB  {by / ts[0] / 1e9:6.0f} GB/s  {ts[0] / base:4.2f}x cfg_ddim_step")
+
+
+def bench_free_init_noise(iters):
+    """FreeInit's effective noise on the cfg2 panorama latent (16 frames, 64 x 128; open clip and ring): the three launches of
+    ``kernels.free_init_noise`` against the eager definition ``pano_geometry.free_init_noise`` on the GPU (fp32 matmuls), device events,
+    allocation of the result and the workspace included; 5 rounds alternated, min / median.  A JSON line per row, for profiles/."""
+    import json
+    from imagine360_amd import pano_geometry as G
+    F, h, w = 16, 64, 128
+    x0 = rn(1, 4, F, h, w)
+    n1, n2 = (torch.randn(1, F, 4, h, w, device=DEV) for _ in range(2))
+    sa, sb = 0.0627, 0.998                                    # about the first of 25 timesteps
+    for loop in (False, True):
+        ops = [G.free_init_operator(n, d, per).to(torch.float32).to(DEV) for n, d, per in ((F, 0.25, loop), (h, 0.25, False), (w, 0.25, True))]
+        kern = lambda: K.free_init_noise(x0, n1, n2, *ops, sa, sb)
+        eager = lambda: G.free_init_noise(x0, n1, n2, sa, sb, *ops)
+        diff = float((kern() - eager()).abs().max())
+        tk, te = [], []
+        for _ in range(5):
+            tk.append(timeit(kern, iters))
+            te.append(timeit(eager, iters))
+        tk.sort(), te.sort()
+        n = n1.numel()
+        flops = 2.0 * n * (F + h + w)
+        row = dict(bench="free_init_noise", shape=[1, 4, F, h, w], dtype="bfloat16", ring=loop, iters=iters, kernel_us=[t * 1e6 for t in (tk[0], tk[2], tk[4])],
+                   eager_us=[t * 1e6 for t in (te[0], te[2], te[4])], max_abs_diff_vs_eager=diff, gflops_per_call=flops / 1e9,
+                   kernel_tflops=flops / tk[0] / 1e12)
+        print(f"free_init_noise {'ring' if loop else 'open'} {n:8d} elements: kernel {tk[0] * 1e6:7.2f} us min {tk[2] * 1e6:7.2f} us median  "
+              f"eager {te[0] * 1e6:7.2f} us min {te[2] * 1e6:7.2f} us median  {flops / tk[0] / 1e12:5.2f} TFLOP/s fp32 fma  max |diff| {diff:.2e}")
+        print("JSON", json.dumps(row))
 
 
 if __name__ == "__main__":
