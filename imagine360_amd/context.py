@@ -90,6 +90,29 @@ def keyframe_mask(f, F, loop=False):
     return m
 
 
+def keyframe_strength(f, F, loop=False, floor=0.0):
+    """The soft sibling of ``keyframe_mask`` for ``regenerate_mode="release"``: a strength map [1, F, 1, 1, 1] (float32) that is 0
+    (pinned to the end) at ``keyframe_frames(f, F, loop)`` and rises linearly with the distance in frames to the nearest source
+    frame, reaching 1 midway between two neighbouring source frames -- an in-between next to a keyframe is released late and
+    changes little, the one in the middle of a gap is free for the whole run.  On a ring (``loop``) the distance wraps: the gap
+    behind the last source frame closes at frame 0.  ``floor`` in [0, 1]: the lowest value a frame that is NOT a source frame may get
+    (every in-between is then free for at least the last ``floor`` of the steps)."""
+    floor = float(floor)
+    if not 0.0 <= floor <= 1.0:
+        raise ValueError(f"keyframe_strength: floor must be in [0, 1], got {floor}")
+    F = int(F)
+    keys = keyframe_frames(f, F, loop)
+    m = torch.zeros(1, F, 1, 1, 1, dtype=torch.float32)
+    ends = keys + [keys[0] + F] if loop else keys
+    for a, b in zip(ends[:-1], ends[1:]):                       # the frames strictly between two neighbouring source frames
+        for j in range(a + 1, b):
+            m[0, j % F] = max(floor, min(2.0 * min(j - a, b - j) / (b - a), 1.0))
+    if not loop:
+        # (an open clip starts and ends on a source frame, keyframe_frames: nothing lies outside the gaps)
+        assert keys[0] == 0 and keys[-1] == F - 1
+    return m
+
+
 class WindowPlan:
     """The windows of one clip: ``starts`` (host ints), ``length``, the device tables the blend kernel reads, and the per-window
     model inputs.  ``inputs``: the keyword tensors of MultiViewBaseModel.forward for the WHOLE clip.  ``loop``: the windows of a

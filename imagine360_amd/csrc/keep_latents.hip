@@ -19,6 +19,11 @@
 // workgroups.  V = 8: 16-byte lanes in both passes (HW % 8 == 0, Q % 8 == 0, every pointer aligned for its widest access; a group of
 // eight that changes nothing is not stored); V = 1: scalar.  idx is clamped into [0, HW) (plane_index).
 // coef (device float[2], may be null): sa, sb read by the kernel instead of the arguments (graph replay).
+//
+// RELEASE (AnimationPipeline regenerate_mode="release"; Differential Diffusion, arXiv 2306.00950): the mask is a per-pixel strength s and
+// nothing is averaged -- an element is PINNED (`known`, bit for bit, the w <= 0 end of blend) while s <= tau and FREE (bits untouched, the
+// w >= 1 end) otherwise; the compare is in fp32, tau is the host's scheduler.release_threshold of the step.  The same kernel, paths and
+// stores; `free` takes the place of `w >= 1` and the select that of the fma.  coef is then float[3] = (sa, sb, tau).
 #include "latent_plane.h"
 
 namespace im360 {
@@ -31,16 +36,28 @@ template <typename T> __device__ __forceinline__ uint16_t keep_blend(uint16_t x,
     return bits16<T>(fma_f32(w, bits16_f32<T>(x) - kf, kf));
 }
 
-template <typename T, int V, bool LDS>
+// RELEASE: is the element left alone (s > tau; a NaN strength is free) / BLEND: w >= 1
+template <bool RELEASE> __device__ __forceinline__ bool keep_untouched(float w, float tau) {
+    if constexpr (RELEASE) return !(w <= tau);
+    else return w >= 1.0f;
+}
+// the element after the launch: the select of release mode, or blend
+template <typename T, bool RELEASE> __device__ __forceinline__ uint16_t keep_element(uint16_t x, uint16_t k, float w, float tau) {
+    if constexpr (RELEASE) return w <= tau ? k : x;
+    else return keep_blend<T>(x, k, w);
+}
+
+template <typename T, int V, bool LDS, bool RELEASE>
 __global__ __launch_bounds__(256) void keep_latents_kernel(T* __restrict__ pano, T* __restrict__ pers, const T* __restrict__ x0,
                                                            const float* __restrict__ noise, const float* __restrict__ mask,
                                                            const int* __restrict__ idx, const uint8_t* __restrict__ ok, int F, int C,
-                                                           int HW, int M, int Q, float sa, float sb, const float* __restrict__ coef) {
+                                                           int HW, int M, int Q, float sa, float sb, float tau, const float* __restrict__ coef) {
     extern __shared__ __attribute__((aligned(16))) char keep_plane_smem[];
     uint16_t* plane = (uint16_t*)keep_plane_smem;             // [HW] rounded `known` of this (c, f) plane (LDS path only)
     if (coef) {
         sa = coef[0];
         sb = coef[1];
+        if constexpr (RELEASE) tau = coef[2];
     }
     const int c = blockIdx.x / F, f = blockIdx.x - c * F;
     const long xb = (long)blockIdx.x * HW;                    // (c F + f) HW: x0, pano
@@ -64,13 +81,13 @@ __global__ __launch_bounds__(256) void keep_latents_kernel(T* __restrict__ pano,
             if constexpr (LDS) ((uint4*)plane)[i] = kv;
             bool all_new = true;
 #pragma unroll
-            for (int e = 0; e < 8; ++e) all_new = all_new && w[e] >= 1.0f;
+            for (int e = 0; e < 8; ++e) all_new = all_new && keep_untouched<RELEASE>(w[e], tau);
             if (!all_new) {
                 uint16_t k[8], cur[8];
                 bits16_unpack(kv, k);
                 bits16_unpack(((const uint4*)pp)[i], cur);
 #pragma unroll
-                for (int e = 0; e < 8; ++e) cur[e] = keep_blend<T>(cur[e], k[e], w[e]);
+                for (int e = 0; e < 8; ++e) cur[e] = keep_element<T, RELEASE>(cur[e], k[e], w[e], tau);
                 ((uint4*)pp)[i] = bits16_pack(cur);
             }
         }
@@ -79,7 +96,7 @@ __global__ __launch_bounds__(256) void keep_latents_kernel(T* __restrict__ pano,
             const uint16_t k = bits16<T>(noised(to_f32(xp[i]), np[i], sa, sb));
             if constexpr (LDS) plane[i] = k;
             const float w = mp[i];
-            if (!(w >= 1.0f)) pp[i] = keep_blend<T>(pp[i], k, w);
+            if (!keep_untouched<RELEASE>(w, tau)) pp[i] = keep_element<T, RELEASE>(pp[i], k, w, tau);
         }
     }
     if constexpr (LDS) __syncthreads();
@@ -90,11 +107,11 @@ __global__ __launch_bounds__(256) void keep_latents_kernel(T* __restrict__ pano,
         if (!valid) return cur;
         const unsigned p = plane_index(id, HW);
         const float w = mp[p];
-        if (w >= 1.0f) return cur;
+        if (keep_untouched<RELEASE>(w, tau)) return cur;
         uint16_t k;
         if constexpr (LDS) k = plane[p];
         else k = bits16<T>(noised(to_f32(xp[p]), np[p], sa, sb));
-        return keep_blend<T>(cur, k, w);
+        return keep_element<T, RELEASE>(cur, k, w, tau);
     };
     const long CF = (long)C * F;
     const int MQ = M * Q;
@@ -128,6 +145,29 @@ __global__ __launch_bounds__(256) void keep_latents_kernel(T* __restrict__ pano,
     }
 }
 
+// the common body of the two entry points under the caller's name `who`
+template <bool RELEASE>
+static int keep_launch(const char* who, void* pano, void* pers, const void* x0, const float* noise, const float* mask, const int32_t* idx,
+                       const uint8_t* ok, int64_t F, int64_t C, int64_t HW, int64_t M, int64_t Q, float sqrt_a, float sqrt_b, float tau, int dtype,
+                       void* stream, const void* coef_dev) {
+    IM360_CHECK_ARG(pano && pers && x0 && noise && mask && idx && ok, "%s: null pointer", who);
+    PlaneLaunch pl;
+    if (const int rc = plane_launch(who, F, C, HW, M, Q, {x0, noise, mask, idx, pano, pers}, ok, &pl)) return rc;
+    IM360_CHECK_ARG(((uintptr_t)noise % 4) == 0 && ((uintptr_t)mask % 4) == 0 && ((uintptr_t)idx % 4) == 0 && ((uintptr_t)coef_dev % 4) == 0,
+                    "%s: misaligned noise, mask, idx or coef_dev (4 bytes)", who);
+    IM360_CHECK_ARG(((uintptr_t)x0 % 2) == 0 && ((uintptr_t)pano % 2) == 0 && ((uintptr_t)pers % 2) == 0, "%s: misaligned 16-bit tensor", who);
+    IM360_CHECK_ARG(x0 != pano, "%s: x0 aliases pano (the clean clip would be overwritten)", who);
+    return with_dtype(dtype, who, [&](auto t) {
+        using T = typename decltype(t)::type;
+        with_const<1, 8>(pl.vec ? 8 : 1, [&](auto v) { with_bool(pl.lds, [&](auto l) {
+            hipLaunchKernelGGL((keep_latents_kernel<T, decltype(v)::value, decltype(l)::value, RELEASE>), dim3((unsigned)(C * F)), dim3(256), pl.smem,
+                               (hipStream_t)stream, (T*)pano, (T*)pers, (const T*)x0, noise, mask, (const int*)idx, ok, (int)F, (int)C, (int)HW, (int)M,
+                               (int)Q, sqrt_a, sqrt_b, tau, (const float*)coef_dev);
+        }); });
+        return im360_launch_status();
+    });
+}
+
 }  // namespace im360
 
 // pano / x0 [C, F, HW] and pers [M, C, F, Q] of one 16-bit dtype (pano and pers updated in place), noise fp32 [F, C, HW], mask fp32
@@ -136,22 +176,14 @@ __global__ __launch_bounds__(256) void keep_latents_kernel(T* __restrict__ pano,
 extern "C" __attribute__((visibility("default"))) int im360_keep_latents(void* pano, void* pers, const void* x0, const float* noise, const float* mask,
                                   const int32_t* idx, const uint8_t* ok, int64_t F, int64_t C, int64_t HW, int64_t M, int64_t Q,
                                   float sqrt_a, float sqrt_b, int dtype, void* stream, const void* coef_dev) {
-    using namespace im360;
-    IM360_CHECK_ARG(pano && pers && x0 && noise && mask && idx && ok, "keep_latents: null pointer");
-    PlaneLaunch pl;
-    if (const int rc = plane_launch("keep_latents", F, C, HW, M, Q, {x0, noise, mask, idx, pano, pers}, ok, &pl)) return rc;
-    IM360_CHECK_ARG(((uintptr_t)noise % 4) == 0 && ((uintptr_t)mask % 4) == 0 && ((uintptr_t)idx % 4) == 0 && ((uintptr_t)coef_dev % 4) == 0,
-                    "keep_latents: misaligned noise, mask, idx or coef_dev (4 bytes)");
-    IM360_CHECK_ARG(((uintptr_t)x0 % 2) == 0 && ((uintptr_t)pano % 2) == 0 && ((uintptr_t)pers % 2) == 0,
-                    "keep_latents: misaligned 16-bit tensor");
-    IM360_CHECK_ARG(x0 != pano, "keep_latents: x0 aliases pano (the clean clip would be overwritten)");
-    return with_dtype(dtype, "keep_latents", [&](auto t) {
-        using T = typename decltype(t)::type;
-        with_const<1, 8>(pl.vec ? 8 : 1, [&](auto v) { with_bool(pl.lds, [&](auto l) {
-            hipLaunchKernelGGL((keep_latents_kernel<T, decltype(v)::value, decltype(l)::value>), dim3((unsigned)(C * F)), dim3(256), pl.smem, (hipStream_t)stream,
-                               (T*)pano, (T*)pers, (const T*)x0, noise, mask, (const int*)idx, ok, (int)F, (int)C, (int)HW, (int)M, (int)Q,
-                               sqrt_a, sqrt_b, (const float*)coef_dev);
-        }); });
-        return im360_launch_status();
-    });
+    return im360::keep_launch<false>("keep_latents", pano, pers, x0, noise, mask, idx, ok, F, C, HW, M, Q, sqrt_a, sqrt_b, 0.0f, dtype, stream, coef_dev);
+}
+
+// release mode: the same tensors, mask = the strength map; an element with mask <= tau is pinned to `known`, every other one keeps its
+// bits; coef_dev: null, or device float[3] = (sqrt_a, sqrt_b, tau) read instead of the three arguments
+extern "C" __attribute__((visibility("default"))) int im360_keep_latents_release(void* pano, void* pers, const void* x0, const float* noise,
+                                  const float* mask, const int32_t* idx, const uint8_t* ok, int64_t F, int64_t C, int64_t HW, int64_t M, int64_t Q,
+                                  float sqrt_a, float sqrt_b, float tau, int dtype, void* stream, const void* coef_dev) {
+    return im360::keep_launch<true>("keep_latents_release", pano, pers, x0, noise, mask, idx, ok, F, C, HW, M, Q, sqrt_a, sqrt_b, tau, dtype, stream,
+                                    coef_dev);
 }

@@ -10,7 +10,8 @@ caller's generator (registered with the graph) or the default one; the coefficie
 sqrt b_t, sqrt a_prev, dir, sigma) for ``cfg_ddim_step``.  Guidance rescale (``guidance_rescale`` != 0) adds one captured
 statistics launch in front of each branch's step launch; its workspace is a graph-pool tensor and nothing more is uploaded.
 A partly regenerated clip (``keep``, pipeline ``regenerate_mask``) adds one captured ``keep_latents`` launch after the two step launches;
-its two coefficients are a fifth tiny buffer, refreshed per step through a pinned ring of its own.
+its two coefficients are a fifth tiny buffer, refreshed per step through a pinned ring of its own.  A release-mode region
+(``regenerate_mode="release"``) captures ``keep_latents_release`` in its place and uploads three: the step's threshold rides along.
 """
 import random
 
@@ -74,7 +75,7 @@ class GraphedDenoiseStep:
         self._up_t, self._up_c = _PinnedUploads(self.timestep), _PinnedUploads(self.coef)
         self.keep = keep
         if keep is not None:
-            self.keep_coef = torch.zeros(2, dtype=torch.float32, device=dev)
+            self.keep_coef = torch.zeros(keep.n_coef, dtype=torch.float32, device=dev)      # (sqrt_a, sqrt_b[, tau])
             self._up_keep = _PinnedUploads(self.keep_coef)
         # Building the graph must not consume randomness: the warm-up steps draw device noise (the per-step IP-adapter
         # noise) and allocating the coin buffer used to take 7 Python draws, which shifted the streams of the default

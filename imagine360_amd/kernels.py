@@ -68,6 +68,8 @@ _SIGNATURES = {
     "im360_cfg_multistep_step_windows": (_INT, [_PTR] * 6 + [_INT] + [_I64] * 5 + [_F32] * 6 + [_INT, _F32, _PTR, _I64, _INT, _PTR, _PTR]),
     "im360_noise_latents": (_INT, [_PTR] * 6 + [_I64] * 5 + [_F32, _F32, _INT, _PTR]),
     "im360_keep_latents": (_INT, [_PTR] * 7 + [_I64] * 5 + [_F32, _F32, _INT, _PTR, _PTR]),
+    "im360_keep_latents_release": (_INT, [_PTR] * 7 + [_I64] * 5 + [_F32, _F32, _F32, _INT, _PTR, _PTR]),
+    "im360_sphere_distance2": (_INT, [_PTR] * 3 + [_I64] * 2 + [_PTR]),
     "im360_resize_pano_latent": (_INT, [_PTR] * 2 + [_I64] * 6 + [_INT, _INT, _PTR]),
     "im360_retime_pano_latent": (_INT, [_PTR] * 2 + [_I64] * 4 + [_INT, _INT, _INT, _PTR]),
     "im360_free_init_noise": (_INT, [_PTR] * 8 + [_I64] * 5 + [_F32] * 3 + [_INT, _PTR]),
@@ -1082,6 +1084,34 @@ def noise_latents(x0, noise, idx, ok, sqrt_a, sqrt_b):
     return pano, pers
 
 
+def _check_keep(who, ncoef, pano, pers, x0, noise, mask, idx, ok, coef_dev):
+    """The argument checks ``keep_latents`` and ``keep_latents_release`` share (``ncoef``: the floats of ``coef_dev``); returns the
+    sizes (F, C, HW, M, Q) and the dtype code."""
+    _dev(pano, pers, x0, noise, mask, idx, ok, coef_dev)
+    dt = _dt(pano)
+    if pers.dtype != pano.dtype or x0.dtype != pano.dtype:
+        raise TypeError(f"{who}: pano, pers and x0 must have one dtype, got {pano.dtype}, {pers.dtype} and {x0.dtype}")
+    if noise.dtype != torch.float32 or mask.dtype != torch.float32:
+        raise TypeError(f"{who}: noise and mask must be float32, got {noise.dtype} and {mask.dtype}")
+    # (the shapes of noise and idx / ok are checked in front of those of x0 and mask: of two wrong shapes the first of this list is named)
+    C, F, h, w, M, ph, pw = _check_latent_tables(who, "pano", pano, noise, idx, ok)
+    if x0.shape != pano.shape:
+        raise ValueError(f"{who}: x0 must be {list(pano.shape)} like pano, got {list(x0.shape)}")
+    if tuple(mask.shape) != (F, h, w):
+        raise ValueError(f"{who}: mask must be {[F, h, w]} for pano {list(pano.shape)}, got {list(mask.shape)}")
+    if tuple(pers.shape) != (1, M, C, F, ph, pw):
+        raise ValueError(f"{who}: pers must be {[1, M, C, F, ph, pw]}, got {list(pers.shape)}")
+    _check_one_device(who, "pano, pers, x0, noise, mask, idx and ok", (pano, pers, x0, noise, mask, idx, ok))
+    if x0.data_ptr() == pano.data_ptr():
+        raise ValueError(f"{who}: x0 aliases pano (the update is in place: the clean clip would be overwritten)")
+    if coef_dev is not None:
+        if coef_dev.dtype != torch.float32:
+            raise TypeError(f"{who}: coef_dev must be float32, got {coef_dev.dtype}")
+        if coef_dev.numel() != ncoef or not coef_dev.is_contiguous() or coef_dev.device != pano.device:
+            raise ValueError(f"{who}: coef_dev must be a contiguous float32[{ncoef}] on the latents' device")
+    return (F, C, h * w, M, ph * pw), dt
+
+
 def keep_latents(pano, pers, x0, noise, mask, idx, ok, sqrt_a, sqrt_b, coef_dev=None):
     """Regenerating part of a given clip: both latents blended IN PLACE with ``known = T(sqrt_a * x0 + sqrt_b * noise)`` (the expression
     of ``noise_latents``, one rounding), one launch: ``pano = blend(pano, known, mask)`` and, where ``ok``, ``pers = blend(pers, known
@@ -1090,32 +1120,48 @@ def keep_latents(pano, pers, x0, noise, mask, idx, ok, sqrt_a, sqrt_b, coef_dev=
     [F, h, w] (1: regenerate, 0: keep);  ``idx`` int32 / ``ok`` uint8 [M, ph, pw] as for ``noise_latents``;  ``sqrt_a``, ``sqrt_b``:
     ``DDIMScheduler.keep_coefficients``;  ``coef_dev`` = device float32[2] holding them, read by the kernel instead (graph replay).
     Returns (pano, pers), the tensors given."""
-    _dev(pano, pers, x0, noise, mask, idx, ok, coef_dev)
-    dt = _dt(pano)
-    if pers.dtype != pano.dtype or x0.dtype != pano.dtype:
-        raise TypeError(f"keep_latents: pano, pers and x0 must have one dtype, got {pano.dtype}, {pers.dtype} and {x0.dtype}")
-    if noise.dtype != torch.float32 or mask.dtype != torch.float32:
-        raise TypeError(f"keep_latents: noise and mask must be float32, got {noise.dtype} and {mask.dtype}")
-    # (the shapes of noise and idx / ok are checked in front of those of x0 and mask: of two wrong shapes the first of this list is named)
-    C, F, h, w, M, ph, pw = _check_latent_tables("keep_latents", "pano", pano, noise, idx, ok)
-    if x0.shape != pano.shape:
-        raise ValueError(f"keep_latents: x0 must be {list(pano.shape)} like pano, got {list(x0.shape)}")
-    if tuple(mask.shape) != (F, h, w):
-        raise ValueError(f"keep_latents: mask must be {[F, h, w]} for pano {list(pano.shape)}, got {list(mask.shape)}")
-    if tuple(pers.shape) != (1, M, C, F, ph, pw):
-        raise ValueError(f"keep_latents: pers must be {[1, M, C, F, ph, pw]}, got {list(pers.shape)}")
-    _check_one_device("keep_latents", "pano, pers, x0, noise, mask, idx and ok", (pano, pers, x0, noise, mask, idx, ok))
-    if x0.data_ptr() == pano.data_ptr():
-        raise ValueError("keep_latents: x0 aliases pano (the update is in place: the clean clip would be overwritten)")
-    if coef_dev is not None:
-        if coef_dev.dtype != torch.float32:
-            raise TypeError(f"keep_latents: coef_dev must be float32, got {coef_dev.dtype}")
-        if coef_dev.numel() != 2 or not coef_dev.is_contiguous() or coef_dev.device != pano.device:
-            raise ValueError("keep_latents: coef_dev must be a contiguous float32[2] on the latents' device")
-    rc = lib().im360_keep_latents(_p(pano), _p(pers), _p(x0), _p(noise), _p(mask), _p(idx), _p(ok), F, C, h * w, M, ph * pw,
+    sizes, dt = _check_keep("keep_latents", 2, pano, pers, x0, noise, mask, idx, ok, coef_dev)
+    rc = lib().im360_keep_latents(_p(pano), _p(pers), _p(x0), _p(noise), _p(mask), _p(idx), _p(ok), *sizes,
                                   float(sqrt_a), float(sqrt_b), dt, _stream(), _p(coef_dev))
     _check(rc, "im360_keep_latents")
     return pano, pers
+
+
+def keep_latents_release(pano, pers, x0, noise, mask, idx, ok, sqrt_a, sqrt_b, tau, coef_dev=None):
+    """Release mode of ``keep_latents`` (pipeline ``regenerate_mode="release"``; Differential Diffusion, arXiv 2306.00950): ``mask`` is a
+    per-pixel strength and nothing is averaged.  IN PLACE, one launch: an element with ``mask <= tau`` (at ``idx`` for the views, where
+    ``ok``) is PINNED -- set to ``known = T(sqrt_a * x0 + sqrt_b * noise)``, the bits ``noise_latents`` writes at the same coefficients --
+    and every other element keeps its bits.  The compare is in fp32; ``tau``: ``DDIMScheduler.release_threshold``; a negative ``tau``
+    pins nothing.  The tensors and their checks are those of ``keep_latents``;  ``coef_dev`` = device float32[3] holding
+    ``(sqrt_a, sqrt_b, tau)``, read by the kernel instead (graph replay).  With a 0 / 1 mask and ``0 <= tau < 1`` the result is that of
+    ``keep_latents``, bit for bit.  Returns (pano, pers), the tensors given."""
+    sizes, dt = _check_keep("keep_latents_release", 3, pano, pers, x0, noise, mask, idx, ok, coef_dev)
+    rc = lib().im360_keep_latents_release(_p(pano), _p(pers), _p(x0), _p(noise), _p(mask), _p(idx), _p(ok), *sizes,
+                                          float(sqrt_a), float(sqrt_b), float(tau), dt, _stream(), _p(coef_dev))
+    _check(rc, "im360_keep_latents_release")
+    return pano, pers
+
+
+def sphere_distance2(keep, dirs):
+    """The squared chord from every pixel of an equirectangular frame to the nearest kept pixel of that frame, one launch, no
+    ``HW x HW`` intermediate: ``keep`` bool or uint8 [F, h, w] (non-zero: kept), ``dirs`` float32 [h * w, 3]
+    (``pano_geometry.pixel_directions``) -> float32 [F, h, w], ``min_q |dirs[p] - dirs[q]|^2`` over the kept q of the frame in fp32
+    from differences, ``+inf`` for a frame that keeps nothing.  The definition is ``pano_geometry.sphere_distance2``."""
+    if keep.dtype == torch.bool:
+        keep = keep.to(torch.uint8)
+    _dev(keep, dirs)
+    if keep.dtype != torch.uint8 or dirs.dtype != torch.float32:
+        raise TypeError(f"sphere_distance2: keep must be bool or uint8 and dirs float32, got {keep.dtype} and {dirs.dtype}")
+    if keep.dim() != 3 or keep.numel() == 0:
+        raise ValueError(f"sphere_distance2: keep must be a non-empty [F, h, w], got {list(keep.shape)}")
+    F, h, w = keep.shape
+    if tuple(dirs.shape) != (h * w, 3):
+        raise ValueError(f"sphere_distance2: dirs must be {[h * w, 3]} for keep {list(keep.shape)}, got {list(dirs.shape)}")
+    _check_one_device("sphere_distance2", "keep and dirs", (keep, dirs))
+    out = torch.empty((F, h, w), dtype=torch.float32, device=keep.device)
+    rc = lib().im360_sphere_distance2(_p(keep), _p(dirs), _p(out), F, h * w, _stream())
+    _check(rc, "im360_sphere_distance2")
+    return out
 
 
 RESIZE_MODES = {"bilinear": 0, "bicubic": 1}

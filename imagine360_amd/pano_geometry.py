@@ -373,3 +373,70 @@ def free_init_noise(x0, n1, n2, sa, sb, Lf, Lh, Lw):
     y = torch.matmul(Lh, y)
     y = torch.einsum("ij,bjchw->bichw", Lf, y)
     return n1 + (y - d) / sb
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# The spherical feather of a regenerate_mask (pipeline ``regenerate_feather``): distances on the sphere, not on the pixel grid.
+
+def pixel_directions(h, w, dtype=torch.float32):
+    """Unit vectors of the pixel centres of an ``h x w`` equirectangular image, [h * w, 3] (row-major, the order of a flattened plane):
+    longitude ``(x + 1/2) / w * 2 pi - pi``, latitude ``pi / 2 - (y + 1/2) / h * pi``, ``n = (cos lat cos lon, cos lat sin lon, sin lat)``.
+    The trigonometry is fp64 on the host; the table is rounded once to ``dtype`` (float32: what ``kernels.sphere_distance2`` reads)."""
+    lon = (torch.arange(w, dtype=torch.float64) + 0.5) / w * (2.0 * math.pi) - math.pi
+    lat = math.pi / 2.0 - (torch.arange(h, dtype=torch.float64) + 0.5) / h * math.pi
+    lat, lon = lat[:, None].expand(h, w), lon[None, :].expand(h, w)
+    n = torch.stack((lat.cos() * lon.cos(), lat.cos() * lon.sin(), lat.sin()), dim=-1)
+    return n.reshape(h * w, 3).to(dtype).contiguous()
+
+
+def sphere_distance2(keep, dirs, chunk_elems=1 << 22):
+    """The eager definition of ``kernels.sphere_distance2`` in torch ops on any device: ``keep`` bool / uint8 [F, h, w] (non-zero: a
+    kept pixel), ``dirs`` [h * w, 3] (``pixel_directions``; float32, or float64 for the tests) -> [F, h, w] in ``dirs``'s dtype,
+
+        d2[f, p] = min over the kept q of frame f of |dirs[p] - dirs[q]|^2 = dx^2 + dy^2 + dz^2 from the DIFFERENCES
+
+    (``2 - 2 dot`` would lose the small distances), ``+inf`` for a frame that keeps nothing.  The kept vectors of a frame are gathered
+    first and the pixels taken in chunks of at most ``chunk_elems`` pairs, so the ``HW x HW`` matrix never exists whole (4.3 GB per
+    frame at 128 x 256 in fp32)."""
+    F, h, w = keep.shape
+    HW = h * w
+    if tuple(dirs.shape) != (HW, 3):
+        raise ValueError(f"sphere_distance2: dirs must be {[HW, 3]} for keep {list(keep.shape)}, got {list(dirs.shape)}")
+    out = torch.full((F, HW), float("inf"), dtype=dirs.dtype, device=dirs.device)
+    kept = keep.reshape(F, HW).to(dirs.device) != 0
+    for f in range(F):
+        cand = dirs[kept[f]]                                            # [K, 3]
+        if cand.shape[0] == 0:
+            continue
+        step = max(1, int(chunk_elems) // cand.shape[0])
+        for p0 in range(0, HW, step):
+            d = dirs[p0:p0 + step, None, :] - cand[None, :, :]
+            out[f, p0:p0 + step] = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1] + d[..., 2] * d[..., 2]).min(dim=1).values
+    return out.reshape(F, h, w)
+
+
+def feather_ramp(d2, degrees):
+    """``clamp(theta / Theta, 0, 1)`` with ``theta = 2 asin(min(1, sqrt(d2) / 2))`` the great-circle angle of the squared chord ``d2``
+    and ``Theta = degrees`` in radians; 1 where ``d2`` is ``+inf`` (a frame that keeps nothing has nothing to feather from)."""
+    theta = 2.0 * torch.asin((d2.sqrt() / 2.0).clamp(max=1.0))
+    ramp = (theta / math.radians(float(degrees))).clamp(0.0, 1.0)
+    return torch.where(torch.isinf(d2), torch.ones((), dtype=ramp.dtype, device=ramp.device), ramp)
+
+
+def feather_pano_mask(mask, degrees, distance2=None):
+    """A ``regenerate_mask`` at latent resolution feathered on the sphere, the whole map: ``mask`` [F, h, w] in [0, 1] (1: regenerate,
+    0: keep) -> ``min(mask, ramp)``, where ``ramp`` rises from 0 on the kept set ``{mask <= 0}`` of each frame to 1 over ``degrees`` of
+    great-circle arc away from it (``feather_ramp`` of ``sphere_distance2``) -- across the +-180 degree seam, and by the same arc at a
+    pole as at the equator.  A 0 / 1 mask becomes a strength map for ``regenerate_mode="release"``; fractional values are only ever
+    lowered.  ``degrees == 0`` returns the mask.  ``distance2``: the function ``(keep, dirs) -> d2`` (None: the eager
+    ``sphere_distance2``; the pipeline passes ``kernels.sphere_distance2``)."""
+    degrees = float(degrees)
+    if not (math.isfinite(degrees) and degrees >= 0.0):
+        raise ValueError(f"feather_pano_mask: degrees must be finite and >= 0, got {degrees}")
+    if mask.dim() != 3:
+        raise ValueError(f"feather_pano_mask: mask must be [F, h, w], got {list(mask.shape)}")
+    if degrees == 0.0:
+        return mask
+    dirs = pixel_directions(mask.shape[1], mask.shape[2]).to(mask.device)
+    d2 = (distance2 or sphere_distance2)((mask <= 0).to(torch.uint8), dirs)
+    return torch.minimum(mask, feather_ramp(d2, degrees).to(mask.dtype))

@@ -20,7 +20,10 @@ surface, rebuilt for the MI355X:
     remaining steps run.
   * regenerating part of such a clip (``regenerate_mask``): after the two step kernels of every step ONE more kernel
     (``kernels.keep_latents``) blends both latents with the clean clip noised to the level they now have, so the kept region ends as
-    the input, bit for bit.
+    the input, bit for bit.  ``regenerate_mode="release"`` reads the mask as a per-pixel strength instead (Differential Diffusion,
+    arXiv 2306.00950): the same launch pins a pixel to the noised clip until the run passes the pixel's own entry point and leaves it
+    alone from then on (``kernels.keep_latents_release``), so nothing is averaged; ``regenerate_feather`` feathers the mask on the
+    sphere, in great-circle angle, with the distances from ONE kernel (``kernels.sphere_distance2``).
   * a hi-res pass (``init_latents`` / ``init_video`` SMALLER than the run, ``init_resize``): the clean latent of a clip generated at the
     trained size is upscaled once, as the equirectangular image it is (longitude wraps, latitude clamps), in ONE kernel
     (``kernels.resize_pano_latent``) in front of everything above, which then sees a clean latent of the run's size.
@@ -36,6 +39,7 @@ CLIP text encoding and SAM feature extraction are outside the hot path (SURVEY.m
 pipeline uses ``text_encoder``/``tokenizer``/``image_encoder`` when given, and also accepts precomputed
 ``prompt_embeds`` / ``sam_features`` keyword arguments.
 """
+import math
 from dataclasses import dataclass
 
 import numpy as np
@@ -67,28 +71,48 @@ def variance_noise(scheduler, latent, model_dtype, generator, rng, shard=None, f
     return z.to(device=latent.device, dtype=latent.dtype).contiguous()
 
 
+REGENERATE_MODES = ("blend", "release")
+
+
 class KeepRegion:
     """What ``regenerate_mask`` pins while the rest of a given clip is regenerated: the clean panorama latent ``x0`` [1, 4, F, h, w],
     the fp32 panorama noise [1, F, 4, h, w] the start latents were noised with, the mask [F, h, w] (float32; 1: regenerate, 0: keep),
     the nearest-E2P tables of the views and the timesteps that are run.  ``apply`` is the launch after the two step launches of step
-    ``i``; the graphed steps call ``kernels.keep_latents`` themselves with ``coefficients_at`` uploaded to the device."""
+    ``i``; the graphed steps call ``blend`` themselves with ``coefficients_at`` uploaded to the device (``n_coef`` floats).
+    ``mode``: "blend" (``kernels.keep_latents``, two coefficients) or "release" (``kernels.keep_latents_release``: the mask is a
+    per-pixel strength, the third coefficient ``scheduler.release_threshold`` of the step)."""
 
-    def __init__(self, scheduler, steps, x0, noise, mask, idx, ok):
-        self.scheduler, self.steps = scheduler, list(steps)
+    def __init__(self, scheduler, steps, x0, noise, mask, idx, ok, mode="blend"):
+        if mode not in REGENERATE_MODES:
+            raise ValueError(f"regenerate_mode must be one of {list(REGENERATE_MODES)}, got {mode!r}")
+        self.scheduler, self.steps, self.mode = scheduler, list(steps), mode
         self.x0, self.noise, self.mask, self.idx, self.ok = x0, noise, mask, idx, ok
+        self.n_coef = 3 if mode == "release" else 2
+
+    def coefficients(self, i):
+        """The coefficients of the launch after step ``i``: ``scheduler.keep_coefficients``, in release mode followed by
+        ``scheduler.release_threshold``."""
+        c = self.scheduler.keep_coefficients(self.steps, i)
+        return c + (self.scheduler.release_threshold(self.steps, i),) if self.mode == "release" else c
 
     def coefficients_at(self, t_host):
-        """``scheduler.keep_coefficients`` for the step at timestep ``t_host``; (1.0, 0.0) for a timestep the run does not hold (the
-        warm-up of a graphed step, whose numbers are dropped)."""
+        """``coefficients`` for the step at timestep ``t_host``; (1.0, 0.0) for a timestep the run does not hold (the warm-up of a
+        graphed step, whose numbers are dropped), in release mode with a threshold of -1.0, which pins nothing."""
         t = int(t_host)
-        return self.scheduler.keep_coefficients(self.steps, self.steps.index(t)) if t in self.steps else (1.0, 0.0)
+        if t in self.steps:
+            return self.coefficients(self.steps.index(t))
+        return (1.0, 0.0, -1.0) if self.mode == "release" else (1.0, 0.0)
 
-    def blend(self, pano_latent, pers_latent, sqrt_a=1.0, sqrt_b=0.0, coef_dev=None):
+    def blend(self, pano_latent, pers_latent, sqrt_a=1.0, sqrt_b=0.0, tau=-1.0, coef_dev=None):
+        """The launch itself (``tau``: release mode only)."""
+        if self.mode == "release":
+            return kernels.keep_latents_release(pano_latent, pers_latent, self.x0, self.noise, self.mask, self.idx, self.ok, sqrt_a, sqrt_b,
+                                                tau, coef_dev=coef_dev)
         return kernels.keep_latents(pano_latent, pers_latent, self.x0, self.noise, self.mask, self.idx, self.ok, sqrt_a, sqrt_b,
                                     coef_dev=coef_dev)
 
     def apply(self, pano_latent, pers_latent, i):
-        return self.blend(pano_latent, pers_latent, *self.scheduler.keep_coefficients(self.steps, i))
+        return self.blend(pano_latent, pers_latent, *self.coefficients(i))
 
 
 @dataclass
@@ -228,12 +252,13 @@ class AnimationPipeline:
         return kernels.resize_pano_latent(x0.to(device=device, dtype=latents_dtype).contiguous(), equi_h, equi_w, init_resize)
 
     def init_from_clip(self, x0, strength, video_length, equi_h, equi_w, pers_h, pers_w, cameras, device, latents_dtype=torch.float16,
-                       regenerate_mask=None):
+                       regenerate_mask=None, regenerate_mode="blend"):
         """The start of a run from a given clean panorama latent ``x0`` [1, 4, F, h, w] (SDEdit): ``init_noise``'s panorama noise
         draw at its place in the RNG order, the schedule entered at ``scheduler.timesteps_for_strength(strength)``, and ``x0`` noised
         to the first timestep that is run, the perspective start being the nearest-neighbour E2P resampling of the panorama start
         (``kernels.noise_latents``, one launch).  Returns (pano_latent, pers_latent, steps); with ``regenerate_mask`` (float32
-        [F, h, w] on ``device``) a fourth value, the ``KeepRegion`` that holds on to the clean latent, this noise and the tables."""
+        [F, h, w] on ``device``) a fourth value, the ``KeepRegion`` (of ``regenerate_mode``) that holds on to the clean latent, this noise and
+        the tables."""
         if tuple(x0.shape) != (1, 4, video_length, equi_h, equi_w):
             raise ValueError(f"the init latent must be [1, 4, {video_length}, {equi_h}, {equi_w}] (a clean panorama latent, multiplied by "
                              f"VAE_SCALE, such as pipe.last_latents[0]), got {tuple(x0.shape)}")
@@ -243,20 +268,24 @@ class AnimationPipeline:
         x0, noise, idx, ok = x0.to(device=device, dtype=latents_dtype).contiguous(), noise.squeeze(2), idx.to(torch.int32), ok.to(torch.uint8)
         pano, pers = kernels.noise_latents(x0, noise, idx, ok, sqrt_a, sqrt_b)
         if regenerate_mask is not None:
-            return pano, pers, steps, KeepRegion(self.scheduler, steps, x0, noise, regenerate_mask, idx, ok)
+            return pano, pers, steps, KeepRegion(self.scheduler, steps, x0, noise, regenerate_mask, idx, ok, mode=regenerate_mode)
         return pano, pers, steps
 
-    def prepare_regenerate_mask(self, mask, video_length, equi_h, equi_w, device):
+    def prepare_regenerate_mask(self, mask, video_length, equi_h, equi_w, device, feather=0.0):
         """``regenerate_mask`` [1, F, 1, H', W'] (the layout and polarity of ``video_batch["pano_mask"]``: 1 regenerate, 0 keep) ->
         float32 [F, h, w] on ``device``: nearest-resized to the panorama latent with the call of ``prepare_masked_latents_pano``,
-        clamped to [0, 1]."""
+        clamped to [0, 1].  ``feather`` > 0 (degrees of great-circle arc): the map is then feathered on the sphere,
+        ``pano_geometry.feather_pano_mask`` with the distances from ``kernels.sphere_distance2`` (one launch)."""
         if mask.dim() != 5 or mask.shape[0] != 1 or mask.shape[2] != 1:
             raise ValueError(f"regenerate_mask must be [1, F, 1, H, W] like video_batch['pano_mask'], got {tuple(mask.shape)}")
         if mask.shape[1] != video_length:
             raise ValueError(f"regenerate_mask has {mask.shape[1]} frames, the clip has video_length = {video_length}")
         m = mask.to(device=device, dtype=torch.float32).transpose(2, 1)
         m = F.interpolate(m, size=(m.shape[2], equi_h, equi_w))
-        return m.clamp(0.0, 1.0).reshape(video_length, equi_h, equi_w).contiguous()
+        m = m.clamp(0.0, 1.0).reshape(video_length, equi_h, equi_w).contiguous()
+        if float(feather) > 0.0:
+            m = G.feather_pano_mask(m, feather, distance2=kernels.sphere_distance2).contiguous()
+        return m
 
     def _encode_chunks(self, x, chunk=8, keep_rows=None):
         """VAE-encode images [n, 3, H, W] in chunks of ``chunk`` and sample the posteriors (one randn per chunk, in order).
@@ -334,7 +363,7 @@ class AnimationPipeline:
                  ip_plus_condition="image", prompt_embeds=None, sam_features=None, trace=None, frame_shard=None,
                  context_frames=None, context_overlap=4, context_weights="pyramid", guidance_rescale=0.0, context_loop=False,
                  init_latents=None, init_video=None, strength=1.0, regenerate_mask=None, init_resize="bicubic", init_retime=None,
-                 free_init_iters=1, free_init_d_s=0.25, free_init_d_t=0.25, **kwargs):
+                 free_init_iters=1, free_init_d_s=0.25, free_init_d_t=0.25, regenerate_mode="blend", regenerate_feather=0.0, **kwargs):
         """``frame_shard`` (imagine360_amd.dist.FrameShard): this rank denoises a contiguous chunk of the frames (BASELINE
         configs 4 / 5); all ranks must be called with the same seeds and inputs.  Noise is drawn for the whole clip and
         cut, the VAE encodes / the loop runs / the VAE decodes only the local frames, the motion modules exchange tokens
@@ -370,6 +399,25 @@ class AnimationPipeline:
         kept region of ``last_latents[0]`` is the init latent bit for bit; ``trace`` and ``callback`` see the blended latent.
         ``regenerate_mask=video_batch["pano_mask"]`` pins the footage an outpainted panorama came from.  Independent of the model's
         own mask channels; every loop variant; not with ``frame_shard``.  Without the keyword nothing of this runs.
+        ``regenerate_mode`` ("blend": the above, the default; "release": Differential Diffusion, arXiv 2306.00950, diffusers' differential
+        img2img): ``regenerate_mask`` is a per-pixel STRENGTH ``s`` in [0, 1] and nothing is ever averaged -- a blend of the running latent
+        with the noised clip at every step ends as a cross-fade of two clean clips.  After step ``i`` of the ``n`` steps that are run a pixel
+        with ``s <= scheduler.release_threshold(steps, i) = 1 - (i + 1) / n`` is PINNED to the noised clip (the bits of mask 0 in blend
+        mode) and every other pixel is left as the step wrote it: a pixel is released once and then denoised freely with its neighbours, for
+        about the last ``s n`` steps -- the map scales ``strength`` per pixel.  ``s = 1`` is never pinned; ``s = 0`` is pinned after every
+        step including the last, so the kept region of ``last_latents[0]`` is the init latent bit for bit as in blend mode, and a 0 / 1 mask
+        gives the bits of blend mode at every step.  Still the one launch per step (``kernels.keep_latents_release``; the threshold is the
+        third uploaded coefficient of a graphed step); every loop variant ``regenerate_mask`` supports.  "release" without a mask and any
+        other name raise ``ValueError``.  ``regenerate_mask=context.keyframe_strength(f, video_length, loop)`` lets the in-betweens of a
+        frame-interpolation pass change the less the nearer they are to a source frame; a latitude ramp keeps the poles of a hi-res pass.
+        ``regenerate_feather`` (0.0: off; degrees of great-circle arc; needs a mask): the resized mask is feathered ON THE SPHERE once,
+        before the loop -- ``min(mask, ramp)`` where ``ramp`` rises from 0 on the kept set ``{mask <= 0}`` of each frame to 1 over that many
+        degrees of arc away from it (``pano_geometry.feather_pano_mask``; the distances from ``kernels.sphere_distance2``, one launch, no
+        ``HW x HW`` matrix).  It crosses the +-180 degree seam and measures the same arc at a pole as at the equator, which a feather on
+        the pixel grid does not.  Independent of ``regenerate_mode``, but a feathered map is MEANT FOR "release" (in blend mode it is a
+        ghosted band): ``regenerate_mask=video_batch["pano_mask"], regenerate_feather=20, regenerate_mode="release"`` is the refinement
+        pass after an outpaint.  Negative or non-finite values raise ``ValueError``.  Whether release mode and the feather improve a clip
+        can only be judged with trained weights.
         ``init_resize`` ("bicubic", or "bilinear"): the hi-res pass.  ``init_latents`` may be [1, 4, F, h, w] with ``h <= H/8`` and
         ``w <= W/8`` and ``init_video`` [1, F, 3, 8h, 8w] (encoded at its own size, no RNG draw): a smaller clean latent is upscaled once
         to the run's size before anything else sees it (``kernels.resize_pano_latent``, one launch: half-pixel centres, columns wrap
@@ -445,6 +493,15 @@ class AnimationPipeline:
             if not (float(free_init_d_s) > 0.0 and float(free_init_d_t) > 0.0):
                 raise ValueError(f"free_init_d_s={free_init_d_s} and free_init_d_t={free_init_d_t} must be positive (cut-offs as fractions of "
                                  "Nyquist)")
+        if regenerate_mode not in REGENERATE_MODES:
+            raise ValueError(f"regenerate_mode must be one of {list(REGENERATE_MODES)}, got {regenerate_mode!r}")
+        if regenerate_mode == "release" and regenerate_mask is None:
+            raise ValueError('regenerate_mode="release" needs regenerate_mask (the per-pixel strength map)')
+        regenerate_feather = float(regenerate_feather)
+        if not (math.isfinite(regenerate_feather) and regenerate_feather >= 0.0):
+            raise ValueError(f"regenerate_feather must be finite and >= 0 (degrees of arc), got {regenerate_feather}")
+        if regenerate_feather > 0.0 and regenerate_mask is None:
+            raise ValueError("regenerate_feather needs regenerate_mask (the mask that is feathered)")
         if regenerate_mask is not None and not has_init:
             raise ValueError("regenerate_mask needs init_latents or init_video (the clip whose unmasked part is kept)")
         if regenerate_mask is not None and frame_shard is not None:
@@ -483,9 +540,11 @@ class AnimationPipeline:
             x0 = init_latents if init_latents is not None else self.encode_init_video(init_video.to(device))
             x0 = self.resize_init(x0, f, H // 8, W // 8, device, latents_dtype, init_resize, init_retime,
                                   loop=bool(context_loop))                                       # (itself at the run's frame count and size)
-            keep_mask = None if regenerate_mask is None else self.prepare_regenerate_mask(regenerate_mask, f, H // 8, W // 8, device)
+            keep_mask = None if regenerate_mask is None else self.prepare_regenerate_mask(regenerate_mask, f, H // 8, W // 8, device,
+                                                                                                   feather=regenerate_feather)
             pano_latent, pers_latent, steps_host, *region = self.init_from_clip(x0, strength, f, H // 8, W // 8, ps // 8, ps // 8, cameras,
-                                                                                device, latents_dtype, regenerate_mask=keep_mask)
+                                                                                device, latents_dtype, regenerate_mask=keep_mask,
+                                                                                regenerate_mode=regenerate_mode)
             region = region[0] if region else None             # (KeepRegion)
         elif free_init_iters > 1:
             # pass 0 is init_noise, its two halves called here so that the panorama noise is kept in fp32 as drawn

@@ -183,6 +183,18 @@ class DDIMScheduler:
             raise ValueError(f"keep_coefficients: step {i} is not one of the {len(steps)} steps of the run")
         return self.noise_coefficients(steps[i + 1]) if i + 1 < len(steps) else (1.0, 0.0)
 
+    def release_threshold(self, steps, i):
+        """``tau_i = 1 - (i + 1) / n`` of release mode (pipeline ``regenerate_mode="release"``; Differential Diffusion, arXiv 2306.00950)
+        AFTER step ``i`` of the ``n`` steps that are run (``steps``: the run's timestep list, or ``n`` itself): a pixel of strength
+        ``s <= tau_i`` is still pinned to the noised clip, every other one has been released.  fp64, rounded once to the fp32 the
+        kernel compares in (third argument of ``kernels.keep_latents_release``), returned as a host float.  Decreasing in ``i``,
+        exactly 0 after the last step: ``s = 0`` stays pinned to the end, ``s = 1`` never is, and a pixel of strength ``s`` is free for
+        about the last ``s n`` steps."""
+        n, i = (int(steps) if isinstance(steps, int) else len(steps)), int(i)
+        if not 0 <= i < n:
+            raise ValueError(f"release_threshold: step {i} is not one of the {n} steps of the run")
+        return float(torch.tensor(1.0 - (i + 1) / n, dtype=torch.float64).to(torch.float32))
+
     def timesteps_for_strength(self, strength):
         """Where a run that starts from a given clip enters the schedule of ``set_timesteps(N)`` (diffusers' img2img ``get_timesteps``):
         ``k = min(int(N * strength), N)`` steps are run, the last k of the schedule.  Returns ``(i0, steps)`` with ``i0 = N - k`` and
@@ -304,7 +316,7 @@ class DDIMScheduler:
 class DPMSolverMultistepScheduler(DDIMScheduler):
     """DPM-Solver++ 2M (arXiv 2211.01095, algorithm 2: data prediction, multistep, order <= 2) on DDIMScheduler's grid: the same
     tables, ``set_timesteps``, predecessor ``t - num_train_timesteps // N`` (below 0: ``final_alpha_cumprod``), ``add_noise``,
-    ``get_velocity``, ``noise_coefficients``, ``keep_coefficients``, ``timesteps_for_strength`` and ``kernel_mode``, all inherited.  The
+    ``get_velocity``, ``noise_coefficients``, ``keep_coefficients``, ``release_threshold``, ``timesteps_for_strength`` and ``kernel_mode``, all inherited.  The
     eager ``step`` below is the definition; nothing is claimed about bit parity with diffusers' class of the same name.
 
     With a = alphas_cumprod[t]: alpha = sqrt(a), sigma = sqrt(1 - a), lambda = ln(alpha / sigma); primed values belong to the

@@ -414,6 +414,35 @@ int im360_keep_latents(void* pano, void* pers, const void* x0, const float* nois
                        const uint8_t* ok, int64_t F, int64_t C, int64_t HW, int64_t M, int64_t Q, float sqrt_a, float sqrt_b, int dtype,
                        void* stream, const void* coef_dev);
 
+/* ---- release mode of the keep launch (AnimationPipeline regenerate_mode="release"; Differential Diffusion, arXiv 2306.00950, the
+ * "differential img2img" of diffusers' community pipelines): the mask is a per-pixel strength s in [0, 1] and nothing is averaged.
+ *   pano[c, f, p]    = mask[f, p] <= tau ? known[c, f, p] : pano[c, f, p]
+ *   pers[m, c, f, q] = ok[m, q] && mask[f, idx[m, q]] <= tau ? known[c, f, idx[m, q]] : pers[m, c, f, q]
+ * `known`, the tensors, the paths and the refusals are those of im360_keep_latents (the same kernel, instantiated for the select): a
+ * pinned element is `known` bit for bit, as blend writes for w <= 0; a free one keeps its bits and a group of eight free ones is not
+ * stored.  The compare is in fp32; tau = DDIMScheduler.release_threshold of the step (1 - (i + 1) / n in fp64, rounded once), so s = 1
+ * is never pinned, s = 0 always, and a 0 / 1 mask gives the bits of im360_keep_latents at every step.  tau < 0 pins nothing.
+ * coef_dev: null, or device float[3] = (sqrt_a, sqrt_b, tau), read by the kernel instead of the three arguments (graph replay).
+ * Replaces: the per-step `mask = thresholds[i] > map; latents = original_with_noise * mask + latents * (1 - mask)` of diffusers'
+ *   examples/community/pipeline_stable_diffusion_xl_differential_img2img.py, as a select. */
+int im360_keep_latents_release(void* pano, void* pers, const void* x0, const float* noise, const float* mask, const int32_t* idx,
+                               const uint8_t* ok, int64_t F, int64_t C, int64_t HW, int64_t M, int64_t Q, float sqrt_a, float sqrt_b, float tau,
+                               int dtype, void* stream, const void* coef_dev);
+
+/* ---- the spherical feather of a regenerate_mask (AnimationPipeline regenerate_feather), one launch: for every pixel of an
+ * equirectangular frame the squared chord to the nearest kept pixel of that frame.
+ *   d2[f, p] = min over q with keep[f, q] != 0 of fma(dz, dz, fma(dy, dy, dx * dx)),  (dx, dy, dz) = dirs[p] - dirs[q]     fp32, this order
+ * and +inf for a frame without a kept pixel.  keep: uint8 [F, HW]; dirs: fp32 [HW, 3], unit vectors of the pixel centres
+ * (pano_geometry.pixel_directions: fp64 on the host, rounded once -- the kernel does no trigonometry); d2: fp32 [F, HW].  From
+ * differences, so small distances keep their relative accuracy (2 - 2 dot would not).  The host forms the angle 2 asin(sqrt(d2) / 2) and
+ * the ramp (pano_geometry.feather_pano_mask).  One workgroup per (frame, 512 pixels); the candidates stream through LDS in tiles of 1024
+ * and those not kept are skipped; no atomics, deterministic, no HW x HW intermediate.
+ * Refused: a null pointer, a size <= 0, F or HW + 512 >= 2^31, F * ceil(HW / 512) >= 2^24 workgroups, dirs or d2 off 4 bytes, d2
+ * overlapping an input.
+ * Replaces: nothing in the reference; a feather (Gaussian blur / distance transform) of the mask on the pixel grid, which neither
+ *   crosses the +-180 degree seam nor knows that a column near a pole is a fraction of a degree. */
+int im360_sphere_distance2(const uint8_t* keep, const float* dirs, float* d2, int64_t F, int64_t HW, void* stream);
+
 /* ---- upscaling a clean panorama latent (AnimationPipeline init_latents / init_video at a lower resolution than the run, init_resize),
  * one launch: x [C, F, h, w] -> out [C, F, H, W], H >= h, W >= w, one 16-bit dtype; mode 0 bilinear, 1 bicubic.
  *   out[c, f, Y, X] = T(sum_r wy[Y][r] * (sum_j wx[X][j] * x[c, f, row(Y, r), col(X, j)]))     fp32, horizontal pass then vertical, one rounding

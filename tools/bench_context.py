@@ -19,10 +19,11 @@ device events, with the bytes each has to move computed from the shapes.  Prints
                                                       # at this strength, alternated --rounds times; over context windows when --frames > 16 (--loop:
                                                       # on a ring); and kernels.noise_latents at the size of that clip next to the torch-op composition
                                                       # it replaces (device events, alternated), with the bytes the launch has to move
-    python tools/bench_context.py --strength 0.5 --regenerate-mask half [--frames 16]
+    python tools/bench_context.py --strength 0.5 --regenerate-mask half|feather [--frames 16]
                                                       # part of the clip kept (pipeline regenerate_mask; even frames: the left half, odd frames: a
                                                       # rectangle across the seam): the refinement call with the mask next to the same call without it,
-                                                      # alternated --rounds times, and kernels.keep_latents next to the torch ops it replaces
+                                                      # alternated --rounds times, and kernels.keep_latents next to the torch ops it replaces;
+                                                      # feather: that mask with regenerate_feather=20 in regenerate_mode="release"
     python tools/bench_context.py --init-scale 2 --strength 0.5 [--pano-hw 128 256] [--frames 16] [--num-steps 20]
                                                       # the hi-res pass: a first pipeline call from pure noise at 1/N of the size plus a second call
                                                       # at the full size from its latent (init_latents smaller than the run: kernels.resize_pano_latent)
@@ -603,11 +604,14 @@ def strength_bench(args, sch, dev, dt):
 
 
 def masked_refinement(args, res, call, x0, steps, mask, fin):
-    """--regenerate-mask: the refinement call with the mask next to the same call without it, alternated."""
+    """--regenerate-mask: the refinement call with the mask next to the same call without it, alternated.  "feather": the half mask
+    feathered by 20 degrees on the sphere (``regenerate_feather``: one ``sphere_distance2`` launch per call) and run in release mode."""
     times = dict(refine=[], refine_masked=[])
     init = dict(init_latents=x0, strength=args.strength)
+    soft = dict(regenerate_feather=20.0, regenerate_mode="release") if args.regenerate_mask == "feather" else {}
+    res["regenerate_keywords"] = soft
     for _ in range(args.rounds + 1):                       # (round 0 warms the masked call's shapes up)
-        for name, kw in (("refine", init), ("refine_masked", dict(regenerate_mask=mask, **init))):
+        for name, kw in (("refine", init), ("refine_masked", dict(regenerate_mask=mask, **soft, **init))):
             ms, ok = call(**kw)
             times[name].append(ms)
             fin = fin and ok
@@ -632,8 +636,9 @@ def main():
     ap.add_argument("--strength", type=float, default=None, help="the refinement pass: pipeline calls with init_latents at this strength next to calls from pure noise")
     ap.add_argument("--frames", type=int, default=FRAMES, help="--strength: frames of the clip (context windows above 16)")
     ap.add_argument("--num-steps", type=int, default=6, help="--strength: num_inference_steps of every call")
-    ap.add_argument("--regenerate-mask", choices=["half"], default=None,
-                    help="--strength: keep part of the clip (pipeline regenerate_mask) and time that call next to the call without the mask")
+    ap.add_argument("--regenerate-mask", choices=["half", "feather"], default=None,
+                    help="--strength: keep part of the clip (pipeline regenerate_mask) and time that call next to the call without the mask; "
+                         "feather: the half mask with regenerate_feather=20 in regenerate_mode='release'")
     ap.add_argument("--init-scale", type=int, default=None,
                     help="with --strength: the hi-res pass -- a first call at 1/N of --pano-hw, a second call at --pano-hw from its latent -- next to one call from pure noise at --pano-hw")
     ap.add_argument("--init-frames", type=int, default=None,

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Per-kernel micro-benchmarks at BASELINE cfg2 shapes (run on the MI355X):
 
-    python tools/bench_kernels.py [attn] [conv] [temporal] [ln] [gn] [sampler_step] [free_init_noise] [--iters N]
+    python tools/bench_kernels.py [attn] [conv] [temporal] [ln] [gn] [sampler_step] [free_init_noise] [keep_release] [sphere_distance2] [--iters N]
 
 Prints achieved TFLOP/s (MFMA kernels, vs 2500 dense bf16) or GB/s (HBM kernels, vs 8000) per shape.
 Usable under `rocprofv3 --pmc ...` for counters of one kernel class.
@@ -505,8 +505,79 @@ def bench_free_init_noise(iters):
         print("JSON", json.dumps(row))
 
 
+def bench_keep_release(iters):
+    """The keep launch on the two latents of cfg2 (16 frames; panorama 64 x 128, 20 views of 32 x 32) under the half mask feathered by
+    20 degrees: ``kernels.keep_latents`` (blend) next to ``kernels.keep_latents_release`` at the middle threshold, device events, 7 rounds
+    alternated, min / median / max.  ``IM360_PARENT_LIB=<path to another libim360_kernels.so>``: that library's ``im360_keep_latents`` on
+    the same tensors as a third row (a build of the parent commit).  A JSON line, for profiles/."""
+    import ctypes
+    import json
+    from imagine360_amd import pano_geometry as G
+    F, C, h, w, M, p = 16, 4, 64, 128, 20, 32
+    pano, x0, pers = rn(1, C, F, h, w), rn(1, C, F, h, w), rn(1, M, C, F, p, p)
+    noise = torch.randn(1, F, C, h, w, device=DEV)
+    idx = torch.randint(0, h * w, (M, p, p), device=DEV, dtype=torch.int32)
+    ok = (torch.rand(M, p, p, device=DEV) < 0.9).to(torch.uint8)
+    hard = torch.ones(F, h, w, device=DEV)
+    hard[0::2, :, :w // 2] = 0.0
+    hard[1::2, h // 4:3 * h // 4, 7 * w // 8:] = 0.0
+    hard[1::2, h // 4:3 * h // 4, :w // 8] = 0.0
+    s = G.feather_pano_mask(hard, 20.0, distance2=K.sphere_distance2).contiguous()
+    sa, sb, tau = 0.8, 0.6, 0.5
+    fns = {"keep_latents (blend)": lambda: K.keep_latents(pano, pers, x0, noise, s, idx, ok, sa, sb),
+           "keep_latents_release": lambda: K.keep_latents_release(pano, pers, x0, noise, s, idx, ok, sa, sb, tau)}
+    if os.environ.get("IM360_PARENT_LIB"):
+        parent = ctypes.CDLL(os.environ["IM360_PARENT_LIB"])
+        parent.im360_keep_latents.restype, parent.im360_keep_latents.argtypes = K._SIGNATURES["im360_keep_latents"]
+        ptrs = [t.data_ptr() for t in (pano, pers, x0, noise, s, idx, ok)]
+        fns["parent keep_latents"] = lambda: parent.im360_keep_latents(*ptrs, F, C, h * w, M, p * p, sa, sb, 0, torch.cuda.current_stream().cuda_stream, None)
+    times = {k: [] for k in fns}
+    for _ in range(7):
+        for k, fn in fns.items():
+            times[k].append(timeit(fn, iters))
+    # the streams every variant reads: x0, noise, the map per plane, the tables per plane; what is stored depends on the map
+    by = pano.numel() * (2 + 4) + C * F * (h * w * 4 + M * p * p * 5)
+    row = dict(bench="keep_release", F=F, C=C, hw=[h, w], views=[M, p, p], dtype="bfloat16", iters=iters, tau=tau,
+               pinned_fraction=float((s <= tau).float().mean()), fractional_fraction=float(((s > 0) & (s < 1)).float().mean()))
+    for k, ts in times.items():
+        ts.sort()
+        row[k] = dict(us_min=ts[0] * 1e6, us_median=ts[len(ts) // 2] * 1e6, us_max=ts[-1] * 1e6)
+        print(f"keep {k:24s}: {ts[0] * 1e6:7.2f} us min {ts[len(ts) // 2] * 1e6:7.2f} us median {ts[-1] * 1e6:7.2f} us max  "
+              f"{by / ts[0] / 1e9:6.0f} GB/s of the read streams")
+    print("JSON", json.dumps(row))
+
+
+def bench_sphere_distance2(iters):
+    """``kernels.sphere_distance2`` at the cfg2 latent (16 frames of 64 x 128) and at the hi-res pass (128 x 256) under the half mask,
+    against its eager definition ``pano_geometry.sphere_distance2`` on the GPU (chunked), device events, 3 rounds alternated.  A JSON
+    line per size, for profiles/."""
+    import json
+    from imagine360_amd import pano_geometry as G
+    F = 16
+    for h, w in ((64, 128), (128, 256)):
+        keep = torch.zeros(F, h, w, dtype=torch.uint8, device=DEV)
+        keep[0::2, :, :w // 2] = 1
+        keep[1::2, h // 4:3 * h // 4, 7 * w // 8:] = 1
+        keep[1::2, h // 4:3 * h // 4, :w // 8] = 1
+        dirs = G.pixel_directions(h, w).to(DEV)
+        kern, eager = (lambda: K.sphere_distance2(keep, dirs)), (lambda: G.sphere_distance2(keep, dirs, chunk_elems=1 << 26))
+        a, b = kern(), eager()
+        diff = float(((a - b).abs() / b.clamp(min=1e-30)).max())
+        tk, te = [], []
+        for _ in range(3):
+            tk.append(timeit(kern, iters))
+            te.append(timeit(eager, max(1, iters // 5)))
+        tk.sort(), te.sort()
+        pairs = float(keep.flatten(1).sum(1).double().sum()) * h * w                 # chords formed
+        row = dict(bench="sphere_distance2", F=F, hw=[h, w], kept_fraction=float(keep.float().mean()), iters=iters, kernel_us=[t * 1e6 for t in tk],
+                   eager_us=[t * 1e6 for t in te], max_rel_diff_vs_eager=diff, gchords_per_call=pairs / 1e9, kernel_gchords_per_s=pairs / tk[0] / 1e9)
+        print(f"sphere_distance2 {F} x {h} x {w}: kernel {tk[0] * 1e6:9.1f} us min {tk[1] * 1e6:9.1f} us median  eager {te[0] * 1e6:10.1f} us min  "
+              f"{pairs / tk[0] / 1e9:7.1f} Gchord/s  max rel diff {diff:.2e}")
+        print("JSON", json.dumps(row))
+
+
 if __name__ == "__main__":
-    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    args =[a for a in sys.argv[1:] if not a.startswith("--")]
     iters = 10
     if "--iters" in sys.argv:
         iters = int(sys.argv[sys.argv.index("--iters") + 1])
