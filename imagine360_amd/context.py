@@ -193,17 +193,26 @@ class WindowPlan:
             if coins is not None:
                 mv._coins_dev, mv.coins_preloaded = saved
 
-    def pred_buffers(self, pano_latent, pers_latent):
-        """Empty [nW, 2, ...] prediction buffers in the latents' dtype and layout with L frames."""
+    def pred_buffers(self, pano_latent, pers_latent, halves=2):
+        """Empty [nW, 2, ...] prediction buffers in the latents' dtype and layout with L frames; ``halves=1``: [nW, 1, ...], for the
+        steps that run the text half alone (pipeline ``guidance_interval``)."""
         nW, L = len(self), self.length
         ps, qs = list(pano_latent.shape), list(pers_latent.shape)
         ps[2], qs[3] = L, L
-        return (pers_latent.new_empty((nW, 2, *qs[1:])), pano_latent.new_empty((nW, 2, *ps[1:])))
+        return (pers_latent.new_empty((nW, halves, *qs[1:])), pano_latent.new_empty((nW, halves, *ps[1:])))
+
+    @staticmethod
+    def text_half(static):
+        """``static_inputs`` for a forward of the text half alone (pipeline ``guidance_interval``): per window the second CFG row of
+        every tensor, as views.  Made ONCE per run and kept: the model caches the IP tokens on the feature tensors' identity, and
+        ``ip_cache_slots(mv, 2 * len(plan))`` holds both forms of every window at once."""
+        return [{k: (None if v is None else v[1:2]) for k, v in st.items()} for st in static]
 
 
 class ip_cache_slots:
-    """Context manager: both UNets of ``mv`` keep the IP tokens of ``n`` feature tensors (one per window) instead of one; on
-    exit the single-entry behaviour and memory footprint are restored."""
+    """Context manager: both UNets of ``mv`` keep the IP tokens of ``n`` feature tensors (one per window; with a guidance interval
+    two per window, the CFG batch and its text half, and two without windows) instead of one; on exit the single-entry behaviour
+    and memory footprint are restored."""
 
     def __init__(self, mv, n):
         self.unets, self.n = (mv.unet, mv.pano_unet), int(n)

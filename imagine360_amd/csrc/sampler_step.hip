@@ -2,7 +2,10 @@
 // (cfg_ddim_kernel, cfg_ddim_step_kernel), the same step on the blend of temporal context windows on a line or a ring
 // (cfg_ddim_step_windows_kernel), the statistics pass of the guidance rescale (cfg_rescale_*), and the DPM-Solver++ 2M update
 // (arXiv 2211.01095, algorithm 2) on the same combine, blend, rescale and x0 conversion (cfg_multistep_step_kernel,
-// cfg_multistep_step_windows_kernel), with its fp32 x0 history updated in place.
+// cfg_multistep_step_windows_kernel), with its fp32 x0 history updated in place.  Every step kernel has an unguided form
+// (GUIDED = false; for cfg_ddim_kernel the kernel ddim_kernel) for a step outside the guidance interval (arXiv 2404.07724): the model
+// ran the text half alone, the step takes that one prediction as m -- no second load stream, no guidance read, no combine -- and is
+// otherwise the same code.
 // Replaces: the guidance combine + scheduler.step of the denoising loop (pipeline_animation_inference_dual.py:791-800) with
 // DDIMScheduler.step (diffusers/schedulers/scheduling_ddim.py:251-373; eta = 0, v-prediction: 300-350).  Context windows and the
 // guidance rescale have no call site in the reference pipeline: they compose that same step (see their comments).
@@ -36,6 +39,30 @@ __global__ void cfg_ddim_kernel(const T* __restrict__ uncond, const T* __restric
     }
 }
 
+// ---- the unguided form of cfg_ddim_kernel (a step outside the guidance interval: the model ran the text half alone): one prediction,
+//      x_prev = cx * x + cv * pred; coef is cfg_ddim_kernel's (guidance, cx, cv), element 0 not read.  A kernel of its own and not a
+//      template argument of the one above: that one is the default sampler's launch, it keeps its name (the rocprofv3 summaries under
+//      profiles/ name it) and its text -- calling a shared body from it already changes which product hipcc contracts (-ffast-math),
+//      i.e. the default path's bits.  The update is spelled as hipcc contracts the guided line -- cx * x rounded, then one fma with
+//      the prediction -- because left to itself it fuses the other product in some lanes here, and u == c would then not give
+//      cfg_ddim_kernel's bits (tests/test_guidance_interval_gpu.py holds the two to the same bits).
+template <typename T>
+__global__ void ddim_kernel(const T* __restrict__ pred, const T* __restrict__ x, T* __restrict__ out, long n8, float cx, float cv,
+                            const float* __restrict__ coef) {
+    if (coef != nullptr) {
+        cx = coef[1];
+        cv = coef[2];
+    }
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
+        float c[8], s[8];
+        unpack8<T>(((const uint4*)pred)[i], c);
+        unpack8<T>(((const uint4*)x)[i], s);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) s[e] = __fmaf_rn(cv, c[e], cx * s[e]);
+        ((uint4*)out)[i] = pack8<T>(s);
+    }
+}
+
 // ---- CFG combine + the full DDIMScheduler.step (diffusers/schedulers/scheduling_ddim.py:251-373), one elementwise pass:
 //      m = u + g (c - u);  x0 / e from the prediction type (mode bits 0-1: 0 epsilon, 1 v, 2 sample);  x0 clamped to [-1, 1]
 //      (bit 2);  e re-derived from the clamped x0 (bit 3);  out = sa_prev x0 + dir e + sigma z.  sa, sb = sqrt(a_t), sqrt(1 - a_t);
@@ -48,10 +75,11 @@ struct DdimCoefs {
     bool clip, clipped_out;
 };
 
+template <bool GUIDED>
 __device__ __forceinline__ DdimCoefs ddim_coefs(float g, float sa, float sb, float sap, float dir, float sigma, int mode,
                                                 const float* __restrict__ coef) {
     if (coef != nullptr) {          // (guidance, sa, sb, sa_prev, dir, sigma) read on the device: hipGraph replay
-        g = coef[0];
+        if (GUIDED) g = coef[0];     // (an unguided step never reads the guidance)
         sa = coef[1];
         sb = coef[2];
         sap = coef[3];
@@ -110,10 +138,11 @@ struct MultistepCoefs {
     bool clip, hist;                 // hist: c1 != 0, uniform over the launch
 };
 
+template <bool GUIDED>
 __device__ __forceinline__ MultistepCoefs multistep_coefs(float g, float sa, float sb, float cx, float c0, float c1, int mode,
                                                           const float* __restrict__ coef) {
     if (coef != nullptr) {          // (guidance, sa, sb, cx, c0, c1) read on the device: hipGraph replay
-        g = coef[0];
+        if (GUIDED) g = coef[0];
         sa = coef[1];
         sb = coef[2];
         cx = coef[3];
@@ -290,18 +319,21 @@ __device__ __forceinline__ float rescale_mul(float r, float m) {
 }
 
 // RS: the guided prediction is multiplied by rescale_factor(ws, nrec, phi) before the step; those instantiations need workgroups of
-// 256 threads and say so in their launch bounds (1024 is the default, i.e. what the kernel without the factor always had)
-template <typename T, bool RS>
+// 256 threads and say so in their launch bounds (1024 is the default, i.e. what the kernel without the factor always had).
+// GUIDED = false (never with RS: the rescale of a prediction towards its own standard deviation is the identity): m = c, the one
+// prediction of a step outside the guidance interval; `uncond` is not read (the entry points pass null) and neither is the guidance.
+template <typename T, bool RS, bool GUIDED>
 __global__ __launch_bounds__(RS ? 256 : 1024) void cfg_ddim_step_kernel(const T* __restrict__ uncond, const T* __restrict__ cond, const T* __restrict__ x,
                                      const T* __restrict__ noise, T* __restrict__ out, long n8, float g, float sa, float sb,
                                      float sap, float dir, float sigma, int mode, const float* __restrict__ coef,
                                      const float* __restrict__ ws, int nrec, float phi) {
-    const DdimCoefs k = ddim_coefs(g, sa, sb, sap, dir, sigma, mode, coef);
+    static_assert(GUIDED || !RS, "no rescaled unguided step");
+    const DdimCoefs k = ddim_coefs<GUIDED>(g, sa, sb, sap, dir, sigma, mode, coef);
     float r = 1.0f;
     if (RS) r = rescale_factor(ws, nrec, phi);
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
         float u[8], c[8], s[8], z[8];
-        unpack8<T>(((const uint4*)uncond)[i], u);
+        if (GUIDED) unpack8<T>(((const uint4*)uncond)[i], u);
         unpack8<T>(((const uint4*)cond)[i], c);
         unpack8<T>(((const uint4*)x)[i], s);
         if (noise != nullptr) unpack8<T>(((const uint4*)noise)[i], z);
@@ -311,7 +343,7 @@ __global__ __launch_bounds__(RS ? 256 : 1024) void cfg_ddim_step_kernel(const T*
         }
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            const float m = cfg_combine(u[e], c[e], k.g);
+            const float m = GUIDED ? cfg_combine(u[e], c[e], k.g) : c[e];
             s[e] = ddim_step_elem(RS ? rescale_mul(r, m) : m, s[e], z[e], k);
         }
         ((uint4*)out)[i] = pack8<T>(s);
@@ -319,18 +351,19 @@ __global__ __launch_bounds__(RS ? 256 : 1024) void cfg_ddim_step_kernel(const T*
 }
 
 // ---- CFG combine + the multistep update above: the loop of cfg_ddim_step_kernel with the history stream.  hist: float[8 n8], read
-//      (k.hist only) and written by the thread that owns the lane.
-template <typename T, bool RS>
+//      (k.hist only) and written by the thread that owns the lane.  GUIDED: as in cfg_ddim_step_kernel.
+template <typename T, bool RS, bool GUIDED>
 __global__ __launch_bounds__(RS ? 256 : 1024) void cfg_multistep_step_kernel(const T* __restrict__ uncond, const T* __restrict__ cond, const T* __restrict__ x,
                                      float* __restrict__ hist, T* __restrict__ out, long n8, float g, float sa, float sb, float cx,
                                      float c0, float c1, int mode, const float* __restrict__ coef, const float* __restrict__ ws,
                                      int nrec, float phi) {
-    const MultistepCoefs k = multistep_coefs(g, sa, sb, cx, c0, c1, mode, coef);
+    static_assert(GUIDED || !RS, "no rescaled unguided step");
+    const MultistepCoefs k = multistep_coefs<GUIDED>(g, sa, sb, cx, c0, c1, mode, coef);
     float r = 1.0f;
     if (RS) r = rescale_factor(ws, nrec, phi);
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
         float u[8], c[8], s[8], h[8];
-        unpack8<T>(((const uint4*)uncond)[i], u);
+        if (GUIDED) unpack8<T>(((const uint4*)uncond)[i], u);
         unpack8<T>(((const uint4*)cond)[i], c);
         unpack8<T>(((const uint4*)x)[i], s);
         if (k.hist) hist_load8(hist, i, h);
@@ -340,7 +373,7 @@ __global__ __launch_bounds__(RS ? 256 : 1024) void cfg_multistep_step_kernel(con
         }
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            const float m = cfg_combine(u[e], c[e], k.g);
+            const float m = GUIDED ? cfg_combine(u[e], c[e], k.g) : c[e];
             s[e] = multistep_step_elem(RS ? rescale_mul(r, m) : m, s[e], h[e], k);
         }
         hist_store8(hist, i, h);
@@ -361,7 +394,9 @@ __global__ __launch_bounds__(RS ? 256 : 1024) void cfg_multistep_step_kernel(con
 //      whatever the table holds.
 // The blend of the V elements from element e0 on (V = 8: one 16-byte lane inside one frame): mb[] = the guided prediction m above;
 // cb[] (CB only) = the same blend of the text half c_k alone, what the guidance rescale takes std(c) of.
-template <typename T, int V, bool CB>
+// GUIDED = false: pred is [nW, 1, outer, L, inner], the text halves alone; mb[] is their blend -- one load per window, and nothing is
+// read behind the last window's only half.
+template <typename T, int V, bool CB, bool GUIDED = true>
 __device__ __forceinline__ void windows_blend(const T* __restrict__ pred, const int* __restrict__ start, const float* __restrict__ weight,
                                               int nW, int F, int L, int wrap, long inner, long half, long e0, float g, float* mb, float* cb) {
     const long r = e0 % inner, of = e0 / inner;
@@ -377,18 +412,18 @@ __device__ __forceinline__ void windows_blend(const T* __restrict__ pred, const 
         if (j < 0) j += wrap;
         if (j < 0 || j >= L) continue;
         const float wt = weight[j];
-        const long at = (long)w * 2 * half + (o * L + j) * inner + r;
+        const long at = (long)w * (GUIDED ? 2 : 1) * half + (o * L + j) * inner + r;
         float u[V], c[V];
         if (V == 8) {
-            unpack8<T>(*(const uint4*)(pred + at), u);
-            unpack8<T>(*(const uint4*)(pred + at + half), c);
+            if (GUIDED) unpack8<T>(*(const uint4*)(pred + at), u);
+            unpack8<T>(*(const uint4*)(pred + at + (GUIDED ? half : 0)), c);
         } else {
-            u[0] = to_f32<T>(pred[at]);
-            c[0] = to_f32<T>(pred[at + half]);
+            if (GUIDED) u[0] = to_f32<T>(pred[at]);
+            c[0] = to_f32<T>(pred[at + (GUIDED ? half : 0)]);
         }
 #pragma unroll
         for (int e = 0; e < V; ++e) {
-            const float m = wt * cfg_combine(u[e], c[e], g);
+            const float m = wt * (GUIDED ? cfg_combine(u[e], c[e], g) : c[e]);
             acc[e] = first ? m : acc[e] + m;
             if (CB) {
                 const float t = wt * c[e];
@@ -435,20 +470,21 @@ __global__ __launch_bounds__(256) void cfg_rescale_stats_windows_kernel(const T*
     if (threadIdx.x == 0) moments_store(ws, a);
 }
 
-template <typename T, int V, bool RS>
+template <typename T, int V, bool RS, bool GUIDED>
 __global__ __launch_bounds__(RS ? 256 : 1024) void cfg_ddim_step_windows_kernel(const T* __restrict__ pred, const T* __restrict__ x, const T* __restrict__ noise,
                                              T* __restrict__ out, const int* __restrict__ start, const float* __restrict__ weight,
                                              int nW, long outer, int F, int L, int wrap, long inner, float g, float sa, float sb, float sap,
                                              float dir, float sigma, int mode, const float* __restrict__ coef,
                                              const float* __restrict__ ws, int nrec, float phi) {
-    const DdimCoefs k = ddim_coefs(g, sa, sb, sap, dir, sigma, mode, coef);
+    static_assert(GUIDED || !RS, "no rescaled unguided step");
+    const DdimCoefs k = ddim_coefs<GUIDED>(g, sa, sb, sap, dir, sigma, mode, coef);
     float r = 1.0f;
     if (RS) r = rescale_factor(ws, nrec, phi);
     const long nv = outer * F * inner / V;
     const long half = outer * L * inner;              // one CFG half of one window
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
         float m[V], s[V], z[V];
-        windows_blend<T, V, false>(pred, start, weight, nW, F, L, wrap, inner, half, i * V, k.g, m, nullptr);
+        windows_blend<T, V, false, GUIDED>(pred, start, weight, nW, F, L, wrap, inner, half, i * V, k.g, m, nullptr);
         if (V == 8) {
             unpack8<T>(((const uint4*)x)[i], s);
             if (noise != nullptr) unpack8<T>(((const uint4*)noise)[i], z);
@@ -468,20 +504,21 @@ __global__ __launch_bounds__(RS ? 256 : 1024) void cfg_ddim_step_windows_kernel(
 }
 
 // the multistep update on the blend of the windows (windows_blend; wrap: line or ring), hist [outer, F, inner] like x
-template <typename T, int V, bool RS>
+template <typename T, int V, bool RS, bool GUIDED>
 __global__ __launch_bounds__(RS ? 256 : 1024) void cfg_multistep_step_windows_kernel(const T* __restrict__ pred, const T* __restrict__ x, float* __restrict__ hist,
                                              T* __restrict__ out, const int* __restrict__ start, const float* __restrict__ weight,
                                              int nW, long outer, int F, int L, int wrap, long inner, float g, float sa, float sb, float cx,
                                              float c0, float c1, int mode, const float* __restrict__ coef,
                                              const float* __restrict__ ws, int nrec, float phi) {
-    const MultistepCoefs k = multistep_coefs(g, sa, sb, cx, c0, c1, mode, coef);
+    static_assert(GUIDED || !RS, "no rescaled unguided step");
+    const MultistepCoefs k = multistep_coefs<GUIDED>(g, sa, sb, cx, c0, c1, mode, coef);
     float r = 1.0f;
     if (RS) r = rescale_factor(ws, nrec, phi);
     const long nv = outer * F * inner / V;
     const long half = outer * L * inner;              // one CFG half of one window
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
         float m[V], s[V], h[V];
-        windows_blend<T, V, false>(pred, start, weight, nW, F, L, wrap, inner, half, i * V, k.g, m, nullptr);
+        windows_blend<T, V, false, GUIDED>(pred, start, weight, nW, F, L, wrap, inner, half, i * V, k.g, m, nullptr);
         if (V == 8) unpack8<T>(((const uint4*)x)[i], s);
         else s[0] = to_f32<T>(x[i]);
         if (k.hist) {
@@ -566,21 +603,25 @@ static int check_windows(const char* name, const Windows& w, bool others, const 
     IM360_CHECK_ARG(((uintptr_t)w.start % 4) == 0 && ((uintptr_t)w.weight % 4) == 0, "%s: misaligned table", name);
     return IM360_OK;
 }
+// The instantiation a step launch selects: 0 guided, 1 guided with the guidance rescale, 2 unguided (one prediction; never rescaled)
+static int step_variant(bool rescale, bool guided) { return guided ? (rescale ? 1 : 0) : 2; }
 static unsigned step_blocks(long lanes) { return (unsigned)((lanes + 255) / 256 > 4096 ? 4096 : (lanes + 255) / 256); }
 
-// im360_cfg_ddim_step and, with the guidance rescale, im360_cfg_ddim_step_rescale: checks, then the launch
+// im360_cfg_ddim_step and, with the guidance rescale, im360_cfg_ddim_step_rescale: checks, then the launch.  !guided (im360_ddim_step):
+// `cond` is the one prediction, `uncond` is not looked at.
 static int cfg_ddim_step(const char* name, const void* uncond, const void* cond, const void* x, void* out, int64_t n, const StepArgs& s,
-                         bool rescale, int dtype, void* stream) {
-    if (const int rc = check_tensors(name, {uncond, cond, x, out}, s.noise, n)) return rc;
+                         bool rescale, int dtype, void* stream, bool guided = true) {
+    if (const int rc = check_tensors(name, {guided ? uncond : cond, cond, x, out}, s.noise, n)) return rc;
     if (const int rc = check_step(name, s)) return rc;
     if (const int rc = rescale ? check_step_rescale(name, s, n) : IM360_OK) return rc;
     const long n8 = n / 8;
     const int nrec = rescale ? (int)im360_cfg_rescale_records(n) : 0;
     return with_dtype(dtype, name, [&](auto t) {
         using T = typename decltype(t)::type;
-        with_bool(rescale, [&](auto rs) {
-            hipLaunchKernelGGL((cfg_ddim_step_kernel<T, decltype(rs)::value>), dim3(step_blocks(n8)), dim3(256), 0, (hipStream_t)stream,
-                               (const T*)uncond, (const T*)cond, (const T*)x, (const T*)s.noise, (T*)out, n8, s.g, s.sa, s.sb, s.sap, s.dir,
+        with_const<0, 1, 2>(step_variant(rescale, guided), [&](auto v) {
+            constexpr int VAR = decltype(v)::value;
+            hipLaunchKernelGGL((cfg_ddim_step_kernel<T, VAR == 1, VAR != 2>), dim3(step_blocks(n8)), dim3(256), 0, (hipStream_t)stream,
+                               (const T*)(guided ? uncond : nullptr), (const T*)cond, (const T*)x, (const T*)s.noise, (T*)out, n8, s.g, s.sa, s.sb, s.sap, s.dir,
                                s.sigma, s.mode, (const float*)s.coef_dev, (const float*)s.ws, nrec, s.phi);
         });
         return im360_launch_status();
@@ -588,8 +629,9 @@ static int cfg_ddim_step(const char* name, const void* uncond, const void* cond,
 }
 
 // the four windowed step entry points (w.wrap: line or ring; rescale: with or without the guidance rescale): checks, then the launch
+// !guided: w.pred is [nW, 1, outer, L, inner]
 static int cfg_ddim_step_windows(const char* name, const Windows& w, const void* x, void* out, const StepArgs& s, bool rescale, int dtype,
-                                 void* stream) {
+                                 void* stream, bool guided = true) {
     if (const int rc = check_windows(name, w, x && out, &s)) return rc;          // (mode and noise of `s` inside: the entry points' order)
     if (const int rc = rescale ? check_step_rescale(name, s, w.elements()) : IM360_OK) return rc;
     const bool vec = (w.inner % 8) == 0 && (((uintptr_t)w.pred | (uintptr_t)x | (uintptr_t)s.noise | (uintptr_t)out) % 16) == 0;
@@ -597,8 +639,9 @@ static int cfg_ddim_step_windows(const char* name, const Windows& w, const void*
     const int nrec = rescale ? (int)im360_cfg_rescale_records(w.elements()) : 0;
     return with_dtype(dtype, name, [&](auto t) {
         using T = typename decltype(t)::type;
-        with_const<1, 8>(vec ? 8 : 1, [&](auto v) { with_bool(rescale, [&](auto rs) {
-            hipLaunchKernelGGL((cfg_ddim_step_windows_kernel<T, decltype(v)::value, decltype(rs)::value>), dim3(step_blocks(nv)), dim3(256), 0,
+        with_const<1, 8>(vec ? 8 : 1, [&](auto v) { with_const<0, 1, 2>(step_variant(rescale, guided), [&](auto sv) {
+            constexpr int VAR = decltype(sv)::value;
+            hipLaunchKernelGGL((cfg_ddim_step_windows_kernel<T, decltype(v)::value, VAR == 1, VAR != 2>), dim3(step_blocks(nv)), dim3(256), 0,
                                (hipStream_t)stream, (const T*)w.pred, (const T*)x, (const T*)s.noise, (T*)out, (const int*)w.start,
                                (const float*)w.weight, w.nW, (long)w.outer, (int)w.F, (int)w.L, w.wrap, (long)w.inner, s.g, s.sa, s.sb, s.sap,
                                s.dir, s.sigma, s.mode, (const float*)s.coef_dev, (const float*)s.ws, nrec, s.phi);
@@ -643,19 +686,20 @@ static int check_multistep(const char* name, const MultistepArgs& a, int64_t n) 
     return a.rescale() ? check_step_rescale(name, a.s, n) : IM360_OK;
 }
 
-// im360_cfg_multistep_step: checks, then the launch
+// im360_cfg_multistep_step: checks, then the launch.  !guided (im360_multistep_step): `cond` is the one prediction, no workspace.
 static int cfg_multistep_step(const char* name, const void* uncond, const void* cond, const void* x, void* out, int64_t n,
-                              const MultistepArgs& a, int dtype, void* stream) {
-    if (const int rc = check_tensors(name, {uncond, cond, x, a.hist, out}, nullptr, n)) return rc;
+                              const MultistepArgs& a, int dtype, void* stream, bool guided = true) {
+    if (const int rc = check_tensors(name, {guided ? uncond : cond, cond, x, a.hist, out}, nullptr, n)) return rc;
     if (const int rc = check_step(name, a.s)) return rc;
     if (const int rc = check_multistep(name, a, n)) return rc;
     const long n8 = n / 8;
     const int nrec = a.rescale() ? (int)im360_cfg_rescale_records(n) : 0;
     return with_dtype(dtype, name, [&](auto t) {
         using T = typename decltype(t)::type;
-        with_bool(a.rescale(), [&](auto rs) {
-            hipLaunchKernelGGL((cfg_multistep_step_kernel<T, decltype(rs)::value>), dim3(step_blocks(n8)), dim3(256), 0, (hipStream_t)stream,
-                               (const T*)uncond, (const T*)cond, (const T*)x, (float*)a.hist, (T*)out, n8, a.s.g, a.s.sa, a.s.sb, a.cx, a.c0,
+        with_const<0, 1, 2>(step_variant(a.rescale(), guided), [&](auto v) {
+            constexpr int VAR = decltype(v)::value;
+            hipLaunchKernelGGL((cfg_multistep_step_kernel<T, VAR == 1, VAR != 2>), dim3(step_blocks(n8)), dim3(256), 0, (hipStream_t)stream,
+                               (const T*)(guided ? uncond : nullptr), (const T*)cond, (const T*)x, (float*)a.hist, (T*)out, n8, a.s.g, a.s.sa, a.s.sb, a.cx, a.c0,
                                a.c1, a.s.mode, (const float*)a.s.coef_dev, (const float*)a.s.ws, nrec, a.s.phi);
         });
         return im360_launch_status();
@@ -664,7 +708,7 @@ static int cfg_multistep_step(const char* name, const void* uncond, const void* 
 
 // im360_cfg_multistep_step_windows (w.wrap: line or ring): checks, then the launch
 static int cfg_multistep_step_windows(const char* name, const Windows& w, int64_t wrap, const void* x, void* out, const MultistepArgs& a,
-                                      int dtype, void* stream) {
+                                      int dtype, void* stream, bool guided = true) {
     if (const int rc = check_windows(name, w, x && a.hist && out, &a.s)) return rc;
     IM360_CHECK_ARG(wrap == 0 || wrap == w.F, "%s: wrap=%ld must be 0 (line) or F=%ld (ring)", name, (long)wrap, (long)w.F);
     IM360_CHECK_ARG(((uintptr_t)a.hist % 4) == 0, "%s: misaligned history", name);
@@ -674,8 +718,9 @@ static int cfg_multistep_step_windows(const char* name, const Windows& w, int64_
     const int nrec = a.rescale() ? (int)im360_cfg_rescale_records(w.elements()) : 0;
     return with_dtype(dtype, name, [&](auto t) {
         using T = typename decltype(t)::type;
-        with_const<1, 8>(vec ? 8 : 1, [&](auto v) { with_bool(a.rescale(), [&](auto rs) {
-            hipLaunchKernelGGL((cfg_multistep_step_windows_kernel<T, decltype(v)::value, decltype(rs)::value>), dim3(step_blocks(nv)), dim3(256), 0,
+        with_const<1, 8>(vec ? 8 : 1, [&](auto v) { with_const<0, 1, 2>(step_variant(a.rescale(), guided), [&](auto sv) {
+            constexpr int VAR = decltype(sv)::value;
+            hipLaunchKernelGGL((cfg_multistep_step_windows_kernel<T, decltype(v)::value, VAR == 1, VAR != 2>), dim3(step_blocks(nv)), dim3(256), 0,
                                (hipStream_t)stream, (const T*)w.pred, (const T*)x, (float*)a.hist, (T*)out, (const int*)w.start,
                                (const float*)w.weight, w.nW, (long)w.outer, (int)w.F, (int)w.L, w.wrap, (long)w.inner, a.s.g, a.s.sa, a.s.sb,
                                a.cx, a.c0, a.c1, a.s.mode, (const float*)a.s.coef_dev, (const float*)a.s.ws, nrec, a.s.phi);
@@ -823,4 +868,68 @@ extern "C" __attribute__((visibility("default"))) int im360_cfg_multistep_step_w
     const im360::Windows w{pred, start, weight, nW, wrap == 0 ? 0 : (int)F, outer, F, L, inner};
     const im360::MultistepArgs a{im360::multistep_step_args(guidance, sqrt_a, sqrt_b, mode, phi, ws, ws_floats, coef_dev), cx, c0, c1, hist};
     return im360::cfg_multistep_step_windows("cfg_multistep_step_windows", w, wrap, x, out, a, dtype, stream);
+}
+
+// ---- the unguided forms: a step outside the guidance interval (arXiv 2404.07724), where the model ran the text half alone.  `pred` is
+//      that one prediction and takes the place of uncond + g (cond - uncond); there is no guidance argument, and coef_dev is the
+//      sibling's vector (element 0, the guidance, is not read).  For finite inputs each gives what its sibling gives when uncond and
+//      cond are the same tensor, bit for bit.  No rescale forms: a prediction rescaled towards its own standard deviation is itself.
+
+// out = cx * x + cv * pred; coef_dev: float[3] = (guidance, cx, cv) of im360_cfg_ddim_update
+extern "C" __attribute__((visibility("default"))) int im360_ddim_update(const void* pred, const void* x, void* out, int64_t n, float cx, float cv,
+                                   int dtype, void* stream, const void* coef_dev) {
+    using namespace im360;
+    if (const int rc = check_tensors("ddim_update", {pred, x, out}, nullptr, n)) return rc;
+    return with_dtype(dtype, "ddim_update", [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((ddim_kernel<T>), dim3(step_blocks(n / 8)), dim3(256), 0, (hipStream_t)stream, (const T*)pred, (const T*)x, (T*)out,
+                           (long)(n / 8), cx, cv, (const float*)coef_dev);
+        return im360_launch_status();
+    });
+}
+
+// out = DDIMScheduler.step(pred, x, noise): im360_cfg_ddim_step without the combine
+extern "C" __attribute__((visibility("default"))) int im360_ddim_step(const void* pred, const void* x, const void* noise, void* out, int64_t n,
+                                   float sqrt_a, float sqrt_b, float sqrt_a_prev, float dir, float sigma, int mode, int dtype, void* stream,
+                                   const void* coef_dev) {
+    const im360::StepArgs s{0.0f, sqrt_a, sqrt_b, sqrt_a_prev, dir, sigma, mode, noise, coef_dev, nullptr, 0, 0.0f};
+    return im360::cfg_ddim_step("ddim_step", nullptr, pred, x, out, n, s, false, dtype, stream, false);
+}
+
+// im360_cfg_ddim_step_windows on the blend of the text halves alone: pred [nW, 1, outer, L, inner]
+extern "C" __attribute__((visibility("default"))) int im360_ddim_step_windows(const void* pred, const void* x, const void* noise, void* out,
+                                   const void* start, const void* weight, int nW, int64_t outer, int64_t F, int64_t L, int64_t inner,
+                                   float sqrt_a, float sqrt_b, float sqrt_a_prev, float dir, float sigma, int mode, int dtype, void* stream,
+                                   const void* coef_dev) {
+    const im360::Windows w{pred, start, weight, nW, 0, outer, F, L, inner};
+    const im360::StepArgs s{0.0f, sqrt_a, sqrt_b, sqrt_a_prev, dir, sigma, mode, noise, coef_dev, nullptr, 0, 0.0f};
+    return im360::cfg_ddim_step_windows("ddim_step_windows", w, x, out, s, false, dtype, stream, false);
+}
+
+// the same with the windows on a ring of F frames (preconditions of im360_cfg_ddim_step_windows_ring)
+extern "C" __attribute__((visibility("default"))) int im360_ddim_step_windows_ring(const void* pred, const void* x, const void* noise, void* out,
+                                   const void* start, const void* weight, int nW, int64_t outer, int64_t F, int64_t L, int64_t inner,
+                                   float sqrt_a, float sqrt_b, float sqrt_a_prev, float dir, float sigma, int mode, int dtype, void* stream,
+                                   const void* coef_dev) {
+    const im360::Windows w{pred, start, weight, nW, (int)F, outer, F, L, inner};
+    const im360::StepArgs s{0.0f, sqrt_a, sqrt_b, sqrt_a_prev, dir, sigma, mode, noise, coef_dev, nullptr, 0, 0.0f};
+    return im360::cfg_ddim_step_windows("ddim_step_windows_ring", w, x, out, s, false, dtype, stream, false);
+}
+
+// out = the DPM-Solver++ 2M update of x on pred, hist <- x0: im360_cfg_multistep_step without the combine
+extern "C" __attribute__((visibility("default"))) int im360_multistep_step(const void* pred, const void* x, void* hist, void* out, int64_t n,
+                                   float sqrt_a, float sqrt_b, float cx, float c0, float c1, int mode, int dtype, void* stream,
+                                   const void* coef_dev) {
+    const im360::MultistepArgs a{im360::multistep_step_args(0.0f, sqrt_a, sqrt_b, mode, 0.0f, nullptr, 0, coef_dev), cx, c0, c1, hist};
+    return im360::cfg_multistep_step("multistep_step", nullptr, pred, x, out, n, a, dtype, stream, false);
+}
+
+// im360_cfg_multistep_step_windows on the blend of the text halves alone: pred [nW, 1, outer, L, inner]; wrap = 0 or F
+extern "C" __attribute__((visibility("default"))) int im360_multistep_step_windows(const void* pred, const void* x, void* hist, void* out,
+                                   const void* start, const void* weight, int nW, int64_t outer, int64_t F, int64_t L, int64_t inner, int64_t wrap,
+                                   float sqrt_a, float sqrt_b, float cx, float c0, float c1, int mode, int dtype, void* stream,
+                                   const void* coef_dev) {
+    const im360::Windows w{pred, start, weight, nW, wrap == 0 ? 0 : (int)F, outer, F, L, inner};
+    const im360::MultistepArgs a{im360::multistep_step_args(0.0f, sqrt_a, sqrt_b, mode, 0.0f, nullptr, 0, coef_dev), cx, c0, c1, hist};
+    return im360::cfg_multistep_step_windows("multistep_step_windows", w, wrap, x, out, a, dtype, stream, false);
 }

@@ -12,6 +12,10 @@ statistics launch in front of each branch's step launch; its workspace is a grap
 A partly regenerated clip (``keep``, pipeline ``regenerate_mask``) adds one captured ``keep_latents`` launch after the two step launches;
 its two coefficients are a fifth tiny buffer, refreshed per step through a pinned ring of its own.  A release-mode region
 (``regenerate_mode="release"``) captures ``keep_latents_release`` in its place and uploads three: the step's threshold rides along.
+A guidance interval (``guidance_interval``, arXiv 2404.07724) whose run holds guided and unguided steps owns TWO captured graphs over the
+same static latents, x0 histories, coefficient buffers, keep coefficients and coins: the CFG-batch body, and the text-half body (the
+model on rows [1:2] / [m:2m] of every input, the unguided step kernels).  ``step`` uploads as ever and replays the one
+``scheduler.guided_steps`` selects; a run whose steps are all of one kind builds only that graph.
 """
 import random
 
@@ -44,7 +48,8 @@ class GraphedDenoiseStep:
     always_step_kernel = False      # (GraphedWindowedStep) the six-coefficient step kernel for eta = 0 as well
 
     def __init__(self, mv, scheduler, inputs, cameras, pano_latent, pers_latent, guidance, use_fps=True, warmup=2, cfg_pair=None,
-                 eta=0.0, generator=None, use_clipped_model_output=False, frame_shard=None, guidance_rescale=0.0, keep=None):
+                 eta=0.0, generator=None, use_clipped_model_output=False, frame_shard=None, guidance_rescale=0.0, keep=None,
+                 guidance_interval=None, steps=None):
         """``inputs``: the keyword tensors of MultiViewBaseModel.forward (CFG-batched, resident on the GPU);
         ``pano_latent`` [1,4,F,H,W] / ``pers_latent`` [1,m,4,F,h,w]: initial noisy latents.
         Frame-sharded models (``mv.set_frame_shard``) capture their all-to-alls with the step: the exchange buffers are
@@ -54,11 +59,25 @@ class GraphedDenoiseStep:
         ``eta`` / ``generator`` / ``use_clipped_model_output``: DDIMScheduler.step's keywords (defaults: the eta = 0 update).
         ``frame_shard`` (dist.FrameShard): with eta > 0 the variance noise is drawn for the whole clip and cut to the local
         frames, like the initial noise.  ``guidance_rescale``: ``DDIMScheduler.fused_cfg_step``'s keyword.
-        ``keep`` (pipeline.KeepRegion): the kept region of a given clip, blended into both latents after the two updates."""
+        ``keep`` (pipeline.KeepRegion): the kept region of a given clip, blended into both latents after the two updates.
+        ``guidance_interval`` (None: every step guided, one graph, nothing else runs) with ``steps``, the run's timestep list: the kinds
+        of step the run holds (``scheduler.guided_steps``) are each warmed up and captured once.  The caller keeps
+        ``context.ip_cache_slots`` open for both forms of the SAM features (2 entries; 2 per window) while this is built and used."""
         self.mv, self.sch, self.inp, self.cams, self.g = mv, scheduler, inputs, cameras, float(guidance)
         self.cfg_pair = cfg_pair
         self.eta, self.gen, self.clipped, self.shard = float(eta), generator, bool(use_clipped_model_output), frame_shard
         self.rescale = float(guidance_rescale)
+        self.interval = guidance_interval
+        kinds = [True]                           # True: the CFG-batch body, False: the text-half body
+        if guidance_interval is not None:
+            if cfg_pair is not None or frame_shard is not None:
+                raise ValueError("guidance_interval cannot be combined with cfg_pair / frame_shard (the text-half step of a sharded model is "
+                                 "not implemented)")
+            flags = scheduler.guided_steps(scheduler._timesteps_host if steps is None else steps, guidance_interval)
+            kinds = [k for k in (True, False) if k in flags]
+            if False in kinds:
+                from .dist import cfg_half_inputs
+                self.inp_text = cfg_half_inputs(inputs, 1)       # views, made once: the IP-token cache keys on their identity
         self.step_kernel = self.always_step_kernel or scheduler.uses_step_kernel(self.eta, self.clipped, self.rescale)
         dev = pano_latent.device
         # private copies: the caller's tensors may alias the model-input buffers the body writes into
@@ -95,21 +114,25 @@ class GraphedDenoiseStep:
                 # issue every launch once; its numbers are dropped, the start latents restored below, and step() uploads the real one)
                 self._upload(scheduler._timesteps_host[0], draw=False)
                 for _ in range(warmup):
-                    self._body()
+                    for kind in kinds:
+                        (self._body if kind else self._body_text)()
         finally:
             mv.dual_stream_eager = was_eager
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        if generator is not None:
-            self.graph.register_generator_state(generator)      # each replay advances it like the eager draws would
-        mv.coins_preloaded = True
-        try:
-            # thread-local capture mode: a RCCL watchdog / other host thread touching the runtime must not abort the capture
-            with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-                self._body()
-        finally:
-            mv.coins_preloaded = False
+        self.graphs = {}
+        for kind in kinds:
+            graph = self.graphs[kind] = torch.cuda.CUDAGraph()
+            if generator is not None:
+                graph.register_generator_state(generator)      # each replay advances it like the eager draws would
+            mv.coins_preloaded = True
+            try:
+                # thread-local capture mode: a RCCL watchdog / other host thread touching the runtime must not abort the capture
+                with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                    (self._body if kind else self._body_text)()
+            finally:
+                mv.coins_preloaded = False
+        self.graph = self.graphs.get(True)       # (the CFG-batch graph; None in a run without a guided step)
         # the eager warm-up steps advanced the latents; capture itself executes nothing: start from the given ones
         self.pano_lat.copy_(init_pano)
         self.pers_lat.copy_(init_pers)
@@ -151,6 +174,43 @@ class GraphedDenoiseStep:
         self.pano_lat.copy_(new_pano)
         self.pers_lat.copy_(new_pers)
 
+    def _body_text(self):
+        """The body of an unguided step: the model on the text half alone, then the unguided form of each branch's step kernel.  The
+        IP-adapter noise is drawn for the whole CFG batch and cut (``mv._ip_noise_half``), the variance noise is drawn as ever: the
+        generator advances exactly as in ``_body``."""
+        inp = self.inp_text
+        inp["pano_latent"][:, :4] = self.pano_lat
+        inp["latents"][:, :, :4] = self.pers_lat
+        was, was_half = self.mv.coins_preloaded, self.mv._ip_noise_half
+        self.mv.coins_preloaded, self.mv._ip_noise_half = True, (1, 2)
+        try:
+            pred_pers, pred_pano = self.mv(
+                latents=inp["latents"], pano_latent=inp["pano_latent"], timestep=self.timestep,
+                prompt_embd=inp["prompt_embd"], pano_prompt_embd=inp["pano_prompt_embd"], cameras=self.cams,
+                use_fps_condition=self.use_fps, use_ip_plus_cross_attention=True,
+                fps_tensor_pano=inp["fps_tensor_pano"], fps_tensor_pers=inp["fps_tensor_pers"],
+                reference_images_clip_feat_pano=inp["reference_images_clip_feat_pano"],
+                reference_images_clip_feat_pers=inp["reference_images_clip_feat_pers"],
+                relative_position_tensor=inp["relative_position_tensor"], pitchs_tensor=inp["pitchs_tensor"])
+        finally:
+            self.mv.coins_preloaded, self.mv._ip_noise_half = was, was_half
+        self.pred_pano_text, self.pred_pers_text = pred_pano, pred_pers          # static graph-pool tensors (inspection / tests)
+        ldt, mdt = self.pano_lat.dtype, pred_pano.dtype
+        kw = dict(eta=self.eta, use_clipped_model_output=self.clipped, guidance_rescale=self.rescale)
+        new_pano = self.sch.fused_step(pred_pano.to(ldt), None, self.pano_lat, coef_dev=self.coef, noise=self._noise(self.pano_lat, mdt, 2),
+                                       **kw, **self._history(0))
+        new_pers = self.sch.fused_step(pred_pers.to(ldt), None, self.pers_lat, coef_dev=self.coef, noise=self._noise(self.pers_lat, mdt, 3),
+                                       **kw, **self._history(1))
+        self._keep(new_pano, new_pers)
+        self.pano_lat.copy_(new_pano)
+        self.pers_lat.copy_(new_pers)
+
+    def _graph_for(self, t_host):
+        """The graph of the step at timestep ``t_host``: the one ``scheduler.guided_steps`` selects."""
+        if self.interval is None:
+            return self.graph
+        return self.graphs[self.sch.guided_steps([t_host], self.interval)[0]]
+
     def _history(self, branch):
         """``history=`` of one branch's step call (0 panorama, 1 perspective); nothing with a scheduler that keeps none."""
         return {} if self.hist is None else dict(history=self.hist[branch])
@@ -185,12 +245,12 @@ class GraphedDenoiseStep:
     def step(self, t_host):
         """Advance the latents by one DDIM step at (host int) timestep ``t_host``."""
         self._upload(t_host)
-        self.graph.replay()
+        self._graph_for(t_host).replay()
         return self.pano_lat, self.pers_lat
 
     def restart(self, pano_latent, pers_latent):
         """Another run of the schedule on the captured step (pipeline ``free_init_iters``): the given start latents are copied into the
-        static ones -- no new capture, no warm-up.  ``step`` returns the static buffers, so a caller that keeps a result clones it
+        static ones -- no new capture, no warm-up (both graphs of a guidance interval read them).  ``step`` returns the static buffers, so a caller that keeps a result clones it
         first.  A multistep scheduler's histories need no reset: the first step of a run is first order and only writes them."""
         self.pano_lat.copy_(pano_latent)
         self.pers_lat.copy_(pers_latent)
@@ -209,15 +269,44 @@ class GraphedWindowedStep(GraphedDenoiseStep):
     always_step_kernel = True
 
     def __init__(self, mv, scheduler, inputs, cameras, pano_latent, pers_latent, guidance, plan, use_fps=True, warmup=1, eta=0.0,
-                 generator=None, use_clipped_model_output=False, guidance_rescale=0.0, keep=None):
+                 generator=None, use_clipped_model_output=False, guidance_rescale=0.0, keep=None, guidance_interval=None, steps=None):
         dev = pano_latent.device
         self.plan = plan
         self.static = plan.static_inputs(inputs)
-        self.preds_pers, self.preds_pano = plan.pred_buffers(pano_latent, pers_latent)
+        flags = scheduler.guided_steps(scheduler._timesteps_host if steps is None else steps, guidance_interval)
+        if True in flags:
+            self.preds_pers, self.preds_pano = plan.pred_buffers(pano_latent, pers_latent)
+        if False in flags:
+            # the text halves of every window's conditioning, views made once; [nW, 1, ...] prediction buffers
+            self.static_text = plan.text_half(self.static)
+            self.preds_pers_text, self.preds_pano_text = plan.pred_buffers(pano_latent, pers_latent, halves=1)
         self.coins = torch.zeros(len(plan), 8, dtype=torch.int32, device=dev)
         self._up_k = _PinnedUploads(self.coins)
         super().__init__(mv, scheduler, inputs, cameras, pano_latent, pers_latent, guidance, use_fps=use_fps, warmup=warmup, eta=eta,
-                         generator=generator, use_clipped_model_output=use_clipped_model_output, guidance_rescale=guidance_rescale, keep=keep)
+                         generator=generator, use_clipped_model_output=use_clipped_model_output, guidance_rescale=guidance_rescale, keep=keep,
+                         guidance_interval=guidance_interval, steps=steps)
+
+    def _body_text(self):
+        inp = self.inp_text
+        inp["pano_latent"][:, :4] = self.pano_lat
+        inp["latents"][:, :, :4] = self.pers_lat
+        was_half = self.mv._ip_noise_half
+        self.mv._ip_noise_half = (1, 2)
+        try:
+            self.plan.forward(self.mv, inp, self.static_text, self.cams, self.timestep, self.use_fps, self.preds_pers_text,
+                              self.preds_pano_text, coins=self.coins)
+        finally:
+            self.mv._ip_noise_half = was_half
+        mdt = self.mv.unet.dtype
+        kw = dict(coef_dev=self.coef, eta=self.eta, use_clipped_model_output=self.clipped, guidance_rescale=self.rescale,
+                  ring=self.plan.loop)
+        new_pano = self.sch.fused_step_windows(self.preds_pano_text, self.plan.starts_dev, self.plan.weights, None, self.pano_lat,
+                                               noise=self._noise(self.pano_lat, mdt, 2), **kw, **self._history(0))
+        new_pers = self.sch.fused_step_windows(self.preds_pers_text, self.plan.starts_dev, self.plan.weights, None, self.pers_lat,
+                                               noise=self._noise(self.pers_lat, mdt, 3), **kw, **self._history(1))
+        self._keep(new_pano, new_pers)
+        self.pano_lat.copy_(new_pano)
+        self.pers_lat.copy_(new_pers)
 
     def _body(self):
         inp = self.inp

@@ -66,6 +66,12 @@ _SIGNATURES = {
                                                                                                        _PTR, _PTR]),
     "im360_cfg_multistep_step": (_INT, [_PTR] * 5 + [_I64] + [_F32] * 6 + [_INT, _F32, _PTR, _I64, _INT, _PTR, _PTR]),
     "im360_cfg_multistep_step_windows": (_INT, [_PTR] * 6 + [_INT] + [_I64] * 5 + [_F32] * 6 + [_INT, _F32, _PTR, _I64, _INT, _PTR, _PTR]),
+    "im360_ddim_update": (_INT, [_PTR] * 3 + [_I64] + [_F32] * 2 + [_INT, _PTR, _PTR]),
+    "im360_ddim_step": (_INT, [_PTR] * 4 + [_I64] + [_F32] * 5 + [_INT, _INT, _PTR, _PTR]),
+    "im360_ddim_step_windows": (_INT, [_PTR] * 6 + [_INT] + [_I64] * 4 + [_F32] * 5 + [_INT, _INT, _PTR, _PTR]),
+    "im360_ddim_step_windows_ring": (_INT, [_PTR] * 6 + [_INT] + [_I64] * 4 + [_F32] * 5 + [_INT, _INT, _PTR, _PTR]),
+    "im360_multistep_step": (_INT, [_PTR] * 4 + [_I64] + [_F32] * 5 + [_INT, _INT, _PTR, _PTR]),
+    "im360_multistep_step_windows": (_INT, [_PTR] * 6 + [_INT] + [_I64] * 5 + [_F32] * 5 + [_INT, _INT, _PTR, _PTR]),
     "im360_noise_latents": (_INT, [_PTR] * 6 + [_I64] * 5 + [_F32, _F32, _INT, _PTR]),
     "im360_keep_latents": (_INT, [_PTR] * 7 + [_I64] * 5 + [_F32, _F32, _INT, _PTR, _PTR]),
     "im360_keep_latents_release": (_INT, [_PTR] * 7 + [_I64] * 5 + [_F32, _F32, _F32, _INT, _PTR, _PTR]),
@@ -937,14 +943,15 @@ def cfg_ddim_step(uncond, cond, sample, noise, mode, coefs, coef_dev=None, resca
     return out
 
 
-def _windows_geometry(preds, sample, starts, weights):
-    """(nW, outer, F, L, inner) of a windowed step after the layout checks of ``cfg_ddim_step_windows``."""
+def _windows_geometry(preds, sample, starts, weights, halves=2):
+    """(nW, outer, F, L, inner) of a windowed step after the layout checks of ``cfg_ddim_step_windows``; ``halves=1``: ``preds`` holds
+    the text halves alone (the unguided steps)."""
     assert preds.is_contiguous() and sample.is_contiguous() and preds.dtype == sample.dtype
     assert sample.dim() in (5, 6) and sample.shape[0] == 1, "sample must be [1, 4, F, H, W] or [1, m, 4, F, h, w]"
     fd = sample.dim() - 3
     outer, F, inner = math.prod(sample.shape[:fd]), sample.shape[fd], math.prod(sample.shape[fd + 1:])
     nW, L = preds.shape[0], preds.shape[fd + 1]
-    assert tuple(preds.shape) == (nW, 2, *sample.shape[1:fd], L, *sample.shape[fd + 1:]), (tuple(preds.shape), tuple(sample.shape))
+    assert tuple(preds.shape) == (nW, halves, *sample.shape[1:fd], L, *sample.shape[fd + 1:]), (tuple(preds.shape), tuple(sample.shape))
     assert starts.dtype == torch.int32 and starts.is_contiguous() and starts.numel() == nW
     assert weights.dtype == torch.float32 and weights.is_contiguous() and weights.numel() == L and 1 <= L <= F
     return nW, outer, F, L, inner
@@ -1041,6 +1048,70 @@ def cfg_multistep_step_windows(preds, sample, hist, starts, weights, mode, coefs
                                                 F if ring else 0, *(float(v) for v in coefs), int(mode), float(rescale), _p(ws),
                                                 0 if ws is None else ws.numel(), _dt(sample), _stream(), _p(coef_dev))
     _check(rc, "im360_cfg_multistep_step_windows")
+    return out
+
+
+# ---- the unguided forms: a step outside the guidance interval (arXiv 2404.07724; AnimationPipeline guidance_interval), where the model
+#      ran the text half alone.  ``pred`` is that one prediction; ``coefs`` / ``coef_dev`` are the SIBLING's vectors (element 0, the
+#      guidance, is not read), so both forms of a run share one coefficient buffer.  For finite inputs each returns what its sibling
+#      returns for uncond = cond = pred, bit for bit.  No ``rescale``: a prediction rescaled towards its own deviation is itself.
+def ddim_update(pred, sample, cx, cv, coef_dev=None):
+    """``cfg_ddim_update`` on one prediction: cx * sample + cv * pred; ``coef_dev`` = device float32[3] (guidance, cx, cv)."""
+    _dev(pred, sample)
+    assert pred.is_contiguous() and sample.is_contiguous() and pred.shape == sample.shape and pred.dtype == sample.dtype
+    out = torch.empty(sample.shape, dtype=sample.dtype, device=sample.device)
+    rc = lib().im360_ddim_update(_p(pred), _p(sample), _p(out), sample.numel(), float(cx), float(cv), _dt(sample), _stream(), _p(coef_dev))
+    _check(rc, "im360_ddim_update")
+    return out
+
+
+def ddim_step(pred, sample, noise, mode, coefs, coef_dev=None):
+    """``cfg_ddim_step`` on one prediction: DDIMScheduler.step(pred, t, sample); ``coefs`` the six of ``step_coefficients``."""
+    _dev(pred, sample, noise)
+    assert pred.is_contiguous() and sample.is_contiguous() and pred.shape == sample.shape and pred.dtype == sample.dtype
+    _check_step_noise("ddim_step", sample, noise, coefs, coef_dev)
+    out = torch.empty(sample.shape, dtype=sample.dtype, device=sample.device)
+    rc = lib().im360_ddim_step(_p(pred), _p(sample), _p(noise), _p(out), sample.numel(), *(float(v) for v in coefs[1:]), int(mode),
+                               _dt(sample), _stream(), _p(coef_dev))
+    _check(rc, "im360_ddim_step")
+    return out
+
+
+def ddim_step_windows(preds, sample, noise, starts, weights, mode, coefs, coef_dev=None, ring=False):
+    """``cfg_ddim_step_windows`` on the blend of the text halves alone: ``preds`` [nW, 1, *sample.shape with F -> L]."""
+    _dev(preds, sample, noise, starts, weights)
+    nW, outer, F, L, inner = _windows_geometry(preds, sample, starts, weights, halves=1)
+    _check_step_noise("ddim_step_windows", sample, noise, coefs, coef_dev)
+    out = torch.empty(sample.shape, dtype=sample.dtype, device=sample.device)
+    name = "im360_ddim_step_windows_ring" if ring else "im360_ddim_step_windows"
+    rc = getattr(lib(), name)(_p(preds), _p(sample), _p(noise), _p(out), _p(starts), _p(weights), nW, outer, F, L, inner,
+                              *(float(v) for v in coefs[1:]), int(mode), _dt(sample), _stream(), _p(coef_dev))
+    _check(rc, name)
+    return out
+
+
+def multistep_step(pred, sample, hist, mode, coefs, coef_dev=None):
+    """``cfg_multistep_step`` on one prediction; ``hist`` and ``coefs`` (the six of ``multistep_coefficients``) as there."""
+    _dev(pred, sample, hist)
+    assert pred.is_contiguous() and sample.is_contiguous() and pred.shape == sample.shape and pred.dtype == sample.dtype
+    _check_multistep("multistep_step", sample, hist, mode, coefs, coef_dev)
+    out = torch.empty(sample.shape, dtype=sample.dtype, device=sample.device)
+    rc = lib().im360_multistep_step(_p(pred), _p(sample), _p(hist), _p(out), sample.numel(), *(float(v) for v in coefs[1:]), int(mode),
+                                    _dt(sample), _stream(), _p(coef_dev))
+    _check(rc, "im360_multistep_step")
+    return out
+
+
+def multistep_step_windows(preds, sample, hist, starts, weights, mode, coefs, coef_dev=None, ring=False):
+    """``cfg_multistep_step_windows`` on the blend of the text halves alone: ``preds`` [nW, 1, *sample.shape with F -> L]."""
+    _dev(preds, sample, hist, starts, weights)
+    nW, outer, F, L, inner = _windows_geometry(preds, sample, starts, weights, halves=1)
+    _check_multistep("multistep_step_windows", sample, hist, mode, coefs, coef_dev)
+    out = torch.empty(sample.shape, dtype=sample.dtype, device=sample.device)
+    rc = lib().im360_multistep_step_windows(_p(preds), _p(sample), _p(hist), _p(out), _p(starts), _p(weights), nW, outer, F, L, inner,
+                                            F if ring else 0, *(float(v) for v in coefs[1:]), int(mode), _dt(sample), _stream(),
+                                            _p(coef_dev))
+    _check(rc, "im360_multistep_step_windows")
     return out
 
 

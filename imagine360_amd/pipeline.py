@@ -34,6 +34,9 @@ surface, rebuilt for the MI355X:
     noised back to the first timestep with an EFFECTIVE noise that keeps the low spatio-temporal frequencies of the noised clip and takes
     the high ones from a fresh draw (``kernels.free_init_noise``: three launches, each axis filtered with its own boundary -- longitude
     periodic, latitude mirrored, frames periodic only on a looping clip); the captured step graph is replayed across the passes.
+  * a guidance interval (``guidance_interval=(lo, hi)``, arXiv 2404.07724): the steps whose timestep lies outside the interval run the
+    model on the text half alone -- batch 1 instead of the CFG batch of two -- and the unguided form of the same step kernel
+    (``scheduler.fused_step``); a graphed run replays one of two captured graphs per step.
 
 CLIP text encoding and SAM feature extraction are outside the hot path: the
 pipeline uses ``text_encoder``/``tokenizer``/``image_encoder`` when given, and also accepts precomputed
@@ -363,7 +366,8 @@ class AnimationPipeline:
                  ip_plus_condition="image", prompt_embeds=None, sam_features=None, trace=None, frame_shard=None,
                  context_frames=None, context_overlap=4, context_weights="pyramid", guidance_rescale=0.0, context_loop=False,
                  init_latents=None, init_video=None, strength=1.0, regenerate_mask=None, init_resize="bicubic", init_retime=None,
-                 free_init_iters=1, free_init_d_s=0.25, free_init_d_t=0.25, regenerate_mode="blend", regenerate_feather=0.0, **kwargs):
+                 free_init_iters=1, free_init_d_s=0.25, free_init_d_t=0.25, regenerate_mode="blend", regenerate_feather=0.0,
+                 guidance_interval=None, **kwargs):
         """``frame_shard`` (imagine360_amd.dist.FrameShard): this rank denoises a contiguous chunk of the frames (BASELINE
         configs 4 / 5); all ranks must be called with the same seeds and inputs.  Noise is drawn for the whole clip and
         cut, the VAE encodes / the loop runs / the VAE decodes only the local frames, the motion modules exchange tokens
@@ -456,7 +460,26 @@ class AnimationPipeline:
         ``rng="host"`` work across passes.  ``pipe.free_init_passes``: the clean panorama latent of every pass (one clone each; with
         ``free_init_iters=1`` the one of ``last_latents``); only the last pass is decoded.  Refused (``ValueError``): ``init_latents`` /
         ``init_video`` / ``strength != 1`` / ``regenerate_mask`` (FreeInit re-noises its own result from pure noise), ``frame_shard``,
-        ``free_init_iters < 1``.  Whether the passes improve a clip can only be judged with trained weights."""
+        ``free_init_iters < 1``.  Whether the passes improve a clip can only be judged with trained weights.
+        ``guidance_interval`` (None: off, the call without the keyword bit for bit -- nothing new runs and no second graph is built;
+        ``(lo, hi)`` with ``0 <= lo <= hi <= 1``, fractions of ``num_train_timesteps``): "Applying Guidance in a Limited Interval" (arXiv
+        2404.07724; ComfyUI's timestep ranges, A1111's CFG interval).  The step at timestep t is GUIDED iff ``lo T <= t < hi T``
+        (``scheduler.guided_steps``, the one definition); guidance hurts at high noise levels and is superfluous at low ones, and with
+        the shipped zero-terminal-SNR betas at guidance 7.5 that is a quality control of its own.  On an UNGUIDED step the model is
+        evaluated on the text half alone (rows [1:2] / [m:2m] of every CFG-batched input; batch 1 instead of 2) and each branch's latent
+        is updated by the unguided form of the step kernel the run uses (``scheduler.fused_step`` / ``fused_step_windows``: one prediction
+        stream, no guidance read).  RNG: the IP-adapter noise is drawn for the whole CFG batch and cut (``mv._ip_noise_half``, restored
+        also when the loop raises), the WarpAttn coins and the ``eta`` variance noise are drawn as on a guided step -- every stream
+        stands after the call where it stands after the call without the keyword.  ``guidance_rescale`` is SKIPPED on an unguided step
+        (no statistics launch, no factor): the rescale of a prediction towards its own standard deviation is the identity.  Everything
+        behind the step is unchanged: ``regenerate_mask``, ``trace`` / ``callback``, the multistep x0 history (its six coefficients do not
+        depend on guidance), FreeInit's passes (every pass uses the same flags).  ``lo == hi`` guides no step: a conditional-only
+        sampler.  An interval that covers every timestep of the run takes the path of ``None``.  Every loop variant (eager, graph replay,
+        context windows on a line and on a ring, ``eta``, ``init_latents`` / ``strength``, DPM-Solver++ 2M, ``free_init_iters``); a graphed run
+        with both kinds of step owns two captured graphs over the same static buffers and ``step`` replays the one the flags select.
+        The IP tokens of both forms of the SAM features are cached side by side for the run (``context.ip_cache_slots``) and dropped on
+        exit.  Malformed intervals and ``frame_shard`` raise ``ValueError``.  What the interval does to a clip's quality can only be
+        judged with trained weights."""
         device = self.device
         vb = video_batch
         plan = None
@@ -468,6 +491,11 @@ class AnimationPipeline:
             if frame_shard is not None:
                 raise ValueError(f"frame_shard cannot be combined with {type(self.scheduler).__name__} (the cut of the x0 history to a rank's "
                                  "frames is not implemented): use DDIMScheduler")
+        if guidance_interval is not None:
+            self.scheduler.guided_steps((), guidance_interval)            # (ValueError for a malformed interval, before any work)
+            if frame_shard is not None:
+                raise ValueError("guidance_interval cannot be combined with frame_shard (the text-half step of a frame-sharded model and "
+                                 "its second captured graph are not implemented)")
         if guidance_rescale != 0.0 and frame_shard is not None:
             raise ValueError("guidance_rescale cannot be combined with frame_shard (the standard deviations span the frames of all "
                              "ranks and would need an all-reduce inside the step, which is not implemented)")
@@ -576,6 +604,10 @@ class AnimationPipeline:
             # a multistep scheduler: the run's timestep list fixes its coefficients, and each branch's latent owns its x0 history
             self.scheduler.begin_run(steps_host)
             hist = (self.scheduler.new_history(pano_latent), self.scheduler.new_history(pers_latent))
+        # (guidance_interval) the flags of the run's steps; None: every step is guided, the call without the keyword
+        guided = None if guidance_interval is None else self.scheduler.guided_steps(steps_host, guidance_interval)
+        if guided is not None and all(guided):
+            guided, guidance_interval = None, None
         sh = frame_shard
         if sh is not None:
             # every rank drew the whole clip's noise from the same seed: cut to the local frames
@@ -588,6 +620,7 @@ class AnimationPipeline:
         if sh is not None:
             pano_mask_l, pers_mask_l = sh.take(pano_mask_l, 2), sh.take(pers_mask_l, 3)
             self.mv_base_model.set_frame_shard(sh)
+        ip_slots = None
         try:
             if prompt_embeds is not None:
                 text_pano, text_pers = prompt_embeds
@@ -619,8 +652,20 @@ class AnimationPipeline:
                               reference_images_clip_feat_pers=feat_pers, relative_position_tensor=rel, pitchs_tensor=pitch)
                 pano_latent, pers_latent = self._windowed_loop(plan, inputs, cameras, pano_latent, pers_latent, steps_host, ts_dev,
                                                                guidance_scale_text, use_fps_condition, eta, generator, trace,
-                                                               callback, callback_steps, guidance_rescale, region, hist, next_pass)
+                                                               callback, callback_steps, guidance_rescale, region, hist, next_pass,
+                                                               **({} if guided is None else dict(guidance_interval=guidance_interval)))
             graphed = None
+            if guided is not None and plan is None:
+                # the text-half views of the model inputs, made once and kept (the IP-token cache keys on the feature tensors' identity),
+                # and room in that cache for both forms of the SAM features; closed in the `finally` below
+                from .context import ip_cache_slots
+                from .dist import cfg_half_inputs
+                text_half = cfg_half_inputs(dict(latents=in_pers, pano_latent=in_pano, prompt_embd=text_pers, pano_prompt_embd=text_pano,
+                                                 fps_tensor_pano=fps_pano, fps_tensor_pers=fps_pers, reference_images_clip_feat_pano=feat_pano,
+                                                 reference_images_clip_feat_pers=feat_pers, relative_position_tensor=rel,
+                                                 pitchs_tensor=pitch), 1)
+                ip_slots = ip_cache_slots(self.mv_base_model, 2)
+                ip_slots.__enter__()
             import torch.distributed as tdist
             capturable = sh is None or (tdist.is_initialized() and tdist.get_backend(sh.group) == "nccl")     # RCCL all-to-alls are stream ops
             if (plan is None and self.use_graph and self.rng == "device" and pano_latent.is_cuda and trace is None and callback is None
@@ -632,6 +677,8 @@ class AnimationPipeline:
                 stoch = dict(eta=eta, generator=generator, frame_shard=sh) if eta > 0 else {}
                 if region is not None:
                     stoch["keep"] = region
+                if guided is not None:
+                    stoch.update(guidance_interval=guidance_interval, steps=steps_host)
                 graphed = GraphedDenoiseStep(self.mv_base_model, self.scheduler, inputs, cameras, pano_latent, pers_latent,
                                              guidance_scale_text, use_fps=use_fps_condition, warmup=1, guidance_rescale=guidance_rescale, **stoch)       # one eager step fills every cache
             while plan is None:                 # one round per pass: once without free_init_iters
@@ -639,18 +686,22 @@ class AnimationPipeline:
                     if graphed is not None:
                         pano_latent, pers_latent = graphed.step(t)
                         continue
-                    in_pano[:, :4] = pano_latent
-                    in_pers[:, :, :4] = pers_latent
-                    pred_pers, pred_pano = self.mv_base_model(
-                        latents=in_pers, pano_latent=in_pano, timestep=ts_dev[i], prompt_embd=text_pers,
-                        pano_prompt_embd=text_pano, cameras=cameras, use_fps_condition=use_fps_condition,
-                        use_ip_plus_cross_attention=use_ip_plus_cross_attention, fps_tensor_pano=fps_pano, fps_tensor_pers=fps_pers,
-                        reference_images_clip_feat_pano=feat_pano, reference_images_clip_feat_pers=feat_pers,
-                        relative_position_tensor=rel, pitchs_tensor=pitch)
-                    pano_latent = self._cfg_step(pred_pano, guidance_scale_text, t, pano_latent, eta, generator, sh, 2, guidance_rescale,
-                                                 **({} if hist is None else dict(history=hist[0])))
-                    pers_latent = self._cfg_step(pred_pers, guidance_scale_text, t, pers_latent, eta, generator, sh, 3, guidance_rescale,
-                                                 **({} if hist is None else dict(history=hist[1])))
+                    if guided is not None and not guided[i]:
+                        pano_latent, pers_latent = self._unguided_step(text_half, pano_latent, pers_latent, ts_dev[i], t, cameras,
+                                                                       use_fps_condition, eta, generator, guidance_rescale, hist)
+                    else:
+                        in_pano[:, :4] = pano_latent
+                        in_pers[:, :, :4] = pers_latent
+                        pred_pers, pred_pano = self.mv_base_model(
+                            latents=in_pers, pano_latent=in_pano, timestep=ts_dev[i], prompt_embd=text_pers,
+                            pano_prompt_embd=text_pano, cameras=cameras, use_fps_condition=use_fps_condition,
+                            use_ip_plus_cross_attention=use_ip_plus_cross_attention, fps_tensor_pano=fps_pano, fps_tensor_pers=fps_pers,
+                            reference_images_clip_feat_pano=feat_pano, reference_images_clip_feat_pers=feat_pers,
+                            relative_position_tensor=rel, pitchs_tensor=pitch)
+                        pano_latent = self._cfg_step(pred_pano, guidance_scale_text, t, pano_latent, eta, generator, sh, 2, guidance_rescale,
+                                                     **({} if hist is None else dict(history=hist[0])))
+                        pers_latent = self._cfg_step(pred_pers, guidance_scale_text, t, pers_latent, eta, generator, sh, 3, guidance_rescale,
+                                                     **({} if hist is None else dict(history=hist[1])))
                     if region is not None:
                         region.apply(pano_latent, pers_latent, i)
                     if trace is not None:
@@ -681,6 +732,8 @@ class AnimationPipeline:
         finally:
             if sh is not None:
                 self.mv_base_model.set_frame_shard(None)      # also when the loop raises: the model must not stay sharded
+            if ip_slots is not None:
+                ip_slots.__exit__(None, None, None)           # (guidance_interval) back to the single-entry IP-token cache
 
     def _cfg_step(self, pred, g, t, latent, eta=0.0, generator=None, shard=None, frame_dim=2, guidance_rescale=0.0, **history):
         """``history`` (``history=``, a multistep scheduler only): the x0 history of this latent, handed on to the scheduler."""
@@ -690,23 +743,76 @@ class AnimationPipeline:
             return self.scheduler.fused_cfg_step(u, c, g, t, latent, eta=eta, noise=z, guidance_rescale=guidance_rescale)
         return self.scheduler.fused_cfg_step(u, c, g, t, latent, guidance_rescale=guidance_rescale, **history)
 
+    def _text_half_step(self, forward, step, pano_latent, pers_latent, eta, generator, hist, model_dtype=None):
+        """One unguided step (``guidance_interval``): ``forward()`` runs the model on the text half with ``mv._ip_noise_half = (1, 2)`` --
+        the IP-adapter noise is drawn for the whole CFG batch and cut, so the stream advances as on a guided step -- restored also when
+        it raises; then ``step(prediction, latent, noise, frame_dim, history)`` per branch, panorama first, the variance noise drawn
+        where a guided step draws it (in the dtype it draws it in: ``model_dtype``, default the prediction's)."""
+        mv = self.mv_base_model
+        was = mv._ip_noise_half
+        mv._ip_noise_half = (1, 2)
+        try:
+            pred_pers, pred_pano = forward()
+        finally:
+            mv._ip_noise_half = was
+        mdt = pred_pano.dtype if model_dtype is None else model_dtype
+        out = []
+        for branch, (pred, latent, frame_dim) in enumerate(((pred_pano, pano_latent, 2), (pred_pers, pers_latent, 3))):
+            z = variance_noise(self.scheduler, latent, mdt, generator, self.rng, None, frame_dim) if eta > 0 else None
+            out.append(step(pred, latent, z, {} if hist is None else dict(history=hist[branch])))
+        return out
+
+    def _unguided_step(self, text_half, pano_latent, pers_latent, t_dev, t, cameras, use_fps, eta, generator, guidance_rescale, hist):
+        """The one-block loop's unguided step: the model on ``text_half`` (``dist.cfg_half_inputs(inputs, 1)``, made once per run), then
+        ``scheduler.fused_step`` per branch."""
+        def forward():
+            text_half["pano_latent"][:, :4] = pano_latent
+            text_half["latents"][:, :, :4] = pers_latent
+            return self.mv_base_model(timestep=t_dev, cameras=cameras, use_fps_condition=use_fps, use_ip_plus_cross_attention=True, **text_half)
+
+        def step(pred, latent, z, history):
+            return self.scheduler.fused_step(pred.to(latent.dtype), t, latent, **(dict(eta=eta, noise=z) if eta > 0 else {}),
+                                             guidance_rescale=guidance_rescale, **history)
+        return self._text_half_step(forward, step, pano_latent, pers_latent, eta, generator, hist)
+
+    def _unguided_windows_step(self, plan, text_half, text_static, text_preds, pano_latent, pers_latent, t_dev, t, cameras, use_fps, eta,
+                               generator, guidance_rescale, hist):
+        """The windowed loop's unguided step: every window on its text half (``text_half`` / ``text_static``: views made once per run)
+        into the [nW, 1, ...] buffers ``text_preds`` (perspective, panorama), then ``scheduler.fused_step_windows`` per branch."""
+        mv, sch = self.mv_base_model, self.scheduler
+
+        def forward():
+            text_half["pano_latent"][:, :4] = pano_latent
+            text_half["latents"][:, :, :4] = pers_latent
+            plan.forward(mv, text_half, text_static, cameras, t_dev, use_fps, *text_preds)
+            return text_preds
+
+        def step(preds, latent, z, history):
+            return sch.fused_step_windows(preds, plan.starts_dev, plan.weights, t, latent, noise=z, eta=eta,
+                                          guidance_rescale=guidance_rescale, ring=plan.loop, **history)
+        return self._text_half_step(forward, step, pano_latent, pers_latent, eta, generator, hist, model_dtype=mv.unet.dtype)
+
     def _windowed_loop(self, plan, inputs, cameras, pano_latent, pers_latent, steps_host, ts_dev, g, use_fps, eta, generator,
-                       trace, callback, callback_steps, guidance_rescale=0.0, keep=None, hist=None, next_pass=None):
+                       trace, callback, callback_steps, guidance_rescale=0.0, keep=None, hist=None, next_pass=None, guidance_interval=None):
         """The denoising loop over sliding temporal context windows: per step one forward per window (slot order), then ONE
         blend + CFG + DDIM kernel per branch, panorama first.  RNG: as len(plan) successive calls of the model, then (eta > 0)
         the whole clip's panorama and perspective variance noise.  Captured in one hipGraph under the conditions of the
         one-block loop (graph_step.GraphedWindowedStep), issued eagerly otherwise.  ``keep`` (KeepRegion): its blend of the whole
         clip after the two windows kernels of every step.  ``hist``: the (panorama, perspective) x0 histories of a multistep scheduler for the
         eager loop (the graphed step owns its own).  ``next_pass`` (FreeInit): called with the two latents behind the last step; None ends the
-        loop, else it returns the start latents of another run of the whole schedule (the captured step is restarted, not captured again)."""
+        loop, else it returns the start latents of another run of the whole schedule (the captured step is restarted, not captured again).
+        ``guidance_interval`` (None: every step guided): the unguided steps run every window on its text half (views made once, [nW, 1, ...]
+        prediction buffers, ``scheduler.fused_step_windows``), and the IP-token cache holds both forms of every window's features."""
         from .context import ip_cache_slots
         mv, sch = self.mv_base_model, self.scheduler
-        with ip_cache_slots(mv, len(plan)):
+        guided = None if guidance_interval is None else sch.guided_steps(steps_host, guidance_interval)
+        with ip_cache_slots(mv, len(plan) * (1 if guided is None else 2)):
             if self.use_graph and self.rng == "device" and pano_latent.is_cuda and trace is None and callback is None:
                 from .graph_step import GraphedWindowedStep
                 graphed = GraphedWindowedStep(mv, sch, inputs, cameras, pano_latent, pers_latent, g, plan, use_fps=use_fps, warmup=1,
                                               eta=eta, generator=generator, guidance_rescale=guidance_rescale,
-                                              **({} if keep is None else dict(keep=keep)))
+                                              **({} if keep is None else dict(keep=keep)),
+                                              **({} if guided is None else dict(guidance_interval=guidance_interval, steps=steps_host)))
                 while True:
                     for t in self.progress_bar(steps_host):
                         pano_latent, pers_latent = graphed.step(t)
@@ -716,19 +822,28 @@ class AnimationPipeline:
                     graphed.restart(*start)
             static = plan.static_inputs(inputs)
             preds_pers, preds_pano = plan.pred_buffers(pano_latent, pers_latent)
+            if guided is not None:
+                from .dist import cfg_half_inputs
+                text_half, text_static = cfg_half_inputs(inputs, 1), plan.text_half(static)
+                text_preds = plan.pred_buffers(pano_latent, pers_latent, halves=1)           # (perspective, panorama)
             while True:
                 for i, t in enumerate(self.progress_bar(steps_host)):
-                    inputs["pano_latent"][:, :4] = pano_latent
-                    inputs["latents"][:, :, :4] = pers_latent
-                    plan.forward(mv, inputs, static, cameras, ts_dev[i], use_fps, preds_pers, preds_pano)
-                    mdt = mv.unet.dtype
-                    kw = dict(eta=eta, guidance_rescale=guidance_rescale, ring=plan.loop)
-                    z = variance_noise(sch, pano_latent, mdt, generator, self.rng) if eta > 0 else None
-                    pano_latent = sch.fused_cfg_step_windows(preds_pano, plan.starts_dev, plan.weights, g, t, pano_latent, noise=z, **kw,
-                                                             **({} if hist is None else dict(history=hist[0])))
-                    z = variance_noise(sch, pers_latent, mdt, generator, self.rng, frame_dim=3) if eta > 0 else None
-                    pers_latent = sch.fused_cfg_step_windows(preds_pers, plan.starts_dev, plan.weights, g, t, pers_latent, noise=z, **kw,
-                                                             **({} if hist is None else dict(history=hist[1])))
+                    if guided is not None and not guided[i]:
+                        pano_latent, pers_latent = self._unguided_windows_step(plan, text_half, text_static, text_preds, pano_latent,
+                                                                               pers_latent, ts_dev[i], t, cameras, use_fps, eta, generator,
+                                                                               guidance_rescale, hist)
+                    else:
+                        inputs["pano_latent"][:, :4] = pano_latent
+                        inputs["latents"][:, :, :4] = pers_latent
+                        plan.forward(mv, inputs, static, cameras, ts_dev[i], use_fps, preds_pers, preds_pano)
+                        mdt = mv.unet.dtype
+                        kw = dict(eta=eta, guidance_rescale=guidance_rescale, ring=plan.loop)
+                        z = variance_noise(sch, pano_latent, mdt, generator, self.rng) if eta > 0 else None
+                        pano_latent = sch.fused_cfg_step_windows(preds_pano, plan.starts_dev, plan.weights, g, t, pano_latent, noise=z, **kw,
+                                                                 **({} if hist is None else dict(history=hist[0])))
+                        z = variance_noise(sch, pers_latent, mdt, generator, self.rng, frame_dim=3) if eta > 0 else None
+                        pers_latent = sch.fused_cfg_step_windows(preds_pers, plan.starts_dev, plan.weights, g, t, pers_latent, noise=z, **kw,
+                                                                 **({} if hist is None else dict(history=hist[1])))
                     if keep is not None:
                         keep.apply(pano_latent, pers_latent, i)
                     if trace is not None:

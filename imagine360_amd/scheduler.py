@@ -210,6 +210,23 @@ class DDIMScheduler:
                              f"raise one of them")
         return n - k, self._timesteps_host[n - k:]
 
+    def guided_steps(self, steps, interval):
+        """Which steps of the run's timestep list ``steps`` are guided under ``interval = (lo, hi)`` ("Applying Guidance in a Limited
+        Interval", arXiv 2404.07724; pipeline ``guidance_interval``): the step at timestep t is guided iff
+        ``lo * num_train_timesteps <= t < hi * num_train_timesteps``.  A list of bools, one per step; ``None``: every step.  ``lo`` and
+        ``hi`` are fractions with ``0 <= lo <= hi <= 1``; ``lo == hi`` guides no step (a conditional-only sampler).  Anything else
+        raises ``ValueError``.  The one definition: the eager loops, the graphed steps and the multistep scheduler all ask here."""
+        if interval is None:
+            return [True] * len(steps)
+        try:
+            lo, hi = (float(v) for v in interval)
+        except (TypeError, ValueError):
+            raise ValueError(f"guidance_interval must be None or a pair (lo, hi) of fractions of num_train_timesteps, got {interval!r}") from None
+        if not 0.0 <= lo <= hi <= 1.0:            # (a NaN fails every comparison)
+            raise ValueError(f"guidance_interval must satisfy 0 <= lo <= hi <= 1, got {interval!r}")
+        T = self.config.num_train_timesteps
+        return [lo * T <= int(t) < hi * T for t in steps]
+
     def _noise_factors(self, like, timesteps):
         """sqrt(a_t) and sqrt(1 - a_t) of ``timesteps`` in ``like``'s dtype on its device, shaped to broadcast from the left over
         ``like``.  Works on a cast COPY of ``alphas_cumprod``: the table itself stays fp32 on the host, where ``_alphas`` reads it
@@ -311,6 +328,35 @@ class DDIMScheduler:
         return kernels.cfg_ddim_step_windows(preds.contiguous(), x, noise.to(x.dtype).contiguous() if eta > 0 else None, starts,
                                              weights, self.kernel_mode(use_clipped_model_output), coefs, coef_dev=coef_dev, **_rescale_kw(guidance_rescale),
                                              **_ring_kw(ring))
+
+
+    def fused_step(self, pred, timestep, sample, coef_dev=None, *, eta=0.0, noise=None, use_clipped_model_output=False, guidance_rescale=0.0):
+        """``fused_cfg_step`` for an UNGUIDED step (``guided_steps``): the model ran the text half alone and ``pred`` is its one
+        prediction.  The same kernels in their unguided form (``kernels.ddim_update`` / ``kernels.ddim_step``: one prediction stream, no
+        guidance read), the same choice between them, the same coefficient vectors -- ``coef_dev`` is the buffer the guided step reads.
+        ``guidance_rescale`` is SKIPPED -- no statistics launch, no factor: rescaling a prediction towards its own standard deviation is
+        the identity; the keyword only selects the six-coefficient kernel as it does for the guided steps of the run, so that both forms
+        read one coefficient vector."""
+        p, x = pred.contiguous(), sample.contiguous()
+        if not self.uses_step_kernel(eta, use_clipped_model_output, guidance_rescale):
+            cx, cv = (0.0, 0.0) if coef_dev is not None else self.coefficients(timestep)
+            return kernels.ddim_update(p, x, cx, cv, coef_dev=coef_dev)
+        if eta > 0 and noise is None:
+            raise ValueError("fused_step: eta > 0 needs the variance noise")
+        coefs = (0.0,) * 6 if coef_dev is not None else self.step_coefficients(timestep, eta)
+        return kernels.ddim_step(p, x, noise.to(x.dtype).contiguous() if eta > 0 else None, self.kernel_mode(use_clipped_model_output), coefs,
+                                 coef_dev=coef_dev)
+
+    def fused_step_windows(self, preds, starts, weights, timestep, sample, coef_dev=None, *, eta=0.0, noise=None,
+                           use_clipped_model_output=False, guidance_rescale=0.0, ring=False):
+        """``fused_cfg_step_windows`` for an unguided step: ``preds`` [nW, 1, ...], the windows' text halves alone
+        (``kernels.ddim_step_windows``); everything else as there, ``guidance_rescale`` skipped as in ``fused_step``."""
+        if eta > 0 and noise is None:
+            raise ValueError("fused_step_windows: eta > 0 needs the variance noise")
+        x = sample.contiguous()
+        coefs = (0.0,) * 6 if coef_dev is not None else self.step_coefficients(timestep, eta)
+        return kernels.ddim_step_windows(preds.contiguous(), x, noise.to(x.dtype).contiguous() if eta > 0 else None, starts, weights,
+                                         self.kernel_mode(use_clipped_model_output), coefs, coef_dev=coef_dev, **_ring_kw(ring))
 
 
 class DPMSolverMultistepScheduler(DDIMScheduler):
@@ -465,3 +511,16 @@ class DPMSolverMultistepScheduler(DDIMScheduler):
         coefs = self._kernel_args("fused_cfg_step_windows", timestep, guidance_scale, coef_dev, history, eta, noise, kwargs)
         return kernels.cfg_multistep_step_windows(preds.contiguous(), sample.contiguous(), history, starts, weights, self.kernel_mode(), coefs,
                                                   coef_dev=coef_dev, **_rescale_kw(guidance_rescale), **_ring_kw(ring))
+
+    def fused_step(self, pred, timestep, sample, coef_dev=None, *, history=None, eta=0.0, noise=None, guidance_rescale=0.0, **kwargs):
+        """``fused_cfg_step`` for an unguided step (``DDIMScheduler.fused_step``): the multistep update on the one prediction
+        (``kernels.multistep_step``); ``history`` is written and read as on a guided step -- the six coefficients do not depend on guidance."""
+        coefs = self._kernel_args("fused_step", timestep, 1.0, coef_dev, history, eta, noise, kwargs)
+        return kernels.multistep_step(pred.contiguous(), sample.contiguous(), history, self.kernel_mode(), coefs, coef_dev=coef_dev)
+
+    def fused_step_windows(self, preds, starts, weights, timestep, sample, coef_dev=None, *, history=None, eta=0.0, noise=None,
+                           guidance_rescale=0.0, ring=False, **kwargs):
+        """``fused_cfg_step_windows`` for an unguided step: ``preds`` [nW, 1, ...] (``kernels.multistep_step_windows``)."""
+        coefs = self._kernel_args("fused_step_windows", timestep, 1.0, coef_dev, history, eta, noise, kwargs)
+        return kernels.multistep_step_windows(preds.contiguous(), sample.contiguous(), history, starts, weights, self.kernel_mode(), coefs,
+                                              coef_dev=coef_dev, **_ring_kw(ring))

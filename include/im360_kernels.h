@@ -373,6 +373,49 @@ int im360_cfg_multistep_step_windows(const void* pred, const void* x, void* hist
                                      float sqrt_a, float sqrt_b, float cx, float c0, float c1, int mode, float phi, const void* ws,
                                      int64_t ws_floats, int dtype, void* stream, const void* coef_dev);
 
+/* ---- the unguided forms of the step entry points above: a step outside the guidance interval ("Applying Guidance in a Limited
+ * Interval", arXiv 2404.07724; AnimationPipeline guidance_interval), where the model was run on the text half alone.  pred is that
+ * one prediction and stands where m = uncond + guidance * (cond - uncond) stands in the sibling; everything behind m -- prediction
+ * type, clamp, update, history, lanes, the scalar windows path, the checks and their error codes -- is the sibling's.  There is no
+ * guidance argument and no second 16-byte load stream.  coef_dev (optional) is the SIBLING's vector, so a captured guided and a
+ * captured unguided step share one uploaded buffer; its element 0 (the guidance) is not read.  For windows pred is
+ * [nW, 1, outer, L, inner]: the text halves alone, nothing is read behind them.
+ * Defining property: for finite inputs each entry point returns, bit for bit, what its sibling returns when uncond and cond are the
+ * same tensor (both halves of every window equal), for any guidance: u + g (c - u) with c == u is u up to the sign of a zero.
+ * There are no _rescale forms: the guidance rescale of a prediction towards its own standard deviation is the identity.
+ * Replaces: nothing in the reference (its pipeline guides every step); DDIMScheduler.step of scheduling_ddim.py:251-373 /
+ *   algorithm 2 of arXiv 2211.01095 on a single model output. */
+
+/* out = cx * x + cv * pred: im360_cfg_ddim_update; coef_dev: float[3] = (guidance, cx, cv). */
+int im360_ddim_update(const void* pred, const void* x, void* out, int64_t n, float cx, float cv, int dtype, void* stream,
+                      const void* coef_dev);
+
+/* im360_cfg_ddim_step on pred; coef_dev: float[6] = (guidance, sqrt_a, sqrt_b, sqrt_a_prev, dir, sigma). */
+int im360_ddim_step(const void* pred, const void* x, const void* noise, void* out, int64_t n, float sqrt_a, float sqrt_b,
+                    float sqrt_a_prev, float dir, float sigma, int mode, int dtype, void* stream, const void* coef_dev);
+
+/* im360_cfg_ddim_step_windows on the blend of pred [nW, 1, outer, L, inner]. */
+int im360_ddim_step_windows(const void* pred, const void* x, const void* noise, void* out, const void* start, const void* weight,
+                            int nW, int64_t outer, int64_t F, int64_t L, int64_t inner, float sqrt_a, float sqrt_b,
+                            float sqrt_a_prev, float dir, float sigma, int mode, int dtype, void* stream, const void* coef_dev);
+
+/* im360_cfg_ddim_step_windows_ring on the blend of pred [nW, 1, outer, L, inner].
+ * Precondition: 0 <= start[k] < F, every frame covered, L <= F. */
+int im360_ddim_step_windows_ring(const void* pred, const void* x, const void* noise, void* out, const void* start,
+                                 const void* weight, int nW, int64_t outer, int64_t F, int64_t L, int64_t inner, float sqrt_a,
+                                 float sqrt_b, float sqrt_a_prev, float dir, float sigma, int mode, int dtype, void* stream,
+                                 const void* coef_dev);
+
+/* im360_cfg_multistep_step on pred (hist as there); coef_dev: float[6] = (guidance, sqrt_a, sqrt_b, cx, c0, c1). */
+int im360_multistep_step(const void* pred, const void* x, void* hist, void* out, int64_t n, float sqrt_a, float sqrt_b, float cx,
+                         float c0, float c1, int mode, int dtype, void* stream, const void* coef_dev);
+
+/* im360_cfg_multistep_step_windows on the blend of pred [nW, 1, outer, L, inner]; wrap = 0 (line) or F (ring). */
+int im360_multistep_step_windows(const void* pred, const void* x, void* hist, void* out, const void* start, const void* weight,
+                                 int nW, int64_t outer, int64_t F, int64_t L, int64_t inner, int64_t wrap, float sqrt_a,
+                                 float sqrt_b, float cx, float c0, float c1, int mode, int dtype, void* stream,
+                                 const void* coef_dev);
+
 /* ---- start latents of a run that begins from a given clip (AnimationPipeline init_latents / init_video, strength < 1), one launch:
  *   out_pano[c, f, p]    = T(sqrt_a * x0[c, f, p] + sqrt_b * noise[f, c, p])        fp32, one rounding, at the store
  *   out_pers[m, c, f, q] = ok[m, q] ? out_pano[c, f, idx[m, q]] : 0                 the gather of the ROUNDED panorama start, bit for bit

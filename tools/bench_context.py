@@ -109,15 +109,17 @@ def time_kernels(sch, plan, sample, iters, rounds=5, ring_plan=None):
     return {k: dict(us_min=min(v), us_median=statistics.median(v)) for k, v in times.items()}
 
 
-def time_steps(graphs, ts_host, steps, rounds):
-    """Host-clock ms per step of captured steps, replays alternated round by round; round 0 warms every graph up."""
+def time_steps(graphs, ts_host, steps, rounds, per_name=None):
+    """Host-clock ms per step of captured steps, replays alternated round by round; round 0 warms every graph up.  ``per_name``:
+    {name: its own timestep list} instead of ``ts_host`` (--guidance-interval: the timestep selects the graph)."""
     times = {k: [] for k in graphs}
     for r in range(rounds + 1):
         for name, gs in graphs.items():
+            ts = ts_host if per_name is None else per_name[name]
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for i in range(steps):
-                gs.step(ts_host[i % len(ts_host)])
+                gs.step(ts[i % len(ts)])
             torch.cuda.synchronize()
             if r:
                 times[name].append((time.perf_counter() - t0) / steps * 1e3)
@@ -485,6 +487,45 @@ def free_init_bench(args, sch, dev, dt):
     return res
 
 
+def interval_bench(args, sch, dev, dt, ts_host):
+    """--guidance-interval LO HI at cfg2 size (16 frames, 512 x 1024, bf16): one captured step object whose run of 25 steps holds both
+    kinds of step (two graphs over the same static buffers), next to one without the interval (one graph).  ms per guided and per
+    unguided step (replays of the two graphs interleaved round by round in this one process), ms per step of the 25-step run with and
+    without the interval, and the peak device memory behind one graph and behind two."""
+    from imagine360_amd.graph_step import GraphedDenoiseStep
+    frames = 16
+    interval = tuple(args.guidance_interval)
+    flags = sch.guided_steps(ts_host, interval)
+    assert True in flags and False in flags, f"--guidance-interval {interval}: the 25-step run must hold both kinds of step to compare them"
+    res = dict(tool="bench_context --guidance-interval", guidance_interval=list(interval), frames=frames, pano_hw=PANO_HW, pers_hw=PERS_HW,
+               dtype="bfloat16", device=torch.cuda.get_device_name(0), sampler=args.sampler, steps_of_25=dict(guided=sum(flags), unguided=len(flags) - sum(flags)))
+    mv = configs.build_mv_model(1, device=dev, dtype=dt, xformers=True)
+    mv.dual_stream, mv.warp_streams = True, True
+    inp = synthetic.mv_inputs(frames=frames, pano_hw=PANO_HW, pers_hw=PERS_HW, seed=1, dtype=dt, device=dev)
+    inp.pop("timestep")
+    cams = synthetic.icosahedron_cameras(90, PERS_PX, device=dev)
+    pano_lat, pers_lat = inp["pano_latent"][:1, :4].contiguous(), inp["latents"][:1, :, :4].contiguous()
+    mib = lambda: torch.cuda.max_memory_allocated() / 2 ** 20
+    torch.cuda.reset_peak_memory_stats()
+    one = GraphedDenoiseStep(mv, sch, inp, cams, pano_lat, pers_lat, 7.5, warmup=1)
+    torch.cuda.synchronize()
+    res["peak_mib_one_graph"] = mib()
+    with ip_cache_slots(mv, 2):
+        two = GraphedDenoiseStep(mv, sch, inp, cams, pano_lat, pers_lat, 7.5, warmup=1, guidance_interval=interval, steps=ts_host)
+        torch.cuda.synchronize()
+        res["peak_mib_two_graphs"] = mib()                  # (the one-graph object is still alive: the peak behind all three graphs)
+        assert len(two.graphs) == 2
+        t_guided, t_unguided = ts_host[flags.index(True)], ts_host[flags.index(False)]
+        kinds = dict(guided_step=[t_guided], unguided_step=[t_unguided])
+        res.update(time_steps({k: two for k in kinds}, None, args.steps, args.rounds, per_name=kinds))
+        res.update(time_steps(dict(run_without_interval=one, run_with_interval=two), ts_host, len(ts_host), args.rounds))
+        res["finite"] = bool(torch.isfinite(two.pano_lat.float()).all() and torch.isfinite(two.pers_lat.float()).all())
+    res["unguided_over_guided"] = res["unguided_step"]["ms_min"] / res["guided_step"]["ms_min"]
+    res["note"] = ("randomly initialised weights: what the interval does to a clip's quality can only be judged with trained weights; "
+                   "host-clock ms around replays that end in a device synchronise")
+    return res
+
+
 def hires_bench(args, sch, dev, dt):
     """--init-scale N: the two-pass run (1 / N of the size from pure noise, then the full size from its latent at --strength) next to one
     run from pure noise at the full size; whole pipeline calls (encode, loop, decode), host clock around a call that ends in a device
@@ -645,6 +686,8 @@ def main():
                     help="with --strength: the frame-interpolation pass -- a first call with this many frames, a second call with --frames frames from its latent -- next to one call from pure noise with --frames frames")
     ap.add_argument("--free-init", type=int, default=None,
                     help="FreeInit: pipeline calls with free_init_iters = N next to the plain call (--frames, --num-steps, --loop), and the filter kernel against its eager definition")
+    ap.add_argument("--guidance-interval", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                    help="guided and unguided captured steps of one 25-step run at cfg2 size, interleaved (--steps replays per round, --rounds)")
     ap.add_argument("--pano-hw", type=int, nargs=2, default=[128, 256], metavar=("H", "W"), help="--init-scale: latent size of the full-size run (default: cfg5)")
     ap.add_argument("--sampler", choices=["ddim", "dpmpp2m"], default="ddim", help="the scheduler of every step and call (dpmpp2m: DPM-Solver++ 2M)")
     ap.add_argument("--out", default=None)
@@ -656,6 +699,8 @@ def main():
     sch = (DPMSolverMultistepScheduler if args.sampler == "dpmpp2m" else DDIMScheduler)(**configs.NOISE_SCHEDULER_KWARGS)
     sch.set_timesteps(25)
     ts_host = [int(t) for t in sch._timesteps_host]
+    if args.guidance_interval is not None:
+        return emit(interval_bench(args, sch, dev, dt, ts_host), args.out)
     if args.free_init is not None:
         assert args.strength is None and args.init_scale is None and args.init_frames is None, "--free-init N goes alone (FreeInit starts from pure noise)"
         return emit(free_init_bench(args, sch, dev, dt), args.out)

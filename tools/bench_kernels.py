@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Per-kernel micro-benchmarks at BASELINE cfg2 shapes (run on the MI355X):
 
-    python tools/bench_kernels.py [attn] [conv] [temporal] [ln] [gn] [sampler_step] [free_init_noise] [keep_release] [sphere_distance2] [--iters N]
+    python tools/bench_kernels.py [attn] [conv] [temporal] [ln] [gn] [sampler_step] [unguided_step] [free_init_noise] [keep_release] [sphere_distance2] [--iters N]
 
 Prints achieved TFLOP/s (MFMA kernels, vs 2500 dense bf16) or GB/s (HBM kernels, vs 8000) per shape.
 Usable under `rocprofv3 --pmc ...` for counters of one kernel class.
@@ -473,6 +473,34 @@ def bench_sampler_step(iters):
             base = base or ts[0]
             print(f"sampler_step {name} {n:8d} elements  {label:28s}: {ts[0] * 1e6:7.2f} us min {ts[2] * 1e6:7.2f} us median  "
                   f"{by / 1e6:6.2f} MB  {by / ts[0] / 1e9:6.0f} GB/s  {ts[0] / base:4.2f}x cfg_ddim_step")
+
+
+def bench_unguided_step(iters):
+    """The unguided step launches (pipeline ``guidance_interval``: one prediction, no combine) against their guided siblings on the same
+    tensors -- the two latents of cfg2 -- device events, with the bytes each launch has to move: one 16-bit load stream fewer."""
+    from imagine360_amd import configs
+    from imagine360_amd.scheduler import DDIMScheduler, DPMSolverMultistepScheduler
+    ddim, dpm = DDIMScheduler(**configs.NOISE_SCHEDULER_KWARGS), DPMSolverMultistepScheduler(**configs.NOISE_SCHEDULER_KWARGS)
+    ddim.set_timesteps(25), dpm.set_timesteps(25)
+    t = ddim._timesteps_host[8]
+    for name, shape in (("pano", (1, 4, 16, 64, 128)), ("pers", (1, 20, 4, 16, 32, 32))):
+        c, x = rn(*shape), rn(*shape)
+        h = torch.zeros(shape, dtype=torch.float32, device=DEV)
+        n = x.numel()
+        mode = ddim.kernel_mode()
+        cx, cv = ddim.coefficients(t)
+        cd, c2 = ddim.step_coefficients(t, 0.0, 7.5), dpm.multistep_coefficients(dpm._timesteps_host, 8, 7.5)
+        pairs = [("ddim_update", lambda: K.ddim_update(c, x, cx, cv), 6 * n, lambda: K.cfg_ddim_update(c, c, x, 7.5, cx, cv), 8 * n),
+                 ("ddim_step", lambda: K.ddim_step(c, x, None, mode, cd), 6 * n, lambda: K.cfg_ddim_step(c, c, x, None, mode, cd), 8 * n),
+                 ("multistep_step order 2", lambda: K.multistep_step(c, x, h, mode, c2), 14 * n, lambda: K.cfg_multistep_step(c, c, x, h, mode, c2), 16 * n)]
+        for label, fn, by, sib, sib_by in pairs:
+            tu, tg = [], []
+            for _ in range(5):                      # alternated
+                tu.append(timeit(fn, iters))
+                tg.append(timeit(sib, iters))
+            tu, tg = sorted(tu), sorted(tg)
+            print(f"unguided_step {name} {n:8d} elements  {label:24s}: {tu[0] * 1e6:7.2f} us min {tu[2] * 1e6:7.2f} us median {by / 1e6:6.2f} MB"
+                  f"  | cfg_ sibling {tg[0] * 1e6:7.2f} us min {tg[2] * 1e6:7.2f} us median {sib_by / 1e6:6.2f} MB  | {tu[0] / tg[0]:4.2f}x")
 
 
 def bench_free_init_noise(iters):
