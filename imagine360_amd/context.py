@@ -71,6 +71,43 @@ def coverage(frames, length, starts, loop=False):
     return cov
 
 
+def windowed_temporal_attention(qkv, pe_qkv, B, F, P, heads, starts, weights, ring=False):
+    """Eager definition of window-fused temporal attention (``context_level="attention"``; FreeNoise's window-based attention fusion,
+    arXiv 2310.15169 section 3.2) -- what ``kernels.temporal_attention_windows`` computes in one launch.
+    qkv [B*F*P, 3*C] in the activation dtype T, rows (batch, frame, pixel): the fused projection of LayerNorm(x) WITHOUT the frame PE;
+    pe_qkv [L, 3*C] in T: PE rows 0 .. L-1 through the same projection; ``starts`` [nW] ints, ``weights`` [L].  Window k holds the
+    frames f = starts[k] + p (modulo F on a ``ring``) at positions p = 0 .. L-1:
+      rows       r[k, p] = round_T(float(qkv[f]) + float(pe_qkv[p]))       -- the position restarts in every window: PE[p], never PE[f]
+      attention  o[k, p] = softmax(scale q k^T) v over the window's L rows, per (batch, pixel, head)
+      fusion     out[f]  = sum over the windows holding f of w[p] / (sum of their w[p']) * o[k, p], rounded to T once.
+    The arithmetic runs in float32 for 16-bit inputs and in the inputs' own dtype otherwise (float64 in: the reference of the tests).
+    Returns [B*F*P, C] in qkv's dtype."""
+    starts = [int(s) for s in (starts.tolist() if torch.is_tensor(starts) else starts)]
+    T = qkv.dtype
+    wide = torch.float32 if T in (torch.bfloat16, torch.float16) else T
+    C = qkv.shape[1] // 3
+    L, d = pe_qkv.shape[0], C // heads
+    assert qkv.shape == (B * F * P, 3 * C) and pe_qkv.shape == (L, 3 * C) and len(weights) == L and len(starts) >= 1
+    w = torch.as_tensor(weights).to(device=qkv.device, dtype=wide)
+    x = qkv.reshape(B, F, P, 3 * C)
+    pos = torch.arange(L, device=qkv.device)
+    acc = torch.zeros(B, F, P, C, dtype=wide, device=qkv.device)
+    wsum = torch.zeros(F, dtype=wide, device=qkv.device)
+    for s in starts:
+        if not (0 <= s < F and L <= F and (ring or s + L <= F)):
+            raise ValueError(f"windowed_temporal_attention: window at {s} of {L} frames does not fit {F} frames (ring={bool(ring)})")
+        wsum.index_add_(0, (s + pos) % F, w)
+    if not bool((wsum > 0).all()):
+        raise ValueError(f"windowed_temporal_attention: frames {(wsum <= 0).nonzero().flatten().tolist()} lie in no window")
+    for s in starts:
+        f = (s + pos) % F
+        r =(x[:, f].to(wide) + pe_qkv.to(wide)[None, :, None, :]).to(T).to(wide)                 # [B, L, P, 3C]
+        q, k, v = (t.reshape(B, L, P, heads, d).permute(0, 2, 3, 1, 4) for t in r.split(C, dim=-1))        # [B, P, heads, L, d]
+        o = torch.softmax(q @ k.transpose(-1, -2) * d ** -0.5, dim=-1) @ v
+        acc.index_add_(1, f, o.permute(0, 3, 1, 2, 4).reshape(B, L, P, C) * (w / wsum[f])[None, :, None, None])
+    return acc.to(T).reshape(B * F * P, C)
+
+
 def keyframe_frames(f, F, loop=False):
     """The frames of a clip retimed from ``f`` to ``F`` frames (``pano_geometry.retime_pano_latent``) that ARE source frames (t == 0),
     ascending: the j with j (f - 1) divisible by max(F - 1, 1) on an open clip, with j f divisible by F on a ring (``loop``).  The

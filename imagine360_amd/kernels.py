@@ -24,6 +24,7 @@ _SIGNATURES = {
     "im360_attn_fwd": (_INT, [_PTR] * 5 + [_I64] * 15 + [_F32, _F32, _INT, _INT, _PTR, _PTR, _PTR, _PTR, _PTR, _I64]),
     "im360_attn_fwd2": (_INT, [_PTR] * 6 + [_I64] * 19 + [_F32, _F32, _F32, _INT, _PTR]),
     "im360_temporal_attn_fwd": (_INT, [_PTR] * 4 + [_I64] * 11 + [_F32, _INT, _PTR]),
+    "im360_temporal_attn_windows_fwd": (_INT, [_PTR] * 5 + [_I64] * 11 + [_PTR, _I64, _PTR, _I64, _INT, _F32, _INT, _PTR]),
     "im360_shard_pack": (_INT, [_PTR] * 2 + [_I64] * 6 + [_INT, _PTR]),
     "im360_gn_num_slabs": (_I64, [_I64] * 3),
     "im360_groupnorm_stats": (_INT, [_PTR] * 6 + [_I64] * 6 + [_F32, _INT, _PTR]),
@@ -290,6 +291,53 @@ def temporal_attention(qkv, B, F, P, heads, frame_major=False, out=None):
                                        float(d ** -0.5), _dt(qkv), _stream())
     _check(rc, "im360_temporal_attn_fwd")
     _count("temporal", 4.0 * B * P * heads * F * F * d, qkv.element_size() * 4 * B * F * P * C)
+    return out
+
+
+def _host_table(t, ctype):
+    """Host copy of a small plan table (``starts`` / ``weights``: a tensor on any device, or a sequence) as a ctypes array.  A tensor
+    keeps its copy on the tensor OBJECT (with the version it was taken at): the one device-to-host read happens on the first call --
+    the eager warm-up of a captured step -- and never inside a capture."""
+    if not torch.is_tensor(t):
+        vals = list(t)
+        return (ctype * len(vals))(*vals), len(vals)
+    hit = getattr(t, "_im360_host", None)
+    if hit is None or hit[0] != t._version:
+        vals = t.detach().reshape(-1).tolist()
+        hit = (t._version, (ctype * len(vals))(*vals), len(vals))
+        t._im360_host = hit
+    return hit[1], hit[2]
+
+
+def temporal_attention_windows(qkv, pe_qkv, B, F, P, heads, starts, weights, ring=False, out=None):
+    """Window-fused temporal attention (``context.windowed_temporal_attention`` is the definition; FreeNoise, arXiv 2310.15169 3.2).
+    qkv [B*F*P, 3*C]: the fused projection WITHOUT the frame PE, rows (batch, frame, pixel); pe_qkv [L, 3*C]: PE rows 0 .. L-1 through
+    the same projection; ``starts`` [nW] (int32) / ``weights`` [L] (float32): the plan's tables (``context.context_windows`` /
+    ``context.context_weights``; tensors or sequences -- the launch takes host copies, see ``_host_table``); ``ring``: window k
+    holds the frames (starts[k] + p) % F.  One launch; returns [B*F*P, C].  ``out``: preallocated result, rows at any stride that is a
+    multiple of 8 elements."""
+    _dev(qkv, pe_qkv, out)
+    C = qkv.shape[1] // 3
+    assert qkv.shape[0] == B * F * P and qkv.stride(1) == 1
+    assert pe_qkv.dim() == 2 and pe_qkv.shape[1] == 3 * C and pe_qkv.is_contiguous() and pe_qkv.dtype == qkv.dtype
+    rs = qkv.stride(0)
+    if out is None:
+        out = torch.empty((B * F * P, C), dtype=qkv.dtype, device=qkv.device)
+    else:
+        _written(out)
+    assert out.shape == (B * F * P, C) and out.stride(1) == 1 and out.dtype == qkv.dtype
+    os_ = out.stride(0)
+    d = C // heads
+    st, nW = _host_table(starts, ctypes.c_int32)
+    wt, L = _host_table(weights, ctypes.c_float)
+    assert pe_qkv.shape[0] == L, (pe_qkv.shape, L)
+    q, k, v = qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:]
+    rc = lib().im360_temporal_attn_windows_fwd(_p(q), _p(k), _p(v), _p(pe_qkv), _p(out), B, F, P, heads, d,
+                                               P * rs, rs, F * P * rs, P * os_, os_, F * P * os_,
+                                               ctypes.cast(st, _PTR), nW, ctypes.cast(wt, _PTR), L, int(bool(ring)),
+                                               float(d ** -0.5), _dt(qkv), _stream())
+    _check(rc, "im360_temporal_attn_windows_fwd")
+    _count("temporal", 4.0 * B * P * heads * nW * L * L * d, qkv.element_size() * (4 * B * F * P * C + 3 * L * C))
     return out
 
 

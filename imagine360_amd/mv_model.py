@@ -320,6 +320,19 @@ class MultiViewBaseModel(nn.Module):
                 at_module = sh is not None and sh.boundary == "module"
                 mod.frame_shard = sh if at_module == isinstance(mod, TemporalTransformer3DModel) else None
 
+    def set_temporal_windows(self, plan):
+        """Window-fused temporal attention (pipeline ``context_level="attention"``): every VersatileAttention of the motion modules
+        of both UNets attends in the sliding windows of ``plan`` (imagine360_amd.context.WindowPlan: ``starts_dev`` device int32,
+        ``weights`` device float32, ``length``, ``frames``, ``loop``) and fuses the windows' outputs per frame; the model itself runs
+        once on all frames.  None: the plain attention over the whole clip.  The IP adapter's TemporalProjection is no motion module
+        and is never windowed.  Not with a frame shard."""
+        from .unet3d import VersatileAttention
+        if plan is not None and self._sharded:
+            raise ValueError("temporal windows cannot be combined with a frame shard")
+        for mod in self.modules():
+            if isinstance(mod, VersatileAttention):
+                mod.temporal_windows = plan
+
     def _ip_noise(self, like):
         half = self._ip_noise_half
         if half is not None:

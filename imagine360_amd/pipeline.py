@@ -75,6 +75,7 @@ def variance_noise(scheduler, latent, model_dtype, generator, rng, shard=None, f
 
 
 REGENERATE_MODES = ("blend", "release")
+CONTEXT_LEVELS = ("model", "attention")          # where the context windows apply: whole-model forwards, or inside the motion modules' attention
 
 
 class KeepRegion:
@@ -367,7 +368,7 @@ class AnimationPipeline:
                  context_frames=None, context_overlap=4, context_weights="pyramid", guidance_rescale=0.0, context_loop=False,
                  init_latents=None, init_video=None, strength=1.0, regenerate_mask=None, init_resize="bicubic", init_retime=None,
                  free_init_iters=1, free_init_d_s=0.25, free_init_d_t=0.25, regenerate_mode="blend", regenerate_feather=0.0,
-                 guidance_interval=None, **kwargs):
+                 guidance_interval=None, context_level="model", **kwargs):
         """``frame_shard`` (imagine360_amd.dist.FrameShard): this rank denoises a contiguous chunk of the frames (BASELINE
         configs 4 / 5); all ranks must be called with the same seeds and inputs.  Noise is drawn for the whole clip and
         cut, the VAE encodes / the loop runs / the VAE decodes only the local frames, the motion modules exchange tokens
@@ -381,6 +382,17 @@ class AnimationPipeline:
         (context_windows(loop=True)), so a window that crosses the end of the clip shows the motion modules ... F-2, F-1, 0, 1 ...
         as consecutive frames and the loop point is denoised like every other pair of neighbours.  Needs ``context_frames <
         video_length`` (one window cannot wrap); not with ``frame_shard``.
+        ``context_level`` ("model": the above, the default; "attention"): WHERE the windows apply.  "attention" runs the model ONCE per
+        step on all frames and applies the same plan and weight tables inside the motion modules' temporal self-attention -- the only
+        place that looks across frames: every window is attended with frame positions 0 .. L-1 and the windows' attention outputs are
+        fused per frame (FreeNoise's window-based attention fusion, arXiv 2310.15169 section 3.2; one launch of
+        ``kernels.temporal_attention_windows`` per attention, ``context.windowed_temporal_attention`` is its definition).  No frame of
+        an overlap is evaluated twice, and the plain loop runs, so every loop variant works unchanged (graph replay, ``eta``,
+        ``guidance_rescale``, ``init_latents`` / ``strength``, ``regenerate_mask`` in both modes, DPM-Solver++ 2M, ``free_init_iters``,
+        ``guidance_interval``); the IP tokens come from the whole clip.  At most 64 frames (longer clips: "model"), ``context_frames <=
+        16``, not with ``frame_shard``; ``context_frames >= video_length`` is the call without windows.  The result differs from the
+        "model" form (there the windows' noise predictions are blended, here the attention outputs inside every motion module); what
+        either does to a clip's quality can only be judged with trained weights.
         ``guidance_rescale`` (0.0: off; the paper uses 0.7): ``scheduler.rescale_noise_cfg`` on each branch's guided prediction
         before the update (arXiv 2305.08891, section 3.4: with zero-terminal-SNR betas a guidance of 7.5 over-exposes without it),
         the standard deviations over the whole panorama latent / over all views of the perspective latent (with context windows:
@@ -544,11 +556,27 @@ class AnimationPipeline:
         if context_loop and (context_frames is None or int(context_frames) >= vb["video_length"]):
             raise ValueError(f"context_loop needs context_frames < video_length = {vb['video_length']} (one window cannot wrap around), "
                              f"got context_frames={context_frames}")
+        if context_level not in CONTEXT_LEVELS:
+            raise ValueError(f"context_level must be one of {list(CONTEXT_LEVELS)}, got {context_level!r}")
+        attn_plan = None
+        if context_level == "attention":
+            if frame_shard is not None:
+                raise ValueError('context_level="attention" cannot be combined with frame_shard (windows under frame sharding are not '
+                                 "implemented)")
+            if vb["video_length"] > 64:
+                raise ValueError(f'context_level="attention" runs the model once on the whole clip and takes at most 64 frames, got '
+                                 f'video_length={vb["video_length"]}: use context_level="model" (whole-model windows) for longer clips')
+            if context_frames is not None and int(context_frames) > 16:
+                raise ValueError(f'context_level="attention" takes windows of at most 16 frames (the kernel\'s window tile), got '
+                                 f"context_frames={context_frames}")
         if context_frames is not None and int(context_frames) < vb["video_length"]:
             if frame_shard is not None:
                 raise ValueError("context_frames cannot be combined with frame_shard (windows under frame sharding are not implemented)")
             from .context import WindowPlan
             plan = WindowPlan(vb["video_length"], context_frames, context_overlap, context_weights, device, loop=bool(context_loop))
+            if context_level == "attention":
+                # the same plan and tables, applied inside the motion modules' attention: the plain loop runs (``plan`` stays None)
+                attn_plan, plan = plan, None
         assert use_outpaint and use_ip_plus_cross_attention, "the dual pipeline runs with use_outpaint and the IP adapter"
         cfg = guidance_scale_text > 1.0
         assert cfg, "the reference only binds its model inputs under classifier-free guidance (:744-751)"
@@ -622,6 +650,8 @@ class AnimationPipeline:
             self.mv_base_model.set_frame_shard(sh)
         ip_slots = None
         try:
+            if attn_plan is not None:
+                self.mv_base_model.set_temporal_windows(attn_plan)      # before any capture; cleared in the `finally` below
             if prompt_embeds is not None:
                 text_pano, text_pers = prompt_embeds
             else:
@@ -732,6 +762,8 @@ class AnimationPipeline:
         finally:
             if sh is not None:
                 self.mv_base_model.set_frame_shard(None)      # also when the loop raises: the model must not stay sharded
+            if attn_plan is not None:
+                self.mv_base_model.set_temporal_windows(None)  # ... nor windowed
             if ip_slots is not None:
                 ip_slots.__exit__(None, None, None)           # (guidance_interval) back to the single-entry IP-token cache
 

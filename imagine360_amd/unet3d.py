@@ -279,6 +279,19 @@ class VersatileAttention(QKVAttention):
             if temporal_position_encoding else None
         self.is_cross_attention = False
         self.frame_shard = None          # imagine360_amd.dist.FrameShard when frames are split across GPUs
+        self.temporal_windows = None     # imagine360_amd.context.WindowPlan: attend in sliding windows, outputs fused per frame
+
+    def window_pe_qkv(self, length, dtype):
+        """PE rows 0 .. length-1 through the fused QKV weight (no bias) [length, 3 C] in the activation dtype -- the table
+        ``kernels.temporal_attention_windows`` adds to the window rows; built once per (weights, length, dtype) and cached."""
+        if self.pos_encoder is None:
+            raise ValueError("temporal windows need the motion module's positional encoding (temporal_position_encoding=True)")
+        if length > self.pos_encoder.pe.shape[1]:
+            raise ValueError(f"window positions 0 .. {length - 1} exceed temporal_position_encoding_max_len = {self.pos_encoder.pe.shape[1]}")
+        w = self.fused_qkv_weight()
+        pe = self.pos_encoder.pe
+        return self._derived.get(("pe_qkv", length, dtype), (w, pe),
+                                 lambda: (pe[0, :length].to(dtype).float() @ w.float().t()).to(dtype).contiguous())
 
     def frame_pe(self, frames, dtype, f0=None):
         """PE rows of ``frames`` frames starting at ``f0`` (default: this rank's first frame) [frames, C] in the activation
@@ -306,6 +319,19 @@ class VersatileAttention(QKVAttention):
         pixel-sharded layout a frame-sharded motion module works in between its two all-to-alls
         (TemporalTransformer3DModel.forward_cl): the PE row of a token is row // (batch * pixels), no exchange here."""
         c = tokens.shape[-1]
+        win = self.temporal_windows
+        if win is not None:
+            # window-fused attention (pipeline ``context_level="attention"``): the projection WITHOUT the PE, the window positions'
+            # PE rows as a projected table, one launch for all windows (context.windowed_temporal_attention is the definition)
+            if frame_major or self.frame_shard is not None or norm is None:
+                raise ValueError("temporal windows are set: the frame-major / frame-sharded / pre-normalised entries of the motion "
+                                 "module's attention are not windowed")
+            if frames != win.frames:
+                raise ValueError(f"temporal windows were planned for {win.frames} frames, the clip has {frames}")
+            qkv = self.qkv_ln(norm, tokens, stats, post=None)
+            a = kernels.temporal_attention_windows(qkv, self.window_pe_qkv(win.length, tokens.dtype), batch, frames, pixels, self.heads,
+                                                   win.starts_dev, win.weights, ring=win.loop)
+            return self.out_proj(a, residual, row_stats=row_stats)
         sh = None if frame_major else self.frame_shard
         if norm is None:
             qkv = self.qkv(tokens)

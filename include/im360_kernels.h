@@ -80,6 +80,25 @@ int im360_temporal_attn_fwd(const void* q, const void* k, const void* v, void* o
                             int64_t o_fs, int64_t o_ps, int64_t o_bs,
                             float scale, int dtype, void* stream);
 
+/* Window-fused temporal self-attention: the F <= 64 frames are attended as nW sliding windows of L <= 16 consecutive frames
+ * (window k: frames starts[k] + p, modulo F when `ring`, at positions p = 0 .. L-1) and the windows' attention outputs are
+ * fused per frame, weighted by weights[p] over the sum of the weights of the windows that cover the frame -- FreeNoise's
+ * window-based attention fusion (arXiv 2310.15169, section 3.2).  q, k, v: the fused projection WITHOUT the frame PE;
+ * pe_qkv [L, 3 * heads * d] (contiguous): PE rows 0 .. L-1 through the same projection; a window row is
+ * round(q|k|v[frame] + pe_qkv[p]) in the activation dtype.  One launch: q, k, v are read once, every output element is
+ * written once (fp32 fusion, rounded once), no per-window intermediate goes to HBM.  `starts` (nW <= 64) and `weights` (L,
+ * positive) are HOST arrays, copied into the launch: every start in [0, F), start + L <= F unless `ring`, every frame
+ * covered, L <= F; d % 8 == 0; strides and alignment as in im360_temporal_attn_fwd.
+ * Replaces: nothing in the reference (it attends over the whole clip, motion_module.py:343-429); call site:
+ *   imagine360_amd.unet3d.VersatileAttention.forward with windows set (context.windowed_temporal_attention is the
+ *   eager definition). */
+int im360_temporal_attn_windows_fwd(const void* q, const void* k, const void* v, const void* pe_qkv, void* out,
+                                    int64_t B, int64_t F, int64_t P, int64_t heads, int64_t d,
+                                    int64_t qkv_fs, int64_t qkv_ps, int64_t qkv_bs,
+                                    int64_t o_fs, int64_t o_ps, int64_t o_bs,
+                                    const int32_t* starts, int64_t nW, const float* weights, int64_t L, int ring,
+                                    float scale, int dtype, void* stream);
+
 /* Frame-chunk sharding (one process per GPU, imagine360_amd.dist.FrameShard): frame-sharded tokens [B, Fl, P, C] (16-bit,
  * C % 8 == 0) <-> the buffer of the frame <-> pixel all-to-all, [W][Fl][B][PP][C] (W ranks, PP = ceil(P / W), the tail of
  * the last rank zero-filled); dir 0 packs, 1 unpacks.  The receive side of the exchange is read IN PLACE by

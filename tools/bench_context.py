@@ -13,6 +13,10 @@ device events, with the bytes each has to move computed from the shapes.  Prints
                                                       # overlap; ms per step and per window), and the ring entry point of the blend kernel next to
                                                       # the linear one on the SAME non-wrapping tables and on the ring's own; every measurement is
                                                       # made --passes times over, so the spread between identical passes stands next to the numbers
+    python tools/bench_context.py --frames 32 --context-frames 16 --context-overlap 4 --context-level model|attention|both [--loop]
+                                                      # WHERE the windows apply: the captured step of whole-model windows (model) and of windows
+                                                      # inside the motion modules' attention (attention: one forward of all <= 64 frames,
+                                                      # kernels.temporal_attention_windows), alternated round by round for `both`
     python tools/bench_context.py --strength 0.5 [--frames 48] [--num-steps 6] [--loop]
                                                       # the refinement pass: whole pipeline calls (encode, loop, decode; host clock around a call that
                                                       # ends in a device synchronise) from pure noise and, with init_latents taken from a first call,
@@ -666,6 +670,47 @@ def masked_refinement(args, res, call, x0, steps, mask, fin):
     return res
 
 
+def level_bench(args, sch, dev, dt, ts_host):
+    """--context-level: the captured step of one clip under the same window plan at the two levels -- whole-model windows
+    (GraphedWindowedStep: one forward per window, the predictions blended in the step kernel) and windows inside the motion modules'
+    attention (``mv.set_temporal_windows`` + the plain GraphedDenoiseStep: one forward of all frames) -- replays alternated round by
+    round, host clock around work that ends in a device synchronise.  The frame evaluations per step stand next to the times."""
+    from imagine360_amd.graph_step import GraphedDenoiseStep, GraphedWindowedStep
+    frames = args.frames
+    assert args.context_frames < frames <= 64, "--context-level: a clip of at most 64 frames, longer than its windows"
+    plan = WindowPlan(frames, args.context_frames, args.context_overlap, "pyramid", dev, loop=args.loop)
+    levels = ["model", "attention"] if args.context_level == "both" else [args.context_level]
+    res = dict(tool="bench_context --context-level", level=args.context_level, frames=frames, context_frames=plan.length,
+               context_overlap=args.context_overlap, loop=bool(args.loop), windows=plan.starts, pano_hw=PANO_HW, pers_hw=PERS_HW, dtype="bfloat16",
+               device=torch.cuda.get_device_name(0), sampler=args.sampler,
+               frame_evaluations_per_step=dict(model=len(plan) * plan.length, attention=frames))
+    mv = configs.build_mv_model(1, device=dev, dtype=dt, xformers=True)
+    mv.dual_stream, mv.warp_streams = True, True
+    inp = synthetic.mv_inputs(frames=frames, pano_hw=PANO_HW, pers_hw=PERS_HW, seed=1, dtype=dt, device=dev)
+    inp.pop("timestep")
+    cams = synthetic.icosahedron_cameras(90, PERS_PX, device=dev)
+    pano_lat, pers_lat = inp["pano_latent"][:1, :4].contiguous(), inp["latents"][:1, :, :4].contiguous()
+    graphs = {}
+    if "model" in levels:
+        with ip_cache_slots(mv, len(plan)):
+            graphs["model_level_step"] = GraphedWindowedStep(mv, sch, inp, cams, pano_lat, pers_lat, 7.5, plan, warmup=1)
+        torch.cuda.synchronize()
+        print("captured: whole-model windows", file=sys.stderr, flush=True)
+    if "attention" in levels:
+        mv.set_temporal_windows(plan)
+        try:
+            graphs["attention_level_step"] = GraphedDenoiseStep(mv, sch, inp, cams, pano_lat, pers_lat, 7.5, warmup=1)
+        finally:
+            mv.set_temporal_windows(None)            # (the captured launches keep the tables they were made with)
+        torch.cuda.synchronize()
+        print("captured: windows inside the temporal attention", file=sys.stderr, flush=True)
+    res.update(time_steps(graphs, ts_host, args.steps, args.rounds))
+    res["finite"] = all(bool(torch.isfinite(g.pano_lat.float()).all() and torch.isfinite(g.pers_lat.float()).all()) for g in graphs.values())
+    if len(graphs) == 2:
+        res["attention_over_model"] = res["attention_level_step"]["ms_median"] / res["model_level_step"]["ms_median"]
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=3)
@@ -690,6 +735,11 @@ def main():
                     help="guided and unguided captured steps of one 25-step run at cfg2 size, interleaved (--steps replays per round, --rounds)")
     ap.add_argument("--pano-hw", type=int, nargs=2, default=[128, 256], metavar=("H", "W"), help="--init-scale: latent size of the full-size run (default: cfg5)")
     ap.add_argument("--sampler", choices=["ddim", "dpmpp2m"], default="ddim", help="the scheduler of every step and call (dpmpp2m: DPM-Solver++ 2M)")
+    ap.add_argument("--context-level", choices=["model", "attention", "both"], default=None,
+                    help="one captured step of a clip of --frames frames (<= 64) under windows of --context-frames with --context-overlap: whole-model "
+                         "windows (model), windows inside the motion modules' attention (attention), or both alternated round by round")
+    ap.add_argument("--context-frames", type=int, default=LENGTH, help="--context-level: frames per window")
+    ap.add_argument("--context-overlap", type=int, default=OVERLAP, help="--context-level: frames two neighbouring windows share")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_context.py measures on the MI355X; there is nothing to time without one"
@@ -699,6 +749,8 @@ def main():
     sch = (DPMSolverMultistepScheduler if args.sampler == "dpmpp2m" else DDIMScheduler)(**configs.NOISE_SCHEDULER_KWARGS)
     sch.set_timesteps(25)
     ts_host = [int(t) for t in sch._timesteps_host]
+    if args.context_level is not None:
+        return emit(level_bench(args, sch, dev, dt, ts_host), args.out)
     if args.guidance_interval is not None:
         return emit(interval_bench(args, sch, dev, dt, ts_host), args.out)
     if args.free_init is not None:

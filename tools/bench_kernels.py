@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Per-kernel micro-benchmarks at BASELINE cfg2 shapes (run on the MI355X):
 
-    python tools/bench_kernels.py [attn] [conv] [temporal] [ln] [gn] [sampler_step] [unguided_step] [free_init_noise] [keep_release] [sphere_distance2] [--iters N]
+    python tools/bench_kernels.py [attn] [conv] [temporal] [temporal_windows] [ln] [gn] [sampler_step] [unguided_step] [free_init_noise] [keep_release] [sphere_distance2] [--iters N]
 
 Prints achieved TFLOP/s (MFMA kernels, vs 2500 dense bf16) or GB/s (HBM kernels, vs 8000) per shape.
 Usable under `rocprofv3 --pmc ...` for counters of one kernel class.
@@ -191,6 +191,49 @@ def bench_temporal(iters):
         K.tuning_set("tattn_scalar", 0)
         print(f"tattn {name:16s} B={B:3d} F={Fr} P={P:5d} C={C:4d}: {t * 1e3:8.3f} ms  {by / t / 1e9:7.0f} GB/s ({by / t / 8e12 * 100:4.1f}% of HBM peak)"
               f" | scalar kernel {ts * 1e3:8.3f} ms {by / ts / 1e9:7.0f} GB/s")
+
+
+def bench_temporal_windows(iters):
+    """``kernels.temporal_attention_windows`` (windows of 16, overlap 4) at the motion-module shapes of a 32-frame 512 x 1024 run, next to
+    the unwindowed ``kernels.temporal_attention`` at the same (B, F, P, heads, d) -- the same q, k, v, o bytes: the yardstick -- and to the
+    per-window composition in torch on the existing kernel (gather + PE add, one launch per window, fp32 blend).  Device events, 3 rounds
+    alternated.  A JSON line per shape, for profiles/."""
+    import json
+    from imagine360_amd import context as CTX
+    Fr, L, o, heads = 32, 16, 4, 8
+    starts, w = CTX.context_windows(Fr, L, o), CTX.context_weights(L).to(DEV)
+    st = torch.tensor(starts, dtype=torch.int32, device=DEV)
+    wsum = torch.zeros(Fr, device=DEV)
+    for s in starts:
+        wsum[s:s + L] += w
+    for name, B, P, C in [("pers L0", 40, 1024, 320), ("pano L0", 2, 8192, 320), ("pers L1", 40, 256, 640), ("pano L1", 2, 2048, 640),
+                          ("pers L2", 40, 64, 1280), ("pano L2", 2, 512, 1280)]:
+        qkv, pe = rn(B * Fr * P, 3 * C), rn(L, 3 * C)
+
+        def composed():
+            x = qkv.view(B, Fr, P, 3 * C)
+            acc = torch.zeros(B, Fr, P, C, device=DEV)
+            for s in starts:
+                rows = (x[:, s:s + L].float() + pe.float()[None, :, None, :]).to(DT).reshape(B * L * P, 3 * C)
+                a = K.temporal_attention(rows, B, L, P, heads).view(B, L, P, C)
+                acc[:, s:s + L] += a.float() * (w / wsum[s:s + L])[None, :, None, None]
+            return acc.to(DT).view(B * Fr * P, C)
+        fused, plain = (lambda: K.temporal_attention_windows(qkv, pe, B, Fr, P, heads, st, w)), (lambda: K.temporal_attention(qkv, B, Fr, P, heads))
+        diff = float((fused().float() - composed().float()).abs().max())
+        tf, tp, tc = [], [], []
+        for _ in range(3):
+            tf.append(timeit(fused, iters))
+            tp.append(timeit(plain, iters))
+            tc.append(timeit(composed, max(1, iters // 4)))
+        tf.sort(), tp.sort(), tc.sort()
+        by = 4.0 * B * Fr * P * C * 2
+        row = dict(bench="temporal_windows", shape=name, B=B, F=Fr, P=P, heads=heads, d=C // heads, L=L, overlap=o, windows=starts, iters=iters,
+                   windows_us=[t * 1e6 for t in tf], unwindowed_us=[t * 1e6 for t in tp], composed_us=[t * 1e6 for t in tc], bytes=by,
+                   windows_gb_per_s=by / tf[0] / 1e9, unwindowed_gb_per_s=by / tp[0] / 1e9, windows_over_unwindowed=tf[1] / tp[1],
+                   composed_over_windows=tc[1] / tf[1], max_abs_diff_vs_composed=diff)
+        print(f"tattn_windows {name:8s} B={B:3d} F={Fr} P={P:5d} C={C:4d}: {tf[1] * 1e3:8.3f} ms {by / tf[0] / 1e9:6.0f} GB/s | unwindowed {tp[1] * 1e3:8.3f} ms "
+              f"{by / tp[0] / 1e9:6.0f} GB/s | x{tf[1] / tp[1]:5.2f} | per-window composition {tc[1] * 1e3:8.3f} ms | max diff {diff:.3f}")
+        print("JSON", json.dumps(row))
 
 
 def bench_ln(iters):

@@ -24,13 +24,14 @@ tolerance does not count as checked; multi-process tests are not traced):
     python -m pytest -q -m gpu tests/test_release_mask_gpu.py::test_keep_latents_release_parity
     python -m pytest -q -m gpu tests/test_sphere_feather_gpu.py::test_sphere_distance2_parity
     python -m pytest -q -m gpu tests/test_guidance_interval_gpu.py::test_unguided_step_kernels_parity
+    python -m pytest -q -m gpu tests/test_temporal_windows_gpu.py::test_windows_kernel_vs_fp64
 
 each as   rocprofv3 --kernel-trace --stats -M --output-format csv -d <dir>/<label> -o trace -- <command>   (mangled names; kernel trace only,
 no counters), one rocprofv3 invocation per command, each under its own `timeout -k 10`; the job stops at the first step that fails.
 
     python tools/kernel_launch_coverage.py --emit-script <dir> > job.sh      # the MI355X job: per command an untraced run (its wall time x 3 is
                                                                             # the traced run's time limit), then the traced run; writes <dir>/<label>/
-    python tools/kernel_launch_coverage.py --collect <dir> --commit <hash>   # <dir>/<label>/*kernel_stats.csv + meta.json -> tests/golden/kernel_launch_ledger_interval.json
+    python tools/kernel_launch_coverage.py --collect <dir> --commit <hash>   # <dir>/<label>/*kernel_stats.csv + meta.json -> tests/golden/kernel_launch_ledger_tattn_windows.json
     python tools/kernel_launch_coverage.py --report                          # library kernels against the ledger: unlaunched, stale, unpaired dtypes
 """
 import argparse
@@ -52,9 +53,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # resize_pano_latent_kernel, kernel_launch_ledger_resize.json the one before the multistep step kernels,
 # kernel_launch_ledger_multistep.json the one before retime_pano_latent_kernel, kernel_launch_ledger_retime.json the one before the
 # free_init kernels, kernel_launch_ledger_freeinit.json the one before keep_latents_kernel took its RELEASE argument and
-# sphere_distance2_kernel, kernel_launch_ledger_release.json the one before the step kernels took their GUIDED argument and ddim_kernel: all ten kept as
-# they were, no longer read)
-LEDGER = os.path.join(ROOT, "tests", "golden", "kernel_launch_ledger_interval.json")
+# sphere_distance2_kernel, kernel_launch_ledger_release.json the one before the step kernels took their GUIDED argument and ddim_kernel,
+# kernel_launch_ledger_interval.json the one before temporal_attn_windows_kernel: all eleven kept as they were, no longer read)
+LEDGER = os.path.join(ROOT, "tests", "golden", "kernel_launch_ledger_tattn_windows.json")
 LIB = os.path.join(ROOT, "imagine360_amd", "libim360_kernels.so")
 LLVM = "/opt/rocm/lib/llvm/bin"
 PREFIX = "_ZN5im360"
@@ -82,7 +83,8 @@ RUNS = [("test_kernels_gpu", ["tests/test_kernels_gpu.py"]),
         ("test_free_init_gpu", ["tests/test_free_init_gpu.py::test_free_init_noise_parity"]),
         ("test_release_mask_gpu", ["tests/test_release_mask_gpu.py::test_keep_latents_release_parity"]),
         ("test_sphere_feather_gpu", ["tests/test_sphere_feather_gpu.py::test_sphere_distance2_parity"]),
-        ("test_guidance_interval_gpu", ["tests/test_guidance_interval_gpu.py::test_unguided_step_kernels_parity"])]
+        ("test_guidance_interval_gpu", ["tests/test_guidance_interval_gpu.py::test_unguided_step_kernels_parity"]),
+        ("test_temporal_windows_gpu", ["tests/test_temporal_windows_gpu.py::test_windows_kernel_vs_fp64"])]
 
 
 def command(args):
