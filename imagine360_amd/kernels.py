@@ -83,8 +83,10 @@ _SIGNATURES = {
     "im360_layernorm": (_INT, [_PTR] * 6 + [_I64] * 5 + [_F32, _INT, _PTR]),
     "im360_geglu": (_INT, [_PTR] * 2 + [_I64] * 2 + [_INT, _PTR]),
     "im360_linear_geglu": (_INT, [_PTR] * 4 + [_I64] * 3 + [_INT, _PTR]),
+    "im360_ff_fused": (_INT, [_PTR] * 6 + [_I64, _F32] + [_PTR] * 4 + [_I64] * 4 + [_INT, _PTR]),
     "im360_softmax_rows": (_INT, [_PTR] * 2 + [_I64] * 4 + [_F32, _INT, _PTR]),
     "im360_tuning_set": (_INT, [_INT, _INT]),
+    "im360_tuning_get": (_INT, [_INT]),
     "im360_prof_enable": (None, [ctypes.c_uint]),
     "im360_prof_collect": (_INT, [_INT, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long)]),
 }
@@ -814,6 +816,42 @@ def linear_geglu(x, w_packed, bias_packed, inner):
     return y
 
 
+FF_FUSED_SHAPE = (320, 1280)          # (K = N, inner) of the feed-forward that ``ff_fused`` / ``ff_fused_ln`` cover
+
+
+def _ff_fused(x, w1_packed, b1_packed, c1, c2, stats, eps, w2_packed, b2, res, tag):
+    _dev(x, w1_packed, b1_packed, c1, c2, stats, w2_packed, b2, res)
+    k, inner = FF_FUSED_SHAPE
+    m = x.numel() // k
+    assert x.shape[-1] == k and x.is_contiguous() and w1_packed.shape[2] == k and w1_packed.shape[0] >= 2 * inner
+    assert w2_packed.shape[2] == inner and w2_packed.shape[1] == 1 and w2_packed.shape[0] >= k and w2_packed.dtype == x.dtype
+    assert res.is_contiguous() and res.numel() == x.numel() and res.dtype == x.dtype
+    y = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    rc = lib().im360_ff_fused(_p(x), _p(w1_packed), _p(b1_packed), _p(c1), _p(c2), _p(stats), 0 if stats is None else stats.shape[1],
+                              float(eps), _p(w2_packed), _p(b2), _p(res), _p(y), m, k, inner, k, _dt(x), _stream())
+    _check(rc, "im360_ff_fused")
+    es = x.element_size()
+    _count("gemm", 2.0 * m * k * 2 * inner + 2.0 * m * inner * k,
+           es * (x.numel() + 2 * inner * k + k * inner + y.numel() + res.numel()) + (0 if stats is None else 4 * stats.numel()),
+           shape=f"{tag}:{k}:{inner}")
+    return y
+
+
+def ff_fused(x, w1_packed, b1_packed, w2_packed, b2, res):
+    """GEGLU feed-forward of a 320-channel block + residual in ONE launch: ``linear_geglu(x, w1_packed, b1_packed, 1280)`` followed by
+    the [1280 -> 320] Linear with bias ``b2`` and residual ``res`` (w2_packed = ``pack_conv_weight`` of the [320, 1280, 1, 1] view);
+    the 1280-wide intermediate stays in LDS.  Same bits as the pair of launches."""
+    return _ff_fused(x, w1_packed, b1_packed, None, None, None, 0.0, w2_packed, b2, res, "ff")
+
+
+def ff_fused_ln(x, w1_packed, c1, c2, stats, eps, w2_packed, b2, res):
+    """``ff_fused`` with the LayerNorm in front folded into the first GEMM: operands as in ``linear_geglu_ln``."""
+    assert stats.dtype == torch.float32 and stats.is_contiguous() and stats.shape[0] == x.numel() // x.shape[-1] and stats.shape[2] == 2
+    for t in (c1, c2):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == 2 * FF_FUSED_SHAPE[1]
+    return _ff_fused(x, w1_packed, None, c1, c2, stats, eps, w2_packed, b2, res, "ff_ln")
+
+
 def softmax_rows(x, scale=1.0, out=None):
     """softmax(x * scale) over the last dim of a 2-D tensor (fp32 inside); ``out`` may be ``x`` (in place)."""
     _dev(x, out)
@@ -1381,7 +1419,7 @@ def free_init_noise(x0, n1, n2, Lf, Lh, Lw, sa, sb):
 
 # ------------------------------------------------------------------------------------------ tuning knobs
 KNOBS = {"attn_qb": 0, "conv_big": 1, "conv_bk": 2, "tattn_scalar": 3, "conv_ring": 4, "attn_hl": 5, "conv_dbg": 6, "conv_halo": 7, "conv_cm": 8, "ln_packed": 9,
-         "ring_groups": 10, "attn_x": 11, "attn_ds": 12, "attn_one": 13, "attn_dbg": 14, "attn_hg": 15, "conv_small": 16, "attn_w3": 17, "attn_pipe": 18, "conv_stag": 19, "conv_persist": 20, "gn_apply": 21, "tattn_nt": 22, "nt": 23, "g4": 24, "gn_wgs": 25, "conv_ksplit": 26}
+         "ring_groups": 10, "attn_x": 11, "attn_ds": 12, "attn_one": 13, "attn_dbg": 14, "attn_hg": 15, "conv_small": 16, "attn_w3": 17, "attn_pipe": 18, "conv_stag": 19, "conv_persist": 20, "gn_apply": 21, "tattn_nt": 22, "nt": 23, "g4": 24, "gn_wgs": 25, "conv_ksplit": 26, "ff_fused": 27}
 
 
 ATTN_PIPE_DEFAULT = -1         # the library's default for the attn_pipe knob (abi.cpp)
@@ -1397,6 +1435,11 @@ def tuning_set(name, value):
     conv_halo / conv_cm change the fp32 summation order, attn_x (0 against 1 - 3) and attn_ds the 16-bit rounding points,
     conv_dbg / attn_dbg break results on purpose, the others do not change results."""
     _check(lib().im360_tuning_set(KNOBS[name], int(value)), "im360_tuning_set")
+
+
+def tuning_get(name):
+    """The knob's current value in the library (its default, the IM360_* environment variable or the last ``tuning_set``)."""
+    return lib().im360_tuning_get(KNOBS[name])
 
 
 # ------------------------------------------------------------------------------------------ profiling

@@ -218,23 +218,39 @@ class GEGLU(nn.Module):
         # 2I-wide intermediate never goes to HBM); otherwise hipBLASLt + the elementwise kernel
         # (measured, tools/bench_kernels.py geglu_fused: wins for K <= 640 at >= 64k tokens, loses at K = 1280 / 40k)
         fused = (x.is_cuda or ROUTE_ON_CPU) and k % 64 == 0 and k <= GEGLU_FUSED_MAX_K and two_i % 256 == 0 and m >= ROUTE_MIN_TOKENS
-        cache = _module_cache(self)
-        bias = None if self.proj.bias is None else self.proj.bias.detach()
         if fused and ln is not None and stats is not None:
-            def build():
-                wg, c1, c2 = kernels.fold_layer_norm(self.proj.weight, bias, ln.weight, ln.bias)
-                wp, c1p = kernels.pack_geglu(wg, c1)
-                return wp, c1p.contiguous(), kernels.interleave_geglu(wg, c2)[1].contiguous()
-            ps = tuple(t for t in (self.proj.weight, self.proj.bias, ln.weight, ln.bias) if t is not None)
-            wp, c1p, c2p = cache.get("geglu_ln", ps, build)
+            wp, c1p, c2p = self.packed_ln(ln)
             return kernels.linear_geglu_ln(x.contiguous(), wp, c1p, c2p, stats, ln.eps, two_i // 2)
         if ln is not None:
             x = layer_norm(ln, x)
         if fused:
-            ps = (self.proj.weight,) if self.proj.bias is None else (self.proj.weight, self.proj.bias)
-            wp, bp = cache.get("geglu", ps, lambda: kernels.pack_geglu(self.proj.weight.detach(), bias))
+            wp, bp = self.packed()
             return kernels.linear_geglu(x.contiguous(), wp, bp, two_i // 2)
         return kernels.geglu(self.proj(x))
+
+    def packed(self):
+        """Operands of ``kernels.linear_geglu`` / ``kernels.ff_fused``: (packed weight, packed bias or None), cached."""
+        bias = None if self.proj.bias is None else self.proj.bias.detach()
+        ps = (self.proj.weight,) if self.proj.bias is None else (self.proj.weight, self.proj.bias)
+        return _module_cache(self).get("geglu", ps, lambda: kernels.pack_geglu(self.proj.weight.detach(), bias))
+
+    def packed_ln(self, ln):
+        """Operands of ``kernels.linear_geglu_ln`` / ``kernels.ff_fused_ln`` with LayerNorm ``ln`` folded in: (packed gamma (.) W, c1, c2), cached."""
+        bias = None if self.proj.bias is None else self.proj.bias.detach()
+
+        def build():
+            wg, c1, c2 = kernels.fold_layer_norm(self.proj.weight, bias, ln.weight, ln.bias)
+            wp, c1p = kernels.pack_geglu(wg, c1)
+            return wp, c1p.contiguous(), kernels.interleave_geglu(wg, c2)[1].contiguous()
+        ps = tuple(t for t in (self.proj.weight, self.proj.bias, ln.weight, ln.bias) if t is not None)
+        return _module_cache(self).get("geglu_ln", ps, build)
+
+
+def ff_fused_route(on_gpu, k, inner, n, m, has_residual, knob_on):
+    """Whether a feed-forward call (x [m, k] -> inner -> n, + residual) runs as the one fused launch of ``kernels.ff_fused``: on the GPU
+    only -- never on ROUTE_ON_CPU's stand-ins --, the 320-channel blocks (k = n = 320, inner 1280), a residual of x's shape, at least
+    ROUTE_MIN_TOKENS rows (below, the GEMMs go to hipBLASLt), knob ff_fused on."""
+    return bool(on_gpu and (k, inner) == kernels.FF_FUSED_SHAPE and n == k and has_residual and m >= ROUTE_MIN_TOKENS and knob_on)
 
 
 class FeedForward(nn.Module):
@@ -246,9 +262,31 @@ class FeedForward(nn.Module):
         self.net = nn.ModuleList([GEGLU(dim, dim * mult), nn.Dropout(0.0), nn.Linear(dim * mult, dim)])
 
     def forward(self, x, residual=None, ln=None, stats=None):
-        """``ln`` / ``stats``: the LayerNorm in front of the block and (optionally) the statistics of x's rows, see GEGLU."""
+        """``ln`` / ``stats``: the LayerNorm in front of the block and (optionally) the statistics of x's rows, see GEGLU.
+        The 320-channel blocks with a residual take ONE launch (``kernels.ff_fused`` / ``ff_fused_ln``: the 1280-wide GEGLU output
+        stays on the CU) at the token counts that route to the MFMA GEMMs; knob ff_fused = 0: the pair of launches below."""
+        if self.takes_fused(x, residual):
+            geglu, out = self.net[0], self.net[2]
+            n, inner = out.weight.shape
+            w2p = _module_cache(out).get("w1x1", (out.weight,), lambda: kernels.pack_conv_weight(out.weight.detach().reshape(n, inner, 1, 1)))
+            b2 = None if out.bias is None else out.bias.detach()
+            if ln is not None and stats is not None:
+                wp, c1p, c2p = geglu.packed_ln(ln)
+                return kernels.ff_fused_ln(x.contiguous(), wp, c1p, c2p, stats, ln.eps, w2p, b2, residual.contiguous())
+            if ln is not None:
+                x = layer_norm(ln, x)
+            wp, bp = geglu.packed()
+            return kernels.ff_fused(x.contiguous(), wp, bp, w2p, b2, residual.contiguous())
         h = self.net[0](x, ln, stats)
         return self.net[2](h) if residual is None else linear_residual(self.net[2], h, residual)
+
+    def takes_fused(self, x, residual):
+        """Whether this call runs as the one fused launch: on the GPU only (never under ROUTE_ON_CPU's stand-ins), K = N = 320 with inner
+        1280, a residual of x's shape, at least ROUTE_MIN_TOKENS rows, knob ff_fused on."""
+        two_i, k = self.net[0].proj.weight.shape
+        n = self.net[2].weight.shape[0]
+        shapes_fit = ff_fused_route(x.is_cuda, k, two_i // 2, n, x.numel() // k, residual is not None and residual.shape == x.shape, True)
+        return shapes_fit and kernels.tuning_get("ff_fused") != 0             # (the knob lives in the library: asked last, on the GPU only)
 
 
 class QKVAttention(nn.Module):

@@ -609,6 +609,19 @@ int im360_linear_ln_fwd(const void* x, const void* w_packed, const void* c1, con
 int im360_linear_geglu_ln(const void* x, const void* w_packed, const void* c1, const void* c2, const void* rowstats,
                           int64_t rs_p, float eps, void* y, int64_t M, int64_t K, int64_t I, int dtype, void* stream);
 
+/* The whole GEGLU feed-forward of a 320-channel block in one launch (an addition under ABI version 5): the 1280-wide GEGLU output stays in LDS.
+ *   y[M, N] = GEGLU(LN(x) W1^T + b1) W2^T + b2 + res          K = 320, I = 1280, N = 320 only (else IM360_ERR_UNSUPPORTED)
+ * LayerNorm-folded form (c1 != NULL): w1_packed, c1, c2, rowstats, rs_p, eps as in im360_linear_geglu_ln, b1_packed ignored;
+ * plain form (c1 == NULL): w1_packed, b1_packed (optional) as in im360_linear_geglu.  w2_packed = im360_pack_conv_weight of the
+ * [N, I, 1, 1] view, b2 [N] optional, res [M, N] required (it may alias x), y [M, N]; pointers 16-byte aligned (rowstats 8).
+ * Same MFMA shape, K order, 16-bit rounding of the intermediate and epilogue arithmetic as im360_linear_geglu[_ln] followed by
+ * im360_conv_fwd on the [M, 1, 1, I] view with bias and residual.
+ * Replaces: FeedForward (GEGLU -> Dropout(0) -> Linear) + residual behind norm3, diffusers/models/attention_lora.py:493-547,
+ *   activations.py:93-125; animatediff/models/attention.py:503-508; motion_module.py:255-258. */
+int im360_ff_fused(const void* x, const void* w1_packed, const void* b1_packed, const void* c1, const void* c2,
+                   const void* rowstats, int64_t rs_p, float eps, const void* w2_packed, const void* b2, const void* res, void* y,
+                   int64_t M, int64_t K, int64_t I, int64_t N, int dtype, void* stream);
+
 /* y[r, :] = softmax(x[r, :] * scale), fp32 arithmetic on 16-bit rows (cols and the row strides multiples of 8; in place
  * allowed).  With two launches of im360_conv_fwd as GEMMs it forms the single-head d = 512 attention of the VAE.
  * Replaces: AttentionBlock.forward's softmax(attention_scores.float()), diffusers/models/attention.py:336-364. */
@@ -654,6 +667,8 @@ int im360_max_rect(const uint8_t* mask, int64_t H, int64_t W, int64_t* rect);
  * attention load / store forms), 23 (non-temporal epilogue stores), 25 (GroupNorm apply workgroups) -- do not change a bit
  * (tests/test_kernel_variants_gpu.py). */
 int im360_tuning_set(int knob, int value);
+/* the knob's current value (an addition under ABI version 5; 0 for an unknown knob): host-side routing reads knob ff_fused through it */
+int im360_tuning_get(int knob);
 
 /* ---- diagnostics: the ONLY process-global state behind this ABI (boundary nit).  A production binding needs neither
  * im360_tuning_set (A/B switches; the defaults are the measured best and no compute entry point requires a knob) nor the two

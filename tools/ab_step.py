@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Interleaved A/B of WHOLE cfg2 denoising steps (the benchmarked launch mode: one captured hipGraph, panorama branch on a side
 stream) under different tuning knobs / host settings: one model, one graph per variant (the knobs are baked in at capture), the
-variants' replays alternated round by round so that clock ramps and box noise hit all of them alike; minimum and median ms per step,
+variants' replays alternated round by round so that clock ramps and box noise hit all of them alike; minimum and median ms per step (and every round's figure),
 and whether the updated latents are bit-identical to the first variant's.
     python tools/ab_step.py "base" "nt=1" "tattn_nt=1" "nt=1,tattn_nt=3" "GN_MODE=three" [--steps 6] [--rounds 4]
 A variant is a comma-separated list of knob=value (kernels.KNOBS) or NAME=value for an upper-case attribute of imagine360_amd.kernels
@@ -123,6 +123,7 @@ def main():
         rel = float((finals[vi][1].float() - finals[0][1].float()).norm() / finals[0][1].float().norm())
         print(f"{spec:40s} min {min(times[vi]):8.2f} ms  median {statistics.median(times[vi]):8.2f} ms  ({len(times[vi])} rounds x {steps} steps)"
               f"  {'bit-identical to the first' if same else f'differs from the first: rel {rel:.2e}'}", flush=True)
+        print(f"{'':40s} per round: " + "  ".join(f"{t:.2f}" for t in times[vi]), flush=True)
 
 
 if __name__ == "__main__":

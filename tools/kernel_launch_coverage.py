@@ -25,13 +25,16 @@ tolerance does not count as checked; multi-process tests are not traced):
     python -m pytest -q -m gpu tests/test_sphere_feather_gpu.py::test_sphere_distance2_parity
     python -m pytest -q -m gpu tests/test_guidance_interval_gpu.py::test_unguided_step_kernels_parity
     python -m pytest -q -m gpu tests/test_temporal_windows_gpu.py::test_windows_kernel_vs_fp64
+    python -m pytest -q -m gpu tests/test_ff_fused_gpu.py
 
 each as   rocprofv3 --kernel-trace --stats -M --output-format csv -d <dir>/<label> -o trace -- <command>   (mangled names; kernel trace only,
 no counters), one rocprofv3 invocation per command, each under its own `timeout -k 10`; the job stops at the first step that fails.
 
     python tools/kernel_launch_coverage.py --emit-script <dir> > job.sh      # the MI355X job: per command an untraced run (its wall time x 3 is
                                                                             # the traced run's time limit), then the traced run; writes <dir>/<label>/
-    python tools/kernel_launch_coverage.py --collect <dir> --commit <hash>   # <dir>/<label>/*kernel_stats.csv + meta.json -> tests/golden/kernel_launch_ledger_tattn_windows.json
+    python tools/kernel_launch_coverage.py --collect <dir> --commit <hash>   # <dir>/<label>/*kernel_stats.csv + meta.json -> tests/golden/kernel_launch_ledger_ff_fused.json
+    python tools/kernel_launch_coverage.py --collect <dir> --label <label>   # only these runs were traced again: the other runs' launches are taken
+                                                                            # over from --base (default: the previous ledger) for the kernels the library still has
     python tools/kernel_launch_coverage.py --report                          # library kernels against the ledger: unlaunched, stale, unpaired dtypes
 """
 import argparse
@@ -54,8 +57,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # kernel_launch_ledger_multistep.json the one before retime_pano_latent_kernel, kernel_launch_ledger_retime.json the one before the
 # free_init kernels, kernel_launch_ledger_freeinit.json the one before keep_latents_kernel took its RELEASE argument and
 # sphere_distance2_kernel, kernel_launch_ledger_release.json the one before the step kernels took their GUIDED argument and ddim_kernel,
-# kernel_launch_ledger_interval.json the one before temporal_attn_windows_kernel: all eleven kept as they were, no longer read)
-LEDGER = os.path.join(ROOT, "tests", "golden", "kernel_launch_ledger_tattn_windows.json")
+# kernel_launch_ledger_interval.json the one before temporal_attn_windows_kernel, kernel_launch_ledger_tattn_windows.json the one before
+# ff_fused_kernel: all twelve kept as they were; the last one is read only as the default --base of a partial --collect)
+LEDGER = os.path.join(ROOT, "tests", "golden", "kernel_launch_ledger_ff_fused.json")
+PREVIOUS_LEDGER = os.path.join(ROOT, "tests", "golden", "kernel_launch_ledger_tattn_windows.json")
 LIB = os.path.join(ROOT, "imagine360_amd", "libim360_kernels.so")
 LLVM = "/opt/rocm/lib/llvm/bin"
 PREFIX = "_ZN5im360"
@@ -84,7 +89,8 @@ RUNS = [("test_kernels_gpu", ["tests/test_kernels_gpu.py"]),
         ("test_release_mask_gpu", ["tests/test_release_mask_gpu.py::test_keep_latents_release_parity"]),
         ("test_sphere_feather_gpu", ["tests/test_sphere_feather_gpu.py::test_sphere_distance2_parity"]),
         ("test_guidance_interval_gpu", ["tests/test_guidance_interval_gpu.py::test_unguided_step_kernels_parity"]),
-        ("test_temporal_windows_gpu", ["tests/test_temporal_windows_gpu.py::test_windows_kernel_vs_fp64"])]
+        ("test_temporal_windows_gpu", ["tests/test_temporal_windows_gpu.py::test_windows_kernel_vs_fp64"]),
+        ("test_ff_fused_gpu", ["tests/test_ff_fused_gpu.py"])]
 
 
 def command(args):
@@ -135,9 +141,22 @@ def read_counts(path):
     return counts
 
 
-def collect(directory, commit):
+def collect(directory, commit, labels=(), base=None):
     runs, kernels = [], {}
+    old = None
+    if labels:
+        # a partial regeneration: the runs that were not traced again keep the launches the base ledger recorded for them
+        with open(base or (LEDGER if os.path.exists(LEDGER) else PREVIOUS_LEDGER)) as fh:
+            old = json.load(fh)
+        have_now = library_kernels()
+        for name, per in old["kernels"].items():
+            kept = {lab: n for lab, n in per.items() if lab not in labels}
+            if kept and (have_now is None or name in have_now):
+                kernels[name] = kept
     for label, args in RUNS:
+        if labels and label not in labels:
+            runs += [r for r in old["runs"] if r["label"] == label]
+            continue
         d = os.path.join(directory, label)
         files = sorted(glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)) or \
             sorted(glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True))
@@ -160,7 +179,8 @@ def collect(directory, commit):
             h.update(f.encode() + b"\0" + open(os.path.join(csrc, f), "rb").read())
     ledger = {"commit": commit,
               "csrc_sha256": h.hexdigest(),
-              "note": "launches per traced test file of every im360 kernel; regenerate with tools/kernel_launch_coverage.py after adding or re-templating a kernel",
+              "note": "launches per traced test file of every im360 kernel; regenerate with tools/kernel_launch_coverage.py after adding or re-templating a kernel"
+                      + (f"; runs {', '.join(labels)} traced at this commit, the others taken over from the ledger of commit {old['commit']}" if labels else ""),
               "library_kernels": None if have is None else len(have),
               "runs": runs,
               "kernels": {k: kernels[k] for k in sorted(kernels)}}
@@ -221,7 +241,8 @@ def emit_script(directory, labels=()):
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--emit-script", metavar="DIR", help="print the MI355X job that writes DIR/<label>/ (DIR relative to the repository root)")
-    ap.add_argument("--label", action="append", default=[], help="--emit-script: only this run (repeatable; a job has a time limit of its own)")
+    ap.add_argument("--label", action="append", default=[], help="--emit-script / --collect: only this run (repeatable; a job has a time limit of its own)")
+    ap.add_argument("--base", default=None, help="--collect --label: the ledger whose other runs are taken over (default: the current ledger, else the previous one)")
     ap.add_argument("--collect", metavar="DIR", help="build the ledger from DIR/<label>/")
     ap.add_argument("--commit", default=None, help="commit the traced tree was built from (default: git rev-parse HEAD)")
     ap.add_argument("--report", action="store_true", help="compare the ledger with the kernels inside the built library")
@@ -231,7 +252,7 @@ def main():
         emit_script(a.emit_script, tuple(a.label))
     if a.collect:
         commit = a.commit or subprocess.run(["git", "rev-parse", "HEAD"], capture_output=True, text=True, cwd=ROOT, check=True).stdout.strip()
-        collect(a.collect, commit)
+        collect(a.collect, commit, tuple(a.label), a.base)
     if a.report:
         missing, stale, unpaired = report(tuple(a.without))
         sys.exit(1 if (missing or stale or unpaired) else 0)
