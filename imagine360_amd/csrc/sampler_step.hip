@@ -2,7 +2,8 @@
 // (cfg_ddim_kernel, cfg_ddim_step_kernel), the same step on the blend of temporal context windows on a line or a ring
 // (cfg_ddim_step_windows_kernel), the statistics pass of the guidance rescale (cfg_rescale_*), and the DPM-Solver++ 2M update
 // (arXiv 2211.01095, algorithm 2) on the same combine, blend, rescale and x0 conversion (cfg_multistep_step_kernel,
-// cfg_multistep_step_windows_kernel), with its fp32 x0 history updated in place.  Every step kernel has an unguided form
+// cfg_multistep_step_windows_kernel), with its fp32 x0 history updated in place, and the statistics pass and the four guided steps of
+// adaptive projected guidance (arXiv 2410.02416; cfg_apg_*, cfg_*_step*_apg_kernel).  Every step kernel has an unguided form
 // (GUIDED = false; for cfg_ddim_kernel the kernel ddim_kernel) for a step outside the guidance interval (arXiv 2404.07724): the model
 // ran the text half alone, the step takes that one prediction as m -- no second load stream, no guidance read, no combine -- and is
 // otherwise the same code.
@@ -540,6 +541,311 @@ __global__ __launch_bounds__(RS ? 256 : 1024) void cfg_multistep_step_windows_ke
     }
 }
 
+// ---- adaptive projected guidance (APG, arXiv 2410.02416, algorithm 1 without its momentum): the guidance difference is split into the
+//      part parallel to the text branch's denoised prediction and the rest, the parallel part is scaled by eta, and the difference may
+//      be clamped to a radius.  The paper works on x0; mapped back to the model's output the x0 conversion's factor on the prediction
+//      cancels and what the step takes in place of u + g (c - u) is
+//          d = c - u,   q = c + rho x,   rho = -1 / sb (epsilon), -sa / sb (v), 0 (sample)            (q: the x0 of c over that factor)
+//          alpha = sum d q / sum q^2,   s = min(1, r / (kp sqrt(sum d^2 / N))),   kp = sb / sa (epsilon), sb (v), 1 (sample)
+//          m = c + (g - 1) s d - lambda q,   lambda = (g - 1) s (1 - eta) alpha
+//      with the three sums over the whole tensor (the domain of the guidance rescale) and r an RMS in x0 units (+inf: no clamp).
+//      Two launches like the guidance rescale and with its record size, grid cap and workspace: a statistics pass leaves one record
+//      (count, sum d q, sum q^2, sum d^2) per workgroup, every workgroup of the step kernel merges all records in one fixed order.
+//      The sums are plain fp32 sums of products (d and q are differences of like-sized values: nothing to centre), one fma chain per
+//      thread, a shuffle tree per wave, the four waves in ascending order.  The step kernels are kernels of their own beside the RS
+//      instantiations, not a further template argument of those: the mangled names of the shipped instantiations (the launch ledgers
+//      and the profiles name them) and their code stay what they were.  There is no unguided form: there is no u.
+struct ApgSums {
+    float n, dq, qq, dd;
+};
+struct ApgScalars {
+    float alpha, s, gs, lam;         // gs = (g - 1) s
+};
+
+// a + b as one fp32 addition of exactly these two values (-ffast-math may otherwise reassociate a chain differently per kernel)
+__device__ __forceinline__ float add_kept(float a, float b) {
+    float s = a + b;
+    asm volatile("" : "+v"(s));
+    return s;
+}
+
+__device__ __forceinline__ float apg_rho(int pred, float sa, float sb) {
+    const float isb = 1.0f / sb;
+    return pred == 0 ? -isb : pred == 1 ? -sa * isb : 0.0f;
+}
+
+// d and q of one element, the same bits in the statistics pass and in the step, in the plain and in the windows kernels: the value
+// barriers keep a blend's division and rho out of the two operations
+__device__ __forceinline__ void apg_dq(float u, float c, float x, float rho, float& d, float& q) {
+    asm volatile("" : "+v"(u), "+v"(c));
+    d = c - u;
+    q = __fmaf_rn(rho, x, c);
+    asm volatile("" : "+v"(d), "+v"(q));
+}
+
+// a <- a + the cnt (1 .. 8) leading elements, in ascending order
+__device__ __forceinline__ void apg_add(ApgSums& a, const float* u, const float* c, const float* x, int cnt, float rho) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        if (e < cnt) {
+            float d, q;
+            apg_dq(u[e], c[e], x[e], rho, d, q);
+            a.dq = __fmaf_rn(d, q, a.dq);
+            a.qq = __fmaf_rn(q, q, a.qq);
+            a.dd = __fmaf_rn(d, d, a.dd);
+        }
+    }
+    a.n += (float)cnt;
+}
+
+// The sums of a workgroup of exactly 256 threads, valid in thread 0; order and `lds` (4 records) as in moments_block_reduce
+__device__ __forceinline__ ApgSums apg_block_reduce(ApgSums a, ApgSums* lds) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        a.n = add_kept(a.n, __shfl_down(a.n, o));
+        a.dq = add_kept(a.dq, __shfl_down(a.dq, o));
+        a.qq = add_kept(a.qq, __shfl_down(a.qq, o));
+        a.dd = add_kept(a.dd, __shfl_down(a.dd, o));
+    }
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = a;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        a = lds[0];
+        for (int w = 1; w < (int)(blockDim.x >> 6); ++w) {
+            a.n = add_kept(a.n, lds[w].n), a.dq = add_kept(a.dq, lds[w].dq);
+            a.qq = add_kept(a.qq, lds[w].qq), a.dd = add_kept(a.dd, lds[w].dd);
+        }
+    }
+    return a;
+}
+
+__device__ __forceinline__ void apg_store(float* __restrict__ ws, const ApgSums& a) {
+    float* rec = ws + (long)blockIdx.x * kRescaleRecord;
+    rec[0] = a.n, rec[1] = a.dq, rec[2] = a.qq, rec[3] = a.dd;
+}
+
+// (alpha, s, (g - 1) s, lambda) from the nrec records of a statistics pass, the same bits in every thread of every workgroup that
+// calls it.  One record per thread: nrec <= kRescaleMaxRecords = 256 = blockDim.x.  sum q^2 = 0: alpha = NaN, as the formula gives;
+// sum d^2 = 0 (u == c): s = 1 and lambda = 0, i.e. m = c.
+__device__ __forceinline__ ApgScalars apg_scalars(const float* ws, int nrec, float g, float sa, float sb, int pred, float eta, float r) {
+    __shared__ ApgSums lds[4];
+    __shared__ ApgScalars k_lds;
+    ApgSums a;
+    a.n = a.dq = a.qq = a.dd = 0.0f;
+    if ((int)threadIdx.x < nrec) {
+        const float* rec = ws + (long)threadIdx.x * kRescaleRecord;
+        a.n = rec[0], a.dq = rec[1], a.qq = rec[2], a.dd = rec[3];
+    }
+    a = apg_block_reduce(a, lds);
+    if (threadIdx.x == 0) {
+        const float kp = pred == 0 ? sb / sa : pred == 1 ? sb : 1.0f;
+        ApgScalars k;
+        k.alpha = a.dq / a.qq;
+        k.s = r < __builtin_inff() ? fminf(1.0f, r / (kp * sqrtf(a.dd / a.n))) : 1.0f;
+        k.gs = (g - 1.0f) * k.s;
+        k.lam = k.gs * (1.0f - eta) * k.alpha;
+        k_lds = k;
+    }
+    __syncthreads();
+    return k_lds;
+}
+
+// m of one element: two products and two additions of exactly these values (rescale_mul's pattern)
+__device__ __forceinline__ float apg_combine(float u, float c, float x, float rho, const ApgScalars& a) {
+    float d, q;
+    apg_dq(u, c, x, rho, d, q);
+    float p = a.gs * d;
+    asm volatile("" : "+v"(p));
+    float t = a.lam * q;
+    asm volatile("" : "+v"(t));
+    return add_kept(add_kept(c, p), -t);
+}
+
+// statistics pass over (u, c, x): n8 16-byte lanes, grid <= kRescaleMaxRecords, one record per workgroup
+template <typename T>
+__global__ __launch_bounds__(256) void cfg_apg_stats_kernel(const T* __restrict__ uncond, const T* __restrict__ cond, const T* __restrict__ x,
+                                                             long n8, float sa, float sb, int mode, const float* __restrict__ coef,
+                                                             float* __restrict__ ws) {
+    __shared__ ApgSums lds[4];
+    if (coef != nullptr) sa = coef[1], sb = coef[2];
+    const float rho = apg_rho(mode & 3, sa, sb);
+    ApgSums a;
+    a.n = a.dq = a.qq = a.dd = 0.0f;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
+        float u[8], c[8], s[8];
+        unpack8<T>(((const uint4*)uncond)[i], u);
+        unpack8<T>(((const uint4*)cond)[i], c);
+        unpack8<T>(((const uint4*)x)[i], s);
+        apg_add(a, u, c, s, 8, rho);
+    }
+    a = apg_block_reduce(a, lds);
+    if (threadIdx.x == 0) apg_store(ws, a);
+}
+
+// The same over the blends of the windows: u and c are windows_blend's blends of the two halves (guidance 0 makes its combined
+// prediction u + 0 (c - u) = u), x is [outer, F, inner].  Groups of 8 for either V as in cfg_rescale_stats_windows_kernel, so one
+// uniform window with L = F writes cfg_apg_stats_kernel's records.
+template <typename T, int V>
+__global__ __launch_bounds__(256) void cfg_apg_stats_windows_kernel(const T* __restrict__ pred, const T* __restrict__ x,
+                                                                     const int* __restrict__ start, const float* __restrict__ weight, int nW,
+                                                                     long outer, int F, int L, int wrap, long inner, float sa, float sb, int mode,
+                                                                     const float* __restrict__ coef, float* __restrict__ ws) {
+    __shared__ ApgSums lds[4];
+    if (coef != nullptr) sa = coef[1], sb = coef[2];
+    const float rho = apg_rho(mode & 3, sa, sb);
+    const long n = outer * F * inner, n8 = (n + 7) / 8;
+    const long half = outer * L * inner;
+    ApgSums a;
+    a.n = a.dq = a.qq = a.dd = 0.0f;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
+        float u[8], c[8], s[8];
+        int cnt = 8;
+        if (V == 8) {
+            windows_blend<T, 8, true>(pred, start, weight, nW, F, L, wrap, inner, half, i * 8, 0.0f, u, c);
+            unpack8<T>(((const uint4*)x)[i], s);
+        } else {
+            cnt = (int)(n - i * 8 < 8 ? n - i * 8 : 8);
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+                if (e < cnt) {
+                    windows_blend<T, 1, true>(pred, start, weight, nW, F, L, wrap, inner, half, i * 8 + e, 0.0f, &u[e], &c[e]);
+                    s[e] = to_f32<T>(x[i * 8 + e]);
+                }
+        }
+        apg_add(a, u, c, s, cnt, rho);
+    }
+    a = apg_block_reduce(a, lds);
+    if (threadIdx.x == 0) apg_store(ws, a);
+}
+
+// (alpha, s, lambda) alone, for tests and tools: one workgroup, the reduction every step workgroup makes
+__global__ __launch_bounds__(256) void cfg_apg_scalars_kernel(const float* __restrict__ ws, int nrec, float g, float sa, float sb, int mode,
+                                                               float eta, float r, const float* __restrict__ coef, float* __restrict__ out) {
+    if (coef != nullptr) g = coef[0], sa = coef[1], sb = coef[2];
+    const ApgScalars k = apg_scalars(ws, nrec, g, sa, sb, mode & 3, eta, r);
+    if (threadIdx.x == 0) out[0] = k.alpha, out[1] = k.s, out[2] = k.lam;
+}
+
+// cfg_ddim_step_kernel on the projected guidance m above instead of u + g (c - u)
+template <typename T>
+__global__ __launch_bounds__(256) void cfg_ddim_step_apg_kernel(const T* __restrict__ uncond, const T* __restrict__ cond, const T* __restrict__ x,
+                                     const T* __restrict__ noise, T* __restrict__ out, long n8, float g, float sa, float sb,
+                                     float sap, float dir, float sigma, int mode, const float* __restrict__ coef,
+                                     const float* __restrict__ ws, int nrec, float eta, float r) {
+    const DdimCoefs k = ddim_coefs<true>(g, sa, sb, sap, dir, sigma, mode, coef);
+    const ApgScalars a = apg_scalars(ws, nrec, k.g, k.sa, k.sb, k.pred, eta, r);
+    const float rho = apg_rho(k.pred, k.sa, k.sb);
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
+        float u[8], c[8], s[8], z[8];
+        unpack8<T>(((const uint4*)uncond)[i], u);
+        unpack8<T>(((const uint4*)cond)[i], c);
+        unpack8<T>(((const uint4*)x)[i], s);
+        if (noise != nullptr) unpack8<T>(((const uint4*)noise)[i], z);
+        else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) z[e] = 0.0f;
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) s[e] = ddim_step_elem(apg_combine(u[e], c[e], s[e], rho, a), s[e], z[e], k);
+        ((uint4*)out)[i] = pack8<T>(s);
+    }
+}
+
+// cfg_multistep_step_kernel on the projected guidance
+template <typename T>
+__global__ __launch_bounds__(256) void cfg_multistep_step_apg_kernel(const T* __restrict__ uncond, const T* __restrict__ cond, const T* __restrict__ x,
+                                     float* __restrict__ hist, T* __restrict__ out, long n8, float g, float sa, float sb, float cx,
+                                     float c0, float c1, int mode, const float* __restrict__ coef, const float* __restrict__ ws,
+                                     int nrec, float eta, float r) {
+    const MultistepCoefs k = multistep_coefs<true>(g, sa, sb, cx, c0, c1, mode, coef);
+    const ApgScalars a = apg_scalars(ws, nrec, k.g, k.sa, k.sb, k.pred, eta, r);
+    const float rho = apg_rho(k.pred, k.sa, k.sb);
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
+        float u[8], c[8], s[8], h[8];
+        unpack8<T>(((const uint4*)uncond)[i], u);
+        unpack8<T>(((const uint4*)cond)[i], c);
+        unpack8<T>(((const uint4*)x)[i], s);
+        if (k.hist) hist_load8(hist, i, h);
+        else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) h[e] = 0.0f;
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) s[e] = multistep_step_elem(apg_combine(u[e], c[e], s[e], rho, a), s[e], h[e], k);
+        hist_store8(hist, i, h);
+        ((uint4*)out)[i] = pack8<T>(s);
+    }
+}
+
+// cfg_ddim_step_windows_kernel on the projected guidance of the blends (u, c: as in cfg_apg_stats_windows_kernel)
+template <typename T, int V>
+__global__ __launch_bounds__(256) void cfg_ddim_step_windows_apg_kernel(const T* __restrict__ pred, const T* __restrict__ x, const T* __restrict__ noise,
+                                             T* __restrict__ out, const int* __restrict__ start, const float* __restrict__ weight,
+                                             int nW, long outer, int F, int L, int wrap, long inner, float g, float sa, float sb, float sap,
+                                             float dir, float sigma, int mode, const float* __restrict__ coef,
+                                             const float* __restrict__ ws, int nrec, float eta, float r) {
+    const DdimCoefs k = ddim_coefs<true>(g, sa, sb, sap, dir, sigma, mode, coef);
+    const ApgScalars a = apg_scalars(ws, nrec, k.g, k.sa, k.sb, k.pred, eta, r);
+    const float rho = apg_rho(k.pred, k.sa, k.sb);
+    const long nv = outer * F * inner / V;
+    const long half = outer * L * inner;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
+        float u[V], c[V], s[V], z[V];
+        windows_blend<T, V, true>(pred, start, weight, nW, F, L, wrap, inner, half, i * V, 0.0f, u, c);
+        if (V == 8) {
+            unpack8<T>(((const uint4*)x)[i], s);
+            if (noise != nullptr) unpack8<T>(((const uint4*)noise)[i], z);
+        } else {
+            s[0] = to_f32<T>(x[i]);
+            if (noise != nullptr) z[0] = to_f32<T>(noise[i]);
+        }
+        if (noise == nullptr) {
+#pragma unroll
+            for (int e = 0; e < V; ++e) z[e] = 0.0f;
+        }
+#pragma unroll
+        for (int e = 0; e < V; ++e) s[e] = ddim_step_elem(apg_combine(u[e], c[e], s[e], rho, a), s[e], z[e], k);
+        if (V == 8) ((uint4*)out)[i] = pack8<T>(s);
+        else out[i] = from_f32<T>(s[0]);
+    }
+}
+
+// cfg_multistep_step_windows_kernel on the projected guidance of the blends
+template <typename T, int V>
+__global__ __launch_bounds__(256) void cfg_multistep_step_windows_apg_kernel(const T* __restrict__ pred, const T* __restrict__ x, float* __restrict__ hist,
+                                             T* __restrict__ out, const int* __restrict__ start, const float* __restrict__ weight,
+                                             int nW, long outer, int F, int L, int wrap, long inner, float g, float sa, float sb, float cx,
+                                             float c0, float c1, int mode, const float* __restrict__ coef,
+                                             const float* __restrict__ ws, int nrec, float eta, float r) {
+    const MultistepCoefs k = multistep_coefs<true>(g, sa, sb, cx, c0, c1, mode, coef);
+    const ApgScalars a = apg_scalars(ws, nrec, k.g, k.sa, k.sb, k.pred, eta, r);
+    const float rho = apg_rho(k.pred, k.sa, k.sb);
+    const long nv = outer * F * inner / V;
+    const long half = outer * L * inner;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
+        float u[V], c[V], s[V], h[V];
+        windows_blend<T, V, true>(pred, start, weight, nW, F, L, wrap, inner, half, i * V, 0.0f, u, c);
+        if (V == 8) unpack8<T>(((const uint4*)x)[i], s);
+        else s[0] = to_f32<T>(x[i]);
+        if (k.hist) {
+            if (V == 8) hist_load8(hist, i, h);
+            else h[0] = hist[i];
+        } else {
+#pragma unroll
+            for (int e = 0; e < V; ++e) h[e] = 0.0f;
+        }
+#pragma unroll
+        for (int e = 0; e < V; ++e) s[e] = multistep_step_elem(apg_combine(u[e], c[e], s[e], rho, a), s[e], h[e], k);
+        if (V == 8) {
+            hist_store8(hist, i, h);
+            ((uint4*)out)[i] = pack8<T>(s);
+        } else {
+            hist[i] = h[0];
+            out[i] = from_f32<T>(s[0]);
+        }
+    }
+}
+
 }  // namespace im360
 
 // Records a statistics pass of the guidance rescale writes for n elements = its grid: one workgroup per 256 groups of 8 elements,
@@ -932,4 +1238,197 @@ extern "C" __attribute__((visibility("default"))) int im360_multistep_step_windo
     const im360::Windows w{pred, start, weight, nW, wrap == 0 ? 0 : (int)F, outer, F, L, inner};
     const im360::MultistepArgs a{im360::multistep_step_args(0.0f, sqrt_a, sqrt_b, mode, 0.0f, nullptr, 0, coef_dev), cx, c0, c1, hist};
     return im360::cfg_multistep_step_windows("multistep_step_windows", w, wrap, x, out, a, dtype, stream, false);
+}
+
+// ---- adaptive projected guidance: the statistics pass, the scalars, and the four guided steps on the projected guidance
+namespace im360 {
+// What an _apg entry point is given besides its sibling's arguments: eta (the share of the parallel part that is kept), the RMS radius r
+// of the clamp in x0 units (INFINITY: no clamp) and the workspace of records a statistics pass wrote for the same tensors
+struct ApgArgs {
+    float eta, r;
+    const void* ws;
+    int64_t ws_floats;
+};
+static int check_apg(const char* name, const ApgArgs& a, int64_t n) {
+    IM360_CHECK_ARG(std::isfinite(a.eta), "%s: apg eta=%g must be finite", name, (double)a.eta);
+    IM360_CHECK_ARG(a.r > 0.0f, "%s: apg threshold=%g must be > 0 (INFINITY: no clamp)", name, (double)a.r);          // (a NaN fails too)
+    return check_rescale_ws(name, a.ws, a.ws_floats, n);
+}
+// the mode bits of a statistics pass or of the scalars: only the prediction type is read, the whole word is held to the steps' range
+static int check_apg_mode(const char* name, int mode) {
+    IM360_CHECK_ARG(mode >= 0 && mode < 16 && (mode & 3) != 3, "%s: mode %d unsupported", name, mode);
+    return IM360_OK;
+}
+
+// im360_cfg_apg_stats_windows (w.wrap = 0) and im360_cfg_apg_stats_windows_ring (w.wrap = F): checks, then the launch
+static int cfg_apg_stats_windows(const char* name, const Windows& w, const void* x, float sa, float sb, int mode, void* ws, int64_t ws_floats,
+                                 int dtype, void* stream, const void* coef_dev) {
+    if (const int rc = check_windows(name, w, x != nullptr, nullptr)) return rc;
+    if (const int rc = check_apg_mode(name, mode)) return rc;
+    if (const int rc = check_rescale_ws(name, ws, ws_floats, w.elements())) return rc;
+    const bool vec = (w.inner % 8) == 0 && (((uintptr_t)w.pred | (uintptr_t)x) % 16) == 0;
+    const unsigned blocks = (unsigned)im360_cfg_rescale_records(w.elements());
+    return with_dtype(dtype, name, [&](auto t) {
+        using T = typename decltype(t)::type;
+        with_const<1, 8>(vec ? 8 : 1, [&](auto v) {
+            hipLaunchKernelGGL((cfg_apg_stats_windows_kernel<T, decltype(v)::value>), dim3(blocks), dim3(256), 0, (hipStream_t)stream,
+                               (const T*)w.pred, (const T*)x, (const int*)w.start, (const float*)w.weight, w.nW, (long)w.outer, (int)w.F, (int)w.L,
+                               w.wrap, (long)w.inner, sa, sb, mode, (const float*)coef_dev, (float*)ws);
+        });
+        return im360_launch_status();
+    });
+}
+
+// im360_cfg_ddim_step_windows_apg: the checks of cfg_ddim_step_windows, wrap, the APG arguments, then the launch
+static int cfg_ddim_step_windows_apg(const char* name, const Windows& w, int64_t wrap, const void* x, void* out, const StepArgs& s,
+                                     const ApgArgs& a, int dtype, void* stream) {
+    if (const int rc = check_windows(name, w, x && out, &s)) return rc;
+    IM360_CHECK_ARG(wrap == 0 || wrap == w.F, "%s: wrap=%ld must be 0 (line) or F=%ld (ring)", name, (long)wrap, (long)w.F);
+    if (const int rc = check_apg(name, a, w.elements())) return rc;
+    const bool vec = (w.inner % 8) == 0 && (((uintptr_t)w.pred | (uintptr_t)x | (uintptr_t)s.noise | (uintptr_t)out) % 16) == 0;
+    const long nv = (long)w.elements() / (vec ? 8 : 1);
+    const int nrec = (int)im360_cfg_rescale_records(w.elements());
+    return with_dtype(dtype, name, [&](auto t) {
+        using T = typename decltype(t)::type;
+        with_const<1, 8>(vec ? 8 : 1, [&](auto v) {
+            hipLaunchKernelGGL((cfg_ddim_step_windows_apg_kernel<T, decltype(v)::value>), dim3(step_blocks(nv)), dim3(256), 0,
+                               (hipStream_t)stream, (const T*)w.pred, (const T*)x, (const T*)s.noise, (T*)out, (const int*)w.start,
+                               (const float*)w.weight, w.nW, (long)w.outer, (int)w.F, (int)w.L, w.wrap, (long)w.inner, s.g, s.sa, s.sb, s.sap,
+                               s.dir, s.sigma, s.mode, (const float*)s.coef_dev, (const float*)a.ws, nrec, a.eta, a.r);
+        });
+        return im360_launch_status();
+    });
+}
+}  // namespace im360
+
+// partial sums of d q, q^2 and d^2 (d = cond - uncond, q = cond + rho x; see the kernels' comment) over n elements (n % 8 == 0) -> ws
+extern "C" __attribute__((visibility("default"))) int im360_cfg_apg_stats(const void* uncond, const void* cond, const void* x, int64_t n,
+                                   float sqrt_a, float sqrt_b, int mode, void* ws, int64_t ws_floats, int dtype, void* stream,
+                                   const void* coef_dev) {
+    using namespace im360;
+    if (const int rc = check_tensors("cfg_apg_stats", {uncond, cond, x}, nullptr, n)) return rc;
+    if (const int rc = check_apg_mode("cfg_apg_stats", mode)) return rc;
+    if (const int rc = check_rescale_ws("cfg_apg_stats", ws, ws_floats, n)) return rc;
+    const unsigned blocks = (unsigned)im360_cfg_rescale_records(n);
+    return with_dtype(dtype, "cfg_apg_stats", [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((cfg_apg_stats_kernel<T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const T*)uncond, (const T*)cond,
+                           (const T*)x, (long)(n / 8), sqrt_a, sqrt_b, mode, (const float*)coef_dev, (float*)ws);
+        return im360_launch_status();
+    });
+}
+
+// the same over the per-frame blends of nW sliding-window predictions (layout and tables of im360_cfg_ddim_step_windows)
+extern "C" __attribute__((visibility("default"))) int im360_cfg_apg_stats_windows(const void* pred, const void* x, const void* start,
+                                   const void* weight, int nW, int64_t outer, int64_t F, int64_t L, int64_t inner, float sqrt_a, float sqrt_b,
+                                   int mode, void* ws, int64_t ws_floats, int dtype, void* stream, const void* coef_dev) {
+    const im360::Windows w{pred, start, weight, nW, 0, outer, F, L, inner};
+    return im360::cfg_apg_stats_windows("cfg_apg_stats_windows", w, x, sqrt_a, sqrt_b, mode, ws, ws_floats, dtype, stream, coef_dev);
+}
+
+// the same with the windows on a ring of F frames (preconditions of im360_cfg_ddim_step_windows_ring)
+extern "C" __attribute__((visibility("default"))) int im360_cfg_apg_stats_windows_ring(const void* pred, const void* x, const void* start,
+                                   const void* weight, int nW, int64_t outer, int64_t F, int64_t L, int64_t inner, float sqrt_a, float sqrt_b,
+                                   int mode, void* ws, int64_t ws_floats, int dtype, void* stream, const void* coef_dev) {
+    const im360::Windows w{pred, start, weight, nW, (int)F, outer, F, L, inner};
+    return im360::cfg_apg_stats_windows("cfg_apg_stats_windows_ring", w, x, sqrt_a, sqrt_b, mode, ws, ws_floats, dtype, stream, coef_dev);
+}
+
+// out[0 .. 2] = (alpha, s, lambda) from the records a statistics pass over n elements left in ws
+extern "C" __attribute__((visibility("default"))) int im360_cfg_apg_scalars(const void* ws, int64_t ws_floats, int64_t n, float guidance,
+                                   float sqrt_a, float sqrt_b, int mode, float eta, float threshold, void* out, void* stream,
+                                   const void* coef_dev) {
+    using namespace im360;
+    IM360_CHECK_ARG(out && ((uintptr_t)out % 4) == 0 && n > 0, "cfg_apg_scalars: null or misaligned output / empty problem");
+    if (const int rc = check_apg_mode("cfg_apg_scalars", mode)) return rc;
+    if (const int rc = check_apg("cfg_apg_scalars", ApgArgs{eta, threshold, ws, ws_floats}, n)) return rc;
+    hipLaunchKernelGGL(cfg_apg_scalars_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)ws, (int)im360_cfg_rescale_records(n),
+                       guidance, sqrt_a, sqrt_b, mode, eta, threshold, (const float*)coef_dev, (float*)out);
+    return im360_launch_status();
+}
+
+// im360_cfg_ddim_step on the projected guidance m, its scalars from the records im360_cfg_apg_stats left in ws for the same tensors
+extern "C" __attribute__((visibility("default"))) int im360_cfg_ddim_step_apg(const void* uncond, const void* cond, const void* x, const void* noise,
+                                   void* out, int64_t n, float guidance, float sqrt_a, float sqrt_b, float sqrt_a_prev, float dir, float sigma,
+                                   int mode, float eta, float threshold, const void* ws, int64_t ws_floats, int dtype, void* stream,
+                                   const void* coef_dev) {
+    using namespace im360;
+    const char* name = "cfg_ddim_step_apg";
+    const StepArgs s{guidance, sqrt_a, sqrt_b, sqrt_a_prev, dir, sigma, mode, noise, coef_dev, nullptr, 0, 0.0f};
+    const ApgArgs a{eta, threshold, ws, ws_floats};
+    if (const int rc = check_tensors(name, {uncond, cond, x, out}, noise, n)) return rc;
+    if (const int rc = check_step(name, s)) return rc;
+    if (const int rc = check_apg(name, a, n)) return rc;
+    return with_dtype(dtype, name, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((cfg_ddim_step_apg_kernel<T>), dim3(step_blocks(n / 8)), dim3(256), 0, (hipStream_t)stream, (const T*)uncond,
+                           (const T*)cond, (const T*)x, (const T*)noise, (T*)out, (long)(n / 8), guidance, sqrt_a, sqrt_b, sqrt_a_prev, dir, sigma,
+                           mode, (const float*)coef_dev, (const float*)ws, (int)im360_cfg_rescale_records(n), eta, threshold);
+        return im360_launch_status();
+    });
+}
+
+// im360_cfg_ddim_step_windows (wrap = 0) / im360_cfg_ddim_step_windows_ring (wrap = F) on the projected guidance of the blends, its
+// scalars from the records im360_cfg_apg_stats_windows(_ring) left in ws for the same clip
+extern "C" __attribute__((visibility("default"))) int im360_cfg_ddim_step_windows_apg(const void* pred, const void* x, const void* noise,
+                                   void* out, const void* start, const void* weight, int nW, int64_t outer, int64_t F, int64_t L, int64_t inner,
+                                   int64_t wrap, float guidance, float sqrt_a, float sqrt_b, float sqrt_a_prev, float dir, float sigma, int mode,
+                                   float eta, float threshold, const void* ws, int64_t ws_floats, int dtype, void* stream,
+                                   const void* coef_dev) {
+    const im360::Windows w{pred, start, weight, nW, wrap == 0 ? 0 : (int)F, outer, F, L, inner};
+    const im360::StepArgs s{guidance, sqrt_a, sqrt_b, sqrt_a_prev, dir, sigma, mode, noise, coef_dev, nullptr, 0, 0.0f};
+    return im360::cfg_ddim_step_windows_apg("cfg_ddim_step_windows_apg", w, wrap, x, out, s, im360::ApgArgs{eta, threshold, ws, ws_floats}, dtype,
+                                            stream);
+}
+
+// im360_cfg_multistep_step on the projected guidance (hist <- its x0)
+extern "C" __attribute__((visibility("default"))) int im360_cfg_multistep_step_apg(const void* uncond, const void* cond, const void* x, void* hist,
+                                   void* out, int64_t n, float guidance, float sqrt_a, float sqrt_b, float cx, float c0, float c1, int mode,
+                                   float eta, float threshold, const void* ws, int64_t ws_floats, int dtype, void* stream,
+                                   const void* coef_dev) {
+    using namespace im360;
+    const char* name = "cfg_multistep_step_apg";
+    const MultistepArgs m{multistep_step_args(guidance, sqrt_a, sqrt_b, mode, 0.0f, nullptr, 0, coef_dev), cx, c0, c1, hist};
+    const ApgArgs a{eta, threshold, ws, ws_floats};
+    if (const int rc = check_tensors(name, {uncond, cond, x, hist, out}, nullptr, n)) return rc;
+    if (const int rc = check_step(name, m.s)) return rc;
+    if (const int rc = check_multistep(name, m, n)) return rc;
+    if (const int rc = check_apg(name, a, n)) return rc;
+    return with_dtype(dtype, name, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((cfg_multistep_step_apg_kernel<T>), dim3(step_blocks(n / 8)), dim3(256), 0, (hipStream_t)stream, (const T*)uncond,
+                           (const T*)cond, (const T*)x, (float*)hist, (T*)out, (long)(n / 8), guidance, sqrt_a, sqrt_b, cx, c0, c1, mode,
+                           (const float*)coef_dev, (const float*)ws, (int)im360_cfg_rescale_records(n), eta, threshold);
+        return im360_launch_status();
+    });
+}
+
+// im360_cfg_multistep_step_windows on the projected guidance of the blends; wrap = 0 or F
+extern "C" __attribute__((visibility("default"))) int im360_cfg_multistep_step_windows_apg(const void* pred, const void* x, void* hist, void* out,
+                                   const void* start, const void* weight, int nW, int64_t outer, int64_t F, int64_t L, int64_t inner, int64_t wrap,
+                                   float guidance, float sqrt_a, float sqrt_b, float cx, float c0, float c1, int mode, float eta, float threshold,
+                                   const void* ws, int64_t ws_floats, int dtype, void* stream, const void* coef_dev) {
+    using namespace im360;
+    const char* name = "cfg_multistep_step_windows_apg";
+    const Windows w{pred, start, weight, nW, wrap == 0 ? 0 : (int)F, outer, F, L, inner};
+    const MultistepArgs m{multistep_step_args(guidance, sqrt_a, sqrt_b, mode, 0.0f, nullptr, 0, coef_dev), cx, c0, c1, hist};
+    const ApgArgs a{eta, threshold, ws, ws_floats};
+    if (const int rc = check_windows(name, w, x && hist && out, &m.s)) return rc;
+    IM360_CHECK_ARG(wrap == 0 || wrap == F, "%s: wrap=%ld must be 0 (line) or F=%ld (ring)", name, (long)wrap, (long)F);
+    IM360_CHECK_ARG(((uintptr_t)hist % 4) == 0, "%s: misaligned history", name);
+    if (const int rc = check_multistep(name, m, w.elements())) return rc;
+    if (const int rc = check_apg(name, a, w.elements())) return rc;
+    const bool vec = (inner % 8) == 0 && (((uintptr_t)pred | (uintptr_t)x | (uintptr_t)hist | (uintptr_t)out) % 16) == 0;
+    const long nv = (long)w.elements() / (vec ? 8 : 1);
+    const int nrec = (int)im360_cfg_rescale_records(w.elements());
+    return with_dtype(dtype, name, [&](auto t) {
+        using T = typename decltype(t)::type;
+        with_const<1, 8>(vec ? 8 : 1, [&](auto v) {
+            hipLaunchKernelGGL((cfg_multistep_step_windows_apg_kernel<T, decltype(v)::value>), dim3(step_blocks(nv)), dim3(256), 0,
+                               (hipStream_t)stream, (const T*)pred, (const T*)x, (float*)hist, (T*)out, (const int*)start, (const float*)weight, nW,
+                               (long)outer, (int)F, (int)L, w.wrap, (long)inner, guidance, sqrt_a, sqrt_b, cx, c0, c1, mode,
+                               (const float*)coef_dev, (const float*)ws, nrec, eta, threshold);
+        });
+        return im360_launch_status();
+    });
 }

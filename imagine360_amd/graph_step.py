@@ -9,6 +9,8 @@ sampling (eta > 0) draws the two variance noises inside the graph as well, right
 caller's generator (registered with the graph) or the default one; the coefficients are then (guidance, sqrt a_t,
 sqrt b_t, sqrt a_prev, dir, sigma) for ``cfg_ddim_step``.  Guidance rescale (``guidance_rescale`` != 0) adds one captured
 statistics launch in front of each branch's step launch; its workspace is a graph-pool tensor and nothing more is uploaded.
+Adaptive projected guidance (``guidance_apg``) is captured the same way: its statistics launch and its step launch per branch read
+sqrt a_t, sqrt b_t and the guidance from the six uploaded coefficients; only the guided graph of a guidance interval holds them.
 A partly regenerated clip (``keep``, pipeline ``regenerate_mask``) adds one captured ``keep_latents`` launch after the two step launches;
 its two coefficients are a fifth tiny buffer, refreshed per step through a pinned ring of its own.  A release-mode region
 (``regenerate_mode="release"``) captures ``keep_latents_release`` in its place and uploads three: the step's threshold rides along.
@@ -49,7 +51,7 @@ class GraphedDenoiseStep:
 
     def __init__(self, mv, scheduler, inputs, cameras, pano_latent, pers_latent, guidance, use_fps=True, warmup=2, cfg_pair=None,
                  eta=0.0, generator=None, use_clipped_model_output=False, frame_shard=None, guidance_rescale=0.0, keep=None,
-                 guidance_interval=None, steps=None):
+                 guidance_interval=None, steps=None, guidance_apg=None):
         """``inputs``: the keyword tensors of MultiViewBaseModel.forward (CFG-batched, resident on the GPU);
         ``pano_latent`` [1,4,F,H,W] / ``pers_latent`` [1,m,4,F,h,w]: initial noisy latents.
         Frame-sharded models (``mv.set_frame_shard``) capture their all-to-alls with the step: the exchange buffers are
@@ -58,7 +60,7 @@ class GraphedDenoiseStep:
         inside the captured step before the CFG combine.
         ``eta`` / ``generator`` / ``use_clipped_model_output``: DDIMScheduler.step's keywords (defaults: the eta = 0 update).
         ``frame_shard`` (dist.FrameShard): with eta > 0 the variance noise is drawn for the whole clip and cut to the local
-        frames, like the initial noise.  ``guidance_rescale``: ``DDIMScheduler.fused_cfg_step``'s keyword.
+        frames, like the initial noise.  ``guidance_rescale`` / ``guidance_apg``: ``DDIMScheduler.fused_cfg_step``'s keywords.
         ``keep`` (pipeline.KeepRegion): the kept region of a given clip, blended into both latents after the two updates.
         ``guidance_interval`` (None: every step guided, one graph, nothing else runs) with ``steps``, the run's timestep list: the kinds
         of step the run holds (``scheduler.guided_steps``) are each warmed up and captured once.  The caller keeps
@@ -67,6 +69,9 @@ class GraphedDenoiseStep:
         self.cfg_pair = cfg_pair
         self.eta, self.gen, self.clipped, self.shard = float(eta), generator, bool(use_clipped_model_output), frame_shard
         self.rescale = float(guidance_rescale)
+        self.apg = guidance_apg
+        if guidance_apg is not None and frame_shard is not None:
+            raise ValueError("guidance_apg cannot be combined with frame_shard (its sums span all frames)")
         self.interval = guidance_interval
         kinds = [True]                           # True: the CFG-batch body, False: the text-half body
         if guidance_interval is not None:
@@ -78,7 +83,7 @@ class GraphedDenoiseStep:
             if False in kinds:
                 from .dist import cfg_half_inputs
                 self.inp_text = cfg_half_inputs(inputs, 1)       # views, made once: the IP-token cache keys on their identity
-        self.step_kernel = self.always_step_kernel or scheduler.uses_step_kernel(self.eta, self.clipped, self.rescale)
+        self.step_kernel = self.always_step_kernel or scheduler.uses_step_kernel(self.eta, self.clipped, self.rescale, **self._apg_kw())
         dev = pano_latent.device
         # private copies: the caller's tensors may alias the model-input buffers the body writes into
         init_pano, init_pers = pano_latent.clone(), pers_latent.clone()
@@ -165,7 +170,7 @@ class GraphedDenoiseStep:
         self.pred_pano, self.pred_pers = pred_pano, pred_pers          # static graph-pool tensors (inspection / tests)
         ldt, mdt = self.pano_lat.dtype, pred_pano.dtype    # latents may be kept in another 16-bit type than the model (the reference promotes)
         pred_pano, pred_pers = pred_pano.to(ldt), pred_pers.to(ldt)
-        kw = dict(eta=self.eta, use_clipped_model_output=self.clipped, guidance_rescale=self.rescale)
+        kw = dict(eta=self.eta, use_clipped_model_output=self.clipped, guidance_rescale=self.rescale, **self._apg_kw())
         new_pano = self.sch.fused_cfg_step(pred_pano[0:1], pred_pano[1:2], self.g, None, self.pano_lat, coef_dev=self.coef,
                                            noise=self._noise(self.pano_lat, mdt, 2), **kw, **self._history(0))
         new_pers = self.sch.fused_cfg_step(pred_pers[0:1], pred_pers[1:2], self.g, None, self.pers_lat, coef_dev=self.coef,
@@ -196,7 +201,7 @@ class GraphedDenoiseStep:
             self.mv.coins_preloaded, self.mv._ip_noise_half = was, was_half
         self.pred_pano_text, self.pred_pers_text = pred_pano, pred_pers          # static graph-pool tensors (inspection / tests)
         ldt, mdt = self.pano_lat.dtype, pred_pano.dtype
-        kw = dict(eta=self.eta, use_clipped_model_output=self.clipped, guidance_rescale=self.rescale)
+        kw = dict(eta=self.eta, use_clipped_model_output=self.clipped, guidance_rescale=self.rescale, **self._apg_kw())
         new_pano = self.sch.fused_step(pred_pano.to(ldt), None, self.pano_lat, coef_dev=self.coef, noise=self._noise(self.pano_lat, mdt, 2),
                                        **kw, **self._history(0))
         new_pers = self.sch.fused_step(pred_pers.to(ldt), None, self.pers_lat, coef_dev=self.coef, noise=self._noise(self.pers_lat, mdt, 3),
@@ -210,6 +215,10 @@ class GraphedDenoiseStep:
         if self.interval is None:
             return self.graph
         return self.graphs[self.sch.guided_steps([t_host], self.interval)[0]]
+
+    def _apg_kw(self):
+        """``guidance_apg=`` of the scheduler calls, left out when it is off: they are then made with exactly the keywords of before."""
+        return {} if self.apg is None else dict(guidance_apg=self.apg)
 
     def _history(self, branch):
         """``history=`` of one branch's step call (0 panorama, 1 perspective); nothing with a scheduler that keeps none."""
@@ -269,7 +278,8 @@ class GraphedWindowedStep(GraphedDenoiseStep):
     always_step_kernel = True
 
     def __init__(self, mv, scheduler, inputs, cameras, pano_latent, pers_latent, guidance, plan, use_fps=True, warmup=1, eta=0.0,
-                 generator=None, use_clipped_model_output=False, guidance_rescale=0.0, keep=None, guidance_interval=None, steps=None):
+                 generator=None, use_clipped_model_output=False, guidance_rescale=0.0, keep=None, guidance_interval=None, steps=None,
+                 guidance_apg=None):
         dev = pano_latent.device
         self.plan = plan
         self.static = plan.static_inputs(inputs)
@@ -284,7 +294,7 @@ class GraphedWindowedStep(GraphedDenoiseStep):
         self._up_k = _PinnedUploads(self.coins)
         super().__init__(mv, scheduler, inputs, cameras, pano_latent, pers_latent, guidance, use_fps=use_fps, warmup=warmup, eta=eta,
                          generator=generator, use_clipped_model_output=use_clipped_model_output, guidance_rescale=guidance_rescale, keep=keep,
-                         guidance_interval=guidance_interval, steps=steps)
+                         guidance_interval=guidance_interval, steps=steps, guidance_apg=guidance_apg)
 
     def _body_text(self):
         inp = self.inp_text
@@ -299,7 +309,7 @@ class GraphedWindowedStep(GraphedDenoiseStep):
             self.mv._ip_noise_half = was_half
         mdt = self.mv.unet.dtype
         kw = dict(coef_dev=self.coef, eta=self.eta, use_clipped_model_output=self.clipped, guidance_rescale=self.rescale,
-                  ring=self.plan.loop)
+                  ring=self.plan.loop, **self._apg_kw())
         new_pano = self.sch.fused_step_windows(self.preds_pano_text, self.plan.starts_dev, self.plan.weights, None, self.pano_lat,
                                                noise=self._noise(self.pano_lat, mdt, 2), **kw, **self._history(0))
         new_pers = self.sch.fused_step_windows(self.preds_pers_text, self.plan.starts_dev, self.plan.weights, None, self.pers_lat,
@@ -316,7 +326,7 @@ class GraphedWindowedStep(GraphedDenoiseStep):
                           coins=self.coins)
         mdt = self.mv.unet.dtype
         kw = dict(coef_dev=self.coef, eta=self.eta, use_clipped_model_output=self.clipped, guidance_rescale=self.rescale,
-                  ring=self.plan.loop)
+                  ring=self.plan.loop, **self._apg_kw())
         new_pano = self.sch.fused_cfg_step_windows(self.preds_pano, self.plan.starts_dev, self.plan.weights, self.g, None,
                                                    self.pano_lat, noise=self._noise(self.pano_lat, mdt, 2), **kw, **self._history(0))
         new_pers = self.sch.fused_cfg_step_windows(self.preds_pers, self.plan.starts_dev, self.plan.weights, self.g, None,

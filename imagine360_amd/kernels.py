@@ -73,6 +73,16 @@ _SIGNATURES = {
     "im360_ddim_step_windows_ring": (_INT, [_PTR] * 6 + [_INT] + [_I64] * 4 + [_F32] * 5 + [_INT, _INT, _PTR, _PTR]),
     "im360_multistep_step": (_INT, [_PTR] * 4 + [_I64] + [_F32] * 5 + [_INT, _INT, _PTR, _PTR]),
     "im360_multistep_step_windows": (_INT, [_PTR] * 6 + [_INT] + [_I64] * 5 + [_F32] * 5 + [_INT, _INT, _PTR, _PTR]),
+    "im360_cfg_apg_stats": (_INT, [_PTR] * 3 + [_I64, _F32, _F32, _INT, _PTR, _I64, _INT, _PTR, _PTR]),
+    "im360_cfg_apg_stats_windows": (_INT, [_PTR] * 4 + [_INT] + [_I64] * 4 + [_F32, _F32, _INT, _PTR, _I64, _INT, _PTR, _PTR]),
+    "im360_cfg_apg_stats_windows_ring": (_INT, [_PTR] * 4 + [_INT] + [_I64] * 4 + [_F32, _F32, _INT, _PTR, _I64, _INT, _PTR, _PTR]),
+    "im360_cfg_apg_scalars": (_INT, [_PTR, _I64, _I64] + [_F32] * 3 + [_INT, _F32, _F32, _PTR, _PTR, _PTR]),
+    "im360_cfg_ddim_step_apg": (_INT, [_PTR] * 5 + [_I64] + [_F32] * 6 + [_INT, _F32, _F32, _PTR, _I64, _INT, _PTR, _PTR]),
+    "im360_cfg_ddim_step_windows_apg": (_INT, [_PTR] * 6 + [_INT] + [_I64] * 5 + [_F32] * 6 + [_INT, _F32, _F32, _PTR, _I64, _INT, _PTR,
+                                                                                              _PTR]),
+    "im360_cfg_multistep_step_apg": (_INT, [_PTR] * 5 + [_I64] + [_F32] * 6 + [_INT, _F32, _F32, _PTR, _I64, _INT, _PTR, _PTR]),
+    "im360_cfg_multistep_step_windows_apg": (_INT, [_PTR] * 6 + [_INT] + [_I64] * 5 + [_F32] * 6 + [_INT, _F32, _F32, _PTR, _I64, _INT,
+                                                                                                   _PTR, _PTR]),
     "im360_noise_latents": (_INT, [_PTR] * 6 + [_I64] * 5 + [_F32, _F32, _INT, _PTR]),
     "im360_keep_latents": (_INT, [_PTR] * 7 + [_I64] * 5 + [_F32, _F32, _INT, _PTR, _PTR]),
     "im360_keep_latents_release": (_INT, [_PTR] * 7 + [_I64] * 5 + [_F32, _F32, _F32, _INT, _PTR, _PTR]),
@@ -993,6 +1003,61 @@ def cfg_rescale_factor(uncond, cond, guidance, rescale, coef_dev=None):
     return _rescale_factor(_rescale_stats(uncond, cond, guidance, coef_dev), cond, rescale)
 
 
+def _apg_args(who, apg, rescale=0.0):
+    """``apg = (eta, threshold)`` of the step wrappers as the two floats of the ``_apg`` entry points: ``threshold`` None (no clamp)
+    becomes +inf.  Refused: a non-finite ``eta``, a ``threshold`` that is not > 0, and ``rescale`` != 0 beside it (the two address the
+    same defect; the product of the kernel variants is not built)."""
+    if rescale != 0.0:
+        raise ValueError(f"{who}: apg and rescale={rescale} cannot be combined")
+    eta, threshold = apg
+    eta, threshold = float(eta), math.inf if threshold is None else float(threshold)
+    if not math.isfinite(eta):
+        raise ValueError(f"{who}: apg eta={eta} must be finite")
+    if not threshold > 0.0:
+        raise ValueError(f"{who}: apg threshold={threshold} must be > 0 (None: no clamp)")
+    return eta, threshold
+
+
+def _apg_stats(uncond, cond, sample, mode, coefs, coef_dev):
+    ws = _rescale_workspace(sample)
+    rc = lib().im360_cfg_apg_stats(_p(uncond), _p(cond), _p(sample), sample.numel(), float(coefs[1]), float(coefs[2]), int(mode), _p(ws),
+                                   ws.numel(), _dt(sample), _stream(), _p(coef_dev))
+    _check(rc, "im360_cfg_apg_stats")
+    return ws
+
+
+def _apg_stats_windows(preds, sample, starts, weights, geometry, mode, coefs, coef_dev, ring):
+    ws = _rescale_workspace(sample)
+    name = "im360_cfg_apg_stats_windows_ring" if ring else "im360_cfg_apg_stats_windows"
+    rc = getattr(lib(), name)(_p(preds), _p(sample), _p(starts), _p(weights), *geometry, float(coefs[1]), float(coefs[2]), int(mode), _p(ws),
+                              ws.numel(), _dt(sample), _stream(), _p(coef_dev))
+    _check(rc, name)
+    return ws
+
+
+def _apg_scalars(ws, like, mode, coefs, apg, coef_dev):
+    """(alpha, s, lambda) from the records ``ws`` of a statistics pass over ``like``: a device float32[3]."""
+    eta, threshold = _apg_args("cfg_apg_scalars", apg)
+    out = torch.empty(3, dtype=torch.float32, device=like.device)
+    rc = lib().im360_cfg_apg_scalars(_p(ws), ws.numel(), like.numel(), *(float(v) for v in coefs[:3]), int(mode), eta, threshold, _p(out),
+                                     _stream(), _p(coef_dev))
+    _check(rc, "im360_cfg_apg_scalars")
+    return out
+
+
+def cfg_apg_scalars(uncond, cond, sample, mode, coefs, apg, coef_dev=None):
+    """The three scalars of adaptive projected guidance (arXiv 2410.02416; ``cfg_ddim_step(..., apg=)``) as a device float32[3], no
+    synchronisation: ``alpha = <d, q> / <q, q>``, the clamp factor ``s`` and ``lambda = (g - 1) s (1 - eta) alpha`` with d = cond -
+    uncond and q = cond + rho * sample, the sums over the whole tensor in fp32.  Two launches: the statistics pass the step wrappers
+    run, then the merge of its records that every workgroup of the step kernel makes -- the bits the step uses.  ``mode`` / ``coefs``:
+    those of the step (only the prediction type and the first three coefficients are read); ``apg = (eta, threshold)``;
+    ``coef_dev``: device float32[6] whose first three elements are read instead."""
+    _dev(uncond, cond, sample, coef_dev)
+    assert uncond.is_contiguous() and cond.is_contiguous() and sample.is_contiguous()
+    assert uncond.shape == cond.shape == sample.shape and uncond.dtype == cond.dtype == sample.dtype
+    return _apg_scalars(_apg_stats(uncond, cond, sample, mode, coefs, coef_dev), sample, mode, coefs, apg, coef_dev)
+
+
 def _check_step_noise(who, sample, noise, coefs, coef_dev):
     """``noise`` like ``sample`` or None (refused with sigma > 0), ``coef_dev`` a device float32[6] or None: the step wrappers' rule."""
     if noise is not None:
@@ -1003,19 +1068,31 @@ def _check_step_noise(who, sample, noise, coefs, coef_dev):
         assert coef_dev.dtype == torch.float32 and coef_dev.numel() == 6 and coef_dev.is_cuda
 
 
-def cfg_ddim_step(uncond, cond, sample, noise, mode, coefs, coef_dev=None, rescale=0.0):
+def cfg_ddim_step(uncond, cond, sample, noise, mode, coefs, coef_dev=None, rescale=0.0, apg=None):
     """DDIMScheduler.step(uncond + g (cond - uncond), t, sample) for any prediction type / clip / eta in one pass.
     ``mode``: DDIM_PRED_MODE | DDIM_CLIP_SAMPLE | DDIM_CLIPPED_OUTPUT; ``coefs`` = (guidance, sqrt_a, sqrt_b, sqrt_a_prev,
     dir, sigma) (DDIMScheduler.step_coefficients); ``noise``: variance noise like ``sample`` or None (zero noise, refused
     with sigma > 0); ``coef_dev`` = device float32[6] holding ``coefs``, read by the kernel instead (graph replay).
     ``rescale`` != 0: guidance rescale (arXiv 2305.08891, 3.4) -- the step sees r (uncond + g (cond - uncond)) with
     r = rescale * std(cond) / std(uncond + g (cond - uncond)) + (1 - rescale) over the whole tensor; a statistics launch in front of
-    the step launch, no host read.  0 is the single launch without it."""
+    the step launch, no host read.  0 is the single launch without it.
+    ``apg = (eta, threshold)``: adaptive projected guidance (arXiv 2410.02416, algorithm 1 without momentum) -- the step sees
+    ``cond + (g - 1) s d - lambda q`` (``cfg_apg_scalars``) in place of the combination: the guidance difference split along the text
+    branch's denoised prediction, its parallel part scaled by ``eta``, its RMS in x0 units clamped to ``threshold`` (None: no clamp);
+    a statistics launch over (uncond, cond, sample) in front of the step launch.  None is the call without it; refused together with
+    ``rescale`` != 0."""
     _dev(uncond, cond, sample, noise)
     assert uncond.is_contiguous() and cond.is_contiguous() and sample.is_contiguous()
     assert uncond.shape == cond.shape == sample.shape and uncond.dtype == cond.dtype == sample.dtype
     _check_step_noise("cfg_ddim_step", sample, noise, coefs, coef_dev)
     out = torch.empty(sample.shape, dtype=sample.dtype, device=sample.device)
+    if apg is not None:
+        eta, threshold = _apg_args("cfg_ddim_step", apg, rescale)
+        ws = _apg_stats(uncond, cond, sample, mode, coefs, coef_dev)
+        rc = lib().im360_cfg_ddim_step_apg(_p(uncond), _p(cond), _p(sample), _p(noise), _p(out), sample.numel(), *(float(v) for v in coefs),
+                                           int(mode), eta, threshold, _p(ws), ws.numel(), _dt(sample), _stream(), _p(coef_dev))
+        _check(rc, "im360_cfg_ddim_step_apg")
+        return out
     if rescale != 0.0:
         ws = _rescale_stats(uncond, cond, coefs[0], coef_dev)
         rc = lib().im360_cfg_ddim_step_rescale(_p(uncond), _p(cond), _p(sample), _p(noise), _p(out), sample.numel(),
@@ -1061,7 +1138,17 @@ def cfg_rescale_factor_windows(preds, sample, starts, weights, guidance, rescale
     return _rescale_factor(_rescale_stats_windows(preds, sample, starts, weights, geometry, guidance, coef_dev, ring), sample, rescale)
 
 
-def cfg_ddim_step_windows(preds, sample, noise, starts, weights, mode, coefs, coef_dev=None, rescale=0.0, ring=False):
+def cfg_apg_scalars_windows(preds, sample, starts, weights, mode, coefs, apg, coef_dev=None, ring=False):
+    """``cfg_apg_scalars`` over the per-frame blends of sliding-window predictions (arguments of ``cfg_ddim_step_windows``): the
+    statistics pass ``cfg_ddim_step_windows(..., apg=)`` runs over the blends of both halves and ``sample``, then the merge every
+    workgroup of its step kernel makes.  A device float32[3], no synchronisation.  ``ring``: the windows lie on a ring."""
+    _dev(preds, sample, starts, weights, coef_dev)
+    geometry = _windows_geometry(preds, sample, starts, weights)
+    return _apg_scalars(_apg_stats_windows(preds, sample, starts, weights, geometry, mode, coefs, coef_dev, ring), sample, mode, coefs, apg,
+                        coef_dev)
+
+
+def cfg_ddim_step_windows(preds, sample, noise, starts, weights, mode, coefs, coef_dev=None, rescale=0.0, ring=False, apg=None):
     """``cfg_ddim_step`` on the per-frame weighted blend of sliding-window predictions, one pass.  ``sample`` (and ``noise`` /
     the result): a panorama latent [1, 4, F, H, W] or a perspective latent [1, m, 4, F, h, w];  ``preds`` [nW, 2, *sample.shape
     with F -> L]: window k's CFG-batched prediction in slot k;  ``starts`` device int32 [nW] ascending window start frames
@@ -1069,11 +1156,20 @@ def cfg_ddim_step_windows(preds, sample, noise, starts, weights, mode, coefs, co
     ``cfg_ddim_step``.  ``rescale`` != 0: guidance rescale with both standard deviations over the whole clip of blends (the text
     halves blended with the same weights), a statistics launch in front of the step launch.  ``ring``: the windows lie on a ring
     of F frames (context.context_windows(loop=True)) -- window k covers the frames (starts[k] + j) mod F, 0 <= starts[k] < F; the
-    ``_ring`` entry points, the same blend and step."""
+    ``_ring`` entry points, the same blend and step.  ``apg = (eta, threshold)``: adaptive projected guidance as in ``cfg_ddim_step``
+    on the blends of the two halves, the sums over the whole clip."""
     _dev(preds, sample, noise, starts, weights)
     nW, outer, F, L, inner = geometry = _windows_geometry(preds, sample, starts, weights)
     _check_step_noise("cfg_ddim_step_windows", sample, noise, coefs, coef_dev)
     out = torch.empty(sample.shape, dtype=sample.dtype, device=sample.device)
+    if apg is not None:
+        eta, threshold = _apg_args("cfg_ddim_step_windows", apg, rescale)
+        ws = _apg_stats_windows(preds, sample, starts, weights, geometry, mode, coefs, coef_dev, ring)
+        rc = lib().im360_cfg_ddim_step_windows_apg(_p(preds), _p(sample), _p(noise), _p(out), _p(starts), _p(weights), nW, outer, F, L, inner,
+                                                   F if ring else 0, *(float(v) for v in coefs), int(mode), eta, threshold, _p(ws), ws.numel(),
+                                                   _dt(sample), _stream(), _p(coef_dev))
+        _check(rc, "im360_cfg_ddim_step_windows_apg")
+        return out
     if rescale != 0.0:
         ws = _rescale_stats_windows(preds, sample, starts, weights, geometry, coefs[0], coef_dev, ring)
         name = "im360_cfg_ddim_step_windows_ring_rescale" if ring else "im360_cfg_ddim_step_windows_rescale"
@@ -1101,18 +1197,26 @@ def _check_multistep(who, sample, hist, mode, coefs, coef_dev):
         assert coef_dev.dtype == torch.float32 and coef_dev.numel() == 6 and coef_dev.is_cuda
 
 
-def cfg_multistep_step(uncond, cond, sample, hist, mode, coefs, coef_dev=None, rescale=0.0):
+def cfg_multistep_step(uncond, cond, sample, hist, mode, coefs, coef_dev=None, rescale=0.0, apg=None):
     """The DPM-Solver++ 2M update (arXiv 2211.01095, algorithm 2) of ``sample`` on uncond + g (cond - uncond), one pass:
     ``cx * sample + c0 * x0 + c1 * hist`` with x0 the prediction-type conversion (and clamp) of ``cfg_ddim_step``; ``hist`` (float32,
     like ``sample``) then holds x0, written in place, and is not read when c1 == 0.  ``mode``: DDIM_PRED_MODE | DDIM_CLIP_SAMPLE;
     ``coefs`` = (guidance, sqrt_a, sqrt_b, cx, c0, c1) (DPMSolverMultistepScheduler.multistep_coefficients); ``coef_dev`` = device
     float32[6] holding them, read by the kernel instead (graph replay).  ``rescale`` != 0: guidance rescale, the statistics launch of
-    ``cfg_ddim_step`` in front of the step launch."""
+    ``cfg_ddim_step`` in front of the step launch.  ``apg = (eta, threshold)``: adaptive projected guidance as in ``cfg_ddim_step``;
+    ``hist`` then holds the x0 of the projected guidance."""
     _dev(uncond, cond, sample, hist)
     assert uncond.is_contiguous() and cond.is_contiguous() and sample.is_contiguous()
     assert uncond.shape == cond.shape == sample.shape and uncond.dtype == cond.dtype == sample.dtype
     _check_multistep("cfg_multistep_step", sample, hist, mode, coefs, coef_dev)
     out = torch.empty(sample.shape, dtype=sample.dtype, device=sample.device)
+    if apg is not None:
+        eta, threshold = _apg_args("cfg_multistep_step", apg, rescale)
+        ws = _apg_stats(uncond, cond, sample, mode, coefs, coef_dev)
+        rc = lib().im360_cfg_multistep_step_apg(_p(uncond), _p(cond), _p(sample), _p(hist), _p(out), sample.numel(), *(float(v) for v in coefs),
+                                                int(mode), eta, threshold, _p(ws), ws.numel(), _dt(sample), _stream(), _p(coef_dev))
+        _check(rc, "im360_cfg_multistep_step_apg")
+        return out
     ws = _rescale_stats(uncond, cond, coefs[0], coef_dev) if rescale != 0.0 else None
     rc = lib().im360_cfg_multistep_step(_p(uncond), _p(cond), _p(sample), _p(hist), _p(out), sample.numel(), *(float(v) for v in coefs),
                                         int(mode), float(rescale), _p(ws), 0 if ws is None else ws.numel(), _dt(sample), _stream(),
@@ -1121,14 +1225,22 @@ def cfg_multistep_step(uncond, cond, sample, hist, mode, coefs, coef_dev=None, r
     return out
 
 
-def cfg_multistep_step_windows(preds, sample, hist, starts, weights, mode, coefs, coef_dev=None, rescale=0.0, ring=False):
+def cfg_multistep_step_windows(preds, sample, hist, starts, weights, mode, coefs, coef_dev=None, rescale=0.0, ring=False, apg=None):
     """``cfg_multistep_step`` on the per-frame weighted blend of sliding-window predictions, one pass: ``preds`` / ``starts`` /
     ``weights`` / ``ring`` as in ``cfg_ddim_step_windows``, ``hist`` float32 in ``sample``'s layout.  ``rescale`` != 0: the
-    statistics launch over the blends in front of the step launch."""
+    statistics launch over the blends in front of the step launch.  ``apg``: as in ``cfg_ddim_step_windows``."""
     _dev(preds, sample, hist, starts, weights)
     nW, outer, F, L, inner = geometry = _windows_geometry(preds, sample, starts, weights)
     _check_multistep("cfg_multistep_step_windows", sample, hist, mode, coefs, coef_dev)
     out = torch.empty(sample.shape, dtype=sample.dtype, device=sample.device)
+    if apg is not None:
+        eta, threshold = _apg_args("cfg_multistep_step_windows", apg, rescale)
+        ws = _apg_stats_windows(preds, sample, starts, weights, geometry, mode, coefs, coef_dev, ring)
+        rc = lib().im360_cfg_multistep_step_windows_apg(_p(preds), _p(sample), _p(hist), _p(out), _p(starts), _p(weights), nW, outer, F, L,
+                                                        inner, F if ring else 0, *(float(v) for v in coefs), int(mode), eta, threshold, _p(ws),
+                                                        ws.numel(), _dt(sample), _stream(), _p(coef_dev))
+        _check(rc, "im360_cfg_multistep_step_windows_apg")
+        return out
     ws = _rescale_stats_windows(preds, sample, starts, weights, geometry, coefs[0], coef_dev, ring) if rescale != 0.0 else None
     rc = lib().im360_cfg_multistep_step_windows(_p(preds), _p(sample), _p(hist), _p(out), _p(starts), _p(weights), nW, outer, F, L, inner,
                                                 F if ring else 0, *(float(v) for v in coefs), int(mode), float(rescale), _p(ws),

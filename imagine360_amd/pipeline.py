@@ -13,6 +13,9 @@ surface, rebuilt for the MI355X:
     noise is drawn (from ``generator`` when given), exactly where the reference's ``scheduler.step`` draws it;
   * guidance rescale (``guidance_rescale=phi``, arXiv 2305.08891 section 3.4): the guided prediction of each branch scaled towards
     the text prediction's standard deviation inside the CFG + DDIM kernels (a statistics launch in front of the step launch);
+  * adaptive projected guidance (``apg_eta=eta``, ``apg_threshold=r``, arXiv 2410.02416): the guidance difference of each branch split
+    along the text branch's denoised prediction, its parallel part scaled by eta, its RMS clamped to r, in place of the CFG
+    combination inside the fused step kernels (a statistics launch in front of the step launch);
   * long clips (``context_frames=L``): sliding temporal context windows -- one forward of the unmodified model per window
     of L frames, the windows' predictions blended per frame inside the CFG + DDIM kernel (imagine360_amd/context.py).
   * a start from a clip that exists (``init_latents`` / ``init_video`` with ``strength``): the clean latent noised to the timestep at
@@ -368,7 +371,7 @@ class AnimationPipeline:
                  context_frames=None, context_overlap=4, context_weights="pyramid", guidance_rescale=0.0, context_loop=False,
                  init_latents=None, init_video=None, strength=1.0, regenerate_mask=None, init_resize="bicubic", init_retime=None,
                  free_init_iters=1, free_init_d_s=0.25, free_init_d_t=0.25, regenerate_mode="blend", regenerate_feather=0.0,
-                 guidance_interval=None, context_level="model", **kwargs):
+                 guidance_interval=None, context_level="model", apg_eta=None, apg_threshold=None, **kwargs):
         """``frame_shard`` (imagine360_amd.dist.FrameShard): this rank denoises a contiguous chunk of the frames (BASELINE
         configs 4 / 5); all ranks must be called with the same seeds and inputs.  Noise is drawn for the whole clip and
         cut, the VAE encodes / the loop runs / the VAE decodes only the local frames, the motion modules exchange tokens
@@ -491,7 +494,26 @@ class AnimationPipeline:
         with both kinds of step owns two captured graphs over the same static buffers and ``step`` replays the one the flags select.
         The IP tokens of both forms of the SAM features are cached side by side for the run (``context.ip_cache_slots``) and dropped on
         exit.  Malformed intervals and ``frame_shard`` raise ``ValueError``.  What the interval does to a clip's quality can only be
-        judged with trained weights."""
+        judged with trained weights.
+        ``apg_eta`` (None: off; the paper's value is 0.0) / ``apg_threshold`` (None: no clamp): adaptive projected guidance (APG, arXiv
+        2410.02416, algorithm 1 without its momentum; ``scheduler.projected_guidance`` is the definition) in place of the plain CFG
+        combination on every guided step.  In x0 space the guidance difference is split into the part parallel to the text branch's
+        denoised prediction -- the part that saturates under the shipped zero-terminal-SNR, guidance-7.5 configuration -- and the part
+        orthogonal to it; the parallel part is scaled by ``apg_eta`` (0 removes it, 1 keeps it) and the difference is first clamped to
+        ``apg_threshold``.  The threshold is an RMS in x0 units, not the paper's norm (which would tie the setting to clip length and
+        resolution): the paper's radius equals ``apg_threshold * sqrt(C * H * W)``; it must be > 0.  The three sums run over the domain
+        of ``guidance_rescale`` (the whole panorama latent, all views of the perspective latent, with context windows the whole clip of
+        blends) inside the fused step kernels: a statistics launch in front of each branch's step launch, nothing read back, captured
+        with the step under graph replay.  ``apg_eta=1`` without a threshold is plain CFG up to rounding, not bit for bit; equal
+        unconditional and text predictions give the text prediction; a zero denoised text prediction gives NaN.  Everything behind the
+        combination is unchanged (the clamp, ``use_clipped_model_output``, ``eta`` > 0, the multistep update and its history, which
+        receives the x0 of the projected guidance), and so is the RNG order.  Every loop variant (graph replay, ``eta``, context windows
+        on a line and on a ring, ``context_level="attention"``, ``init_latents`` / ``strength``, ``regenerate_mask`` in both modes,
+        DPM-Solver++ 2M, ``free_init_iters``, ``guidance_interval``: an unguided step has no guidance difference and makes no APG
+        launch).  ``ValueError``: ``apg_threshold`` without ``apg_eta``, non-finite values, ``apg_threshold <= 0``, ``apg_eta`` with
+        ``guidance_rescale != 0`` (the two address the same defect; the product of the kernel variants is not built) and with
+        ``frame_shard`` (the sums span the frames of all ranks).  The paper's momentum is not implemented.  What APG does to a clip's
+        look can only be judged with trained weights."""
         device = self.device
         vb = video_batch
         plan = None
@@ -511,6 +533,24 @@ class AnimationPipeline:
         if guidance_rescale != 0.0 and frame_shard is not None:
             raise ValueError("guidance_rescale cannot be combined with frame_shard (the standard deviations span the frames of all "
                              "ranks and would need an all-reduce inside the step, which is not implemented)")
+        apg_kw = {}
+        if apg_eta is None:
+            if apg_threshold is not None:
+                raise ValueError("apg_threshold needs apg_eta (adaptive projected guidance is off without it)")
+        else:
+            apg_eta = float(apg_eta)
+            apg_threshold = None if apg_threshold is None else float(apg_threshold)
+            if not math.isfinite(apg_eta):
+                raise ValueError(f"apg_eta must be finite, got {apg_eta}")
+            if apg_threshold is not None and not (math.isfinite(apg_threshold) and apg_threshold > 0.0):
+                raise ValueError(f"apg_threshold must be None (no clamp) or a finite RMS radius > 0, got {apg_threshold}")
+            if guidance_rescale != 0.0:
+                raise ValueError("apg_eta cannot be combined with guidance_rescale != 0 (both address the over-exposure of a "
+                                 "zero-terminal-SNR schedule under strong guidance; the product of the kernel variants is not built)")
+            if frame_shard is not None:
+                raise ValueError("apg_eta cannot be combined with frame_shard (its sums span the frames of all ranks and would need an "
+                                 "all-reduce inside the step, which is not implemented)")
+            apg_kw = dict(guidance_apg=(apg_eta, apg_threshold))
         if context_loop and frame_shard is not None:
             raise ValueError("context_loop cannot be combined with frame_shard (windows under frame sharding are not implemented)")
         if init_latents is not None and init_video is not None:
@@ -683,7 +723,7 @@ class AnimationPipeline:
                 pano_latent, pers_latent = self._windowed_loop(plan, inputs, cameras, pano_latent, pers_latent, steps_host, ts_dev,
                                                                guidance_scale_text, use_fps_condition, eta, generator, trace,
                                                                callback, callback_steps, guidance_rescale, region, hist, next_pass,
-                                                               **({} if guided is None else dict(guidance_interval=guidance_interval)))
+                                                               **({} if guided is None else dict(guidance_interval=guidance_interval)), **apg_kw)
             graphed = None
             if guided is not None and plan is None:
                 # the text-half views of the model inputs, made once and kept (the IP-token cache keys on the feature tensors' identity),
@@ -709,6 +749,7 @@ class AnimationPipeline:
                     stoch["keep"] = region
                 if guided is not None:
                     stoch.update(guidance_interval=guidance_interval, steps=steps_host)
+                stoch.update(apg_kw)
                 graphed = GraphedDenoiseStep(self.mv_base_model, self.scheduler, inputs, cameras, pano_latent, pers_latent,
                                              guidance_scale_text, use_fps=use_fps_condition, warmup=1, guidance_rescale=guidance_rescale, **stoch)       # one eager step fills every cache
             while plan is None:                 # one round per pass: once without free_init_iters
@@ -718,7 +759,7 @@ class AnimationPipeline:
                         continue
                     if guided is not None and not guided[i]:
                         pano_latent, pers_latent = self._unguided_step(text_half, pano_latent, pers_latent, ts_dev[i], t, cameras,
-                                                                       use_fps_condition, eta, generator, guidance_rescale, hist)
+                                                                       use_fps_condition, eta, generator, guidance_rescale, hist, **apg_kw)
                     else:
                         in_pano[:, :4] = pano_latent
                         in_pers[:, :, :4] = pers_latent
@@ -729,9 +770,9 @@ class AnimationPipeline:
                             reference_images_clip_feat_pano=feat_pano, reference_images_clip_feat_pers=feat_pers,
                             relative_position_tensor=rel, pitchs_tensor=pitch)
                         pano_latent = self._cfg_step(pred_pano, guidance_scale_text, t, pano_latent, eta, generator, sh, 2, guidance_rescale,
-                                                     **({} if hist is None else dict(history=hist[0])))
+                                                     **({} if hist is None else dict(history=hist[0])), **apg_kw)
                         pers_latent = self._cfg_step(pred_pers, guidance_scale_text, t, pers_latent, eta, generator, sh, 3, guidance_rescale,
-                                                     **({} if hist is None else dict(history=hist[1])))
+                                                     **({} if hist is None else dict(history=hist[1])), **apg_kw)
                     if region is not None:
                         region.apply(pano_latent, pers_latent, i)
                     if trace is not None:
@@ -767,13 +808,15 @@ class AnimationPipeline:
             if ip_slots is not None:
                 ip_slots.__exit__(None, None, None)           # (guidance_interval) back to the single-entry IP-token cache
 
-    def _cfg_step(self, pred, g, t, latent, eta=0.0, generator=None, shard=None, frame_dim=2, guidance_rescale=0.0, **history):
-        """``history`` (``history=``, a multistep scheduler only): the x0 history of this latent, handed on to the scheduler."""
+    def _cfg_step(self, pred, g, t, latent, eta=0.0, generator=None, shard=None, frame_dim=2, guidance_rescale=0.0, guidance_apg=None, **history):
+        """``history`` (``history=``, a multistep scheduler only): the x0 history of this latent, handed on to the scheduler.
+        ``guidance_apg``: handed on when it is set (``apg_eta``)."""
         u, c = pred.to(latent.dtype).chunk(2)          # latents_dtype may differ from the model dtype (the reference promotes)
+        apg = {} if guidance_apg is None else dict(guidance_apg=guidance_apg)
         if eta > 0:
             z = variance_noise(self.scheduler, latent, pred.dtype, generator, self.rng, shard, frame_dim)
-            return self.scheduler.fused_cfg_step(u, c, g, t, latent, eta=eta, noise=z, guidance_rescale=guidance_rescale)
-        return self.scheduler.fused_cfg_step(u, c, g, t, latent, guidance_rescale=guidance_rescale, **history)
+            return self.scheduler.fused_cfg_step(u, c, g, t, latent, eta=eta, noise=z, guidance_rescale=guidance_rescale, **apg)
+        return self.scheduler.fused_cfg_step(u, c, g, t, latent, guidance_rescale=guidance_rescale, **apg, **history)
 
     def _text_half_step(self, forward, step, pano_latent, pers_latent, eta, generator, hist, model_dtype=None):
         """One unguided step (``guidance_interval``): ``forward()`` runs the model on the text half with ``mv._ip_noise_half = (1, 2)`` --
@@ -794,7 +837,8 @@ class AnimationPipeline:
             out.append(step(pred, latent, z, {} if hist is None else dict(history=hist[branch])))
         return out
 
-    def _unguided_step(self, text_half, pano_latent, pers_latent, t_dev, t, cameras, use_fps, eta, generator, guidance_rescale, hist):
+    def _unguided_step(self, text_half, pano_latent, pers_latent, t_dev, t, cameras, use_fps, eta, generator, guidance_rescale, hist,
+                       **apg_kw):
         """The one-block loop's unguided step: the model on ``text_half`` (``dist.cfg_half_inputs(inputs, 1)``, made once per run), then
         ``scheduler.fused_step`` per branch."""
         def forward():
@@ -804,11 +848,11 @@ class AnimationPipeline:
 
         def step(pred, latent, z, history):
             return self.scheduler.fused_step(pred.to(latent.dtype), t, latent, **(dict(eta=eta, noise=z) if eta > 0 else {}),
-                                             guidance_rescale=guidance_rescale, **history)
+                                             guidance_rescale=guidance_rescale, **apg_kw, **history)
         return self._text_half_step(forward, step, pano_latent, pers_latent, eta, generator, hist)
 
     def _unguided_windows_step(self, plan, text_half, text_static, text_preds, pano_latent, pers_latent, t_dev, t, cameras, use_fps, eta,
-                               generator, guidance_rescale, hist):
+                               generator, guidance_rescale, hist, **apg_kw):
         """The windowed loop's unguided step: every window on its text half (``text_half`` / ``text_static``: views made once per run)
         into the [nW, 1, ...] buffers ``text_preds`` (perspective, panorama), then ``scheduler.fused_step_windows`` per branch."""
         mv, sch = self.mv_base_model, self.scheduler
@@ -821,11 +865,12 @@ class AnimationPipeline:
 
         def step(preds, latent, z, history):
             return sch.fused_step_windows(preds, plan.starts_dev, plan.weights, t, latent, noise=z, eta=eta,
-                                          guidance_rescale=guidance_rescale, ring=plan.loop, **history)
+                                          guidance_rescale=guidance_rescale, ring=plan.loop, **apg_kw, **history)
         return self._text_half_step(forward, step, pano_latent, pers_latent, eta, generator, hist, model_dtype=mv.unet.dtype)
 
     def _windowed_loop(self, plan, inputs, cameras, pano_latent, pers_latent, steps_host, ts_dev, g, use_fps, eta, generator,
-                       trace, callback, callback_steps, guidance_rescale=0.0, keep=None, hist=None, next_pass=None, guidance_interval=None):
+                       trace, callback, callback_steps, guidance_rescale=0.0, keep=None, hist=None, next_pass=None, guidance_interval=None,
+                       guidance_apg=None):
         """The denoising loop over sliding temporal context windows: per step one forward per window (slot order), then ONE
         blend + CFG + DDIM kernel per branch, panorama first.  RNG: as len(plan) successive calls of the model, then (eta > 0)
         the whole clip's panorama and perspective variance noise.  Captured in one hipGraph under the conditions of the
@@ -834,9 +879,11 @@ class AnimationPipeline:
         eager loop (the graphed step owns its own).  ``next_pass`` (FreeInit): called with the two latents behind the last step; None ends the
         loop, else it returns the start latents of another run of the whole schedule (the captured step is restarted, not captured again).
         ``guidance_interval`` (None: every step guided): the unguided steps run every window on its text half (views made once, [nW, 1, ...]
-        prediction buffers, ``scheduler.fused_step_windows``), and the IP-token cache holds both forms of every window's features."""
+        prediction buffers, ``scheduler.fused_step_windows``), and the IP-token cache holds both forms of every window's features.
+        ``guidance_apg`` (``apg_eta``): handed on to the scheduler's step functions and the graphed step when it is set."""
         from .context import ip_cache_slots
         mv, sch = self.mv_base_model, self.scheduler
+        apg_kw = {} if guidance_apg is None else dict(guidance_apg=guidance_apg)
         guided = None if guidance_interval is None else sch.guided_steps(steps_host, guidance_interval)
         with ip_cache_slots(mv, len(plan) * (1 if guided is None else 2)):
             if self.use_graph and self.rng == "device" and pano_latent.is_cuda and trace is None and callback is None:
@@ -844,7 +891,7 @@ class AnimationPipeline:
                 graphed = GraphedWindowedStep(mv, sch, inputs, cameras, pano_latent, pers_latent, g, plan, use_fps=use_fps, warmup=1,
                                               eta=eta, generator=generator, guidance_rescale=guidance_rescale,
                                               **({} if keep is None else dict(keep=keep)),
-                                              **({} if guided is None else dict(guidance_interval=guidance_interval, steps=steps_host)))
+                                              **({} if guided is None else dict(guidance_interval=guidance_interval, steps=steps_host)), **apg_kw)
                 while True:
                     for t in self.progress_bar(steps_host):
                         pano_latent, pers_latent = graphed.step(t)
@@ -863,13 +910,13 @@ class AnimationPipeline:
                     if guided is not None and not guided[i]:
                         pano_latent, pers_latent = self._unguided_windows_step(plan, text_half, text_static, text_preds, pano_latent,
                                                                                pers_latent, ts_dev[i], t, cameras, use_fps, eta, generator,
-                                                                               guidance_rescale, hist)
+                                                                               guidance_rescale, hist, **apg_kw)
                     else:
                         inputs["pano_latent"][:, :4] = pano_latent
                         inputs["latents"][:, :, :4] = pers_latent
                         plan.forward(mv, inputs, static, cameras, ts_dev[i], use_fps, preds_pers, preds_pano)
                         mdt = mv.unet.dtype
-                        kw = dict(eta=eta, guidance_rescale=guidance_rescale, ring=plan.loop)
+                        kw = dict(eta=eta, guidance_rescale=guidance_rescale, ring=plan.loop, **apg_kw)
                         z = variance_noise(sch, pano_latent, mdt, generator, self.rng) if eta > 0 else None
                         pano_latent = sch.fused_cfg_step_windows(preds_pano, plan.starts_dev, plan.weights, g, t, pano_latent, noise=z, **kw,
                                                                  **({} if hist is None else dict(history=hist[0])))

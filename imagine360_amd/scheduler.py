@@ -6,7 +6,8 @@ bit for bit) and combined in fp64 python floats; on the GPU the whole CFG + upda
 pipeline is one elementwise HIP kernel (``fused_cfg_step``): the eta = 0 v / epsilon update of the dual pipeline on
 ``cfg_ddim_update``, everything else ``step`` supports (eta > 0, clip_sample, prediction_type="sample",
 use_clipped_model_output) on ``cfg_ddim_step``; with ``guidance_rescale`` (arXiv 2305.08891, section 3.4) a statistics launch
-precedes ``cfg_ddim_step``.
+precedes ``cfg_ddim_step``; with ``guidance_apg`` (adaptive projected guidance, arXiv 2410.02416; ``projected_guidance`` is the
+definition) a statistics launch precedes the step kernel on the projected guidance.
 
 ``DPMSolverMultistepScheduler`` (DPM-Solver++ 2M, arXiv 2211.01095) is the second-order sampler on the same tables and timestep grid;
 its update runs on ``cfg_multistep_step`` / ``cfg_multistep_step_windows`` with an fp32 x0 history per latent.
@@ -68,6 +69,53 @@ def rescale_noise_cfg(noise_cfg, noise_pred_text, guidance_rescale=0.0):
     std_text = noise_pred_text.std(dim=dims, keepdim=True)
     std_cfg = noise_cfg.std(dim=dims, keepdim=True)
     return noise_cfg * (guidance_rescale * std_text / std_cfg + (1.0 - guidance_rescale))
+
+
+_APG_KAPPA = {"epsilon": lambda sa, sb: (1.0 / sa, -sb / sa), "v_prediction": lambda sa, sb: (sa, -sb), "sample": lambda sa, sb: (0.0, 1.0)}
+
+
+def projected_guidance(pred_uncond, pred_text, sample, guidance, sqrt_a, sqrt_b, prediction_type, eta, threshold=None):
+    """Adaptive projected guidance (APG, arXiv 2410.02416, algorithm 1 without its momentum; diffusers carries it as a guider) in
+    model-output space: what the step functions take in place of ``pred_uncond + guidance * (pred_text - pred_uncond)``.  The eager
+    definition, in torch ops on any device and in the inputs' dtype (fp64 in, fp64 out); the pipeline's kernels compute the same
+    inside the fused CFG + step kernels.
+
+    With D(p) = kx * sample + kp * p the x0 conversion of the prediction type (epsilon: kx = 1 / sqrt_a, kp = -sqrt_b / sqrt_a;
+    v_prediction: sqrt_a, -sqrt_b; sample: 0, 1) the paper updates the denoised prediction:
+
+        Delta = D(c) - D(u),   alpha = <Delta, D(c)> / <D(c), D(c)>,   s = min(1, threshold / rms(Delta))
+        D^ = D(c) + (guidance - 1) * s * (Delta - (1 - eta) * alpha * D(c))
+
+    i.e. the guidance difference is split into its part parallel to D(c) -- the part that saturates -- and the rest, the parallel
+    part is scaled by ``eta`` (0, the paper's value, removes it; 1 keeps it), and the difference is clamped first.  Mapped back to the
+    model's output kp cancels, and with d = c - u, q = c + (kx / kp) * sample:
+
+        alpha = sum d q / sum q^2,   s = min(1, threshold / (|kp| sqrt(sum d^2 / N))),   m = c + (g - 1) s d - (g - 1) s (1 - eta) alpha q
+
+    The sums run over the WHOLE tensor (the domain of ``rescale_noise_cfg`` in this pipeline: the whole panorama latent, all views of
+    the perspective latent, with context windows the whole clip of blends).  ``threshold`` is an RMS in x0 units, not the paper's
+    norm: a norm over a 4 x F x h x w clip would tie the setting to clip length and resolution; the paper's radius equals
+    ``threshold * sqrt(C * H * W)``.  None: no clamp.
+
+    Edge cases, as the formula gives them: ``eta = 1`` without a threshold is plain CFG up to rounding (not bit for bit);
+    ``pred_uncond == pred_text`` gives m = pred_text; ``sum q^2 = 0`` gives NaN."""
+    if prediction_type not in _APG_KAPPA:
+        raise ValueError(f"prediction_type given as {prediction_type} must be one of `epsilon`, `sample`, or `v_prediction`")
+    kx, kp = _APG_KAPPA[prediction_type](sqrt_a, sqrt_b)
+    u, c = pred_uncond, pred_text
+    d, q = c - u, c + (kx / kp) * sample
+    alpha = (d * q).sum() / (q * q).sum()
+    s = 1.0
+    if threshold is not None:
+        s = torch.clamp(threshold / (abs(kp) * (d * d).mean().sqrt()), max=1.0)
+    gs = (guidance - 1.0) * s
+    return c + gs * d - gs * (1.0 - eta) * alpha * q
+
+
+def _apg_kw(guidance_apg):
+    """``apg=`` for the guided step wrappers of ``kernels``, left out when it is off: they are then called with exactly the arguments of
+    before.  ``guidance_apg``: None or (eta, threshold)."""
+    return dict(apg=(guidance_apg[0], guidance_apg[1])) if guidance_apg is not None else {}
 
 
 def _rescale_kw(guidance_rescale):
@@ -142,11 +190,11 @@ class DDIMScheduler:
             raise ValueError(f"prediction_type {self.config.prediction_type} unsupported")
         return cx, cv
 
-    def uses_step_kernel(self, eta=0.0, use_clipped_model_output=False, guidance_rescale=0.0):
+    def uses_step_kernel(self, eta=0.0, use_clipped_model_output=False, guidance_rescale=0.0, guidance_apg=None):
         """True when an update needs ``cfg_ddim_step``: anything but the eta = 0, unclipped v / epsilon update without guidance
-        rescale that ``coefficients`` / ``cfg_ddim_update`` compute."""
+        rescale and without projected guidance that ``coefficients`` / ``cfg_ddim_update`` compute."""
         return (eta != 0.0 or bool(self.config.clip_sample) or bool(use_clipped_model_output) or guidance_rescale != 0.0
-                or self.config.prediction_type not in ("v_prediction", "epsilon"))
+                or guidance_apg is not None or self.config.prediction_type not in ("v_prediction", "epsilon"))
 
     def kernel_mode(self, use_clipped_model_output=False):
         """Mode bits of ``cfg_ddim_step``: prediction type | clip_sample | use_clipped_model_output."""
@@ -296,49 +344,54 @@ class DDIMScheduler:
         return DDIMSchedulerOutput(prev_sample=prev, pred_original_sample=x0) if return_dict else (prev,)
 
     def fused_cfg_step(self, pred_uncond, pred_text, guidance_scale, timestep, sample, coef_dev=None, *, eta=0.0, noise=None,
-                       use_clipped_model_output=False, guidance_rescale=0.0):
+                       use_clipped_model_output=False, guidance_rescale=0.0, guidance_apg=None):
         """CFG combine + update in one HIP kernel (pipeline_animation_inference_dual.py:791-800).  ``coef_dev``: device
         float32 coefficients read by the kernel instead of host scalars (graph replay): [3] = (guidance, cx, cv) for the
         eta = 0 v / epsilon update, [6] = ``step_coefficients`` otherwise.  ``noise``: the variance noise (like ``sample``),
         used when eta > 0.  ``guidance_rescale`` != 0: ``rescale_noise_cfg`` on the combination before the update, inside the step
-        kernel (always the six-coefficient one)."""
+        kernel (always the six-coefficient one).  ``guidance_apg = (eta, threshold)``: ``projected_guidance`` in place of the
+        combination, inside the step kernel (the six-coefficient one, a statistics launch in front); not together with
+        ``guidance_rescale``."""
         u, c, x = pred_uncond.contiguous(), pred_text.contiguous(), sample.contiguous()
-        if not self.uses_step_kernel(eta, use_clipped_model_output, guidance_rescale):
+        if not self.uses_step_kernel(eta, use_clipped_model_output, guidance_rescale, guidance_apg):
             cx, cv = (0.0, 0.0) if coef_dev is not None else self.coefficients(timestep)
             return kernels.cfg_ddim_update(u, c, x, guidance_scale, cx, cv, coef_dev=coef_dev)
         if eta > 0 and noise is None:
             raise ValueError("fused_cfg_step: eta > 0 needs the variance noise")
         coefs = (0.0,) * 6 if coef_dev is not None else self.step_coefficients(timestep, eta, guidance_scale)
         return kernels.cfg_ddim_step(u, c, x, noise.to(x.dtype).contiguous() if eta > 0 else None,
-                                     self.kernel_mode(use_clipped_model_output), coefs, coef_dev=coef_dev, **_rescale_kw(guidance_rescale))
+                                     self.kernel_mode(use_clipped_model_output), coefs, coef_dev=coef_dev, **_rescale_kw(guidance_rescale),
+                                     **_apg_kw(guidance_apg))
 
     def fused_cfg_step_windows(self, preds, starts, weights, guidance_scale, timestep, sample, coef_dev=None, *, eta=0.0,
-                               noise=None, use_clipped_model_output=False, guidance_rescale=0.0, ring=False):
+                               noise=None, use_clipped_model_output=False, guidance_rescale=0.0, ring=False, guidance_apg=None):
         """``fused_cfg_step`` over sliding temporal context windows: the per-frame weighted blend of the windows' CFG-combined
         predictions + the update, one HIP kernel (``kernels.cfg_ddim_step_windows``).  ``preds`` [nW, 2, ...]: window k's
         CFG-batched prediction in slot k, in ``sample``'s layout with L frames;  ``starts`` device int32 [nW], ``weights`` device
         float32 [L] (imagine360_amd.context).  The step kernel serves eta = 0 as well, so ``coef_dev`` is always float32[6] =
         ``step_coefficients``.  ``guidance_rescale`` != 0: ``rescale_noise_cfg`` on the blends (guided and text), the standard
         deviations over the whole clip.  ``ring``: the windows of a looping clip (context.WindowPlan(loop=True)), ``starts`` on a
-        ring of F frames."""
+        ring of F frames.  ``guidance_apg``: ``projected_guidance`` on the blends of the two halves, the sums over the whole clip."""
         if eta > 0 and noise is None:
             raise ValueError("fused_cfg_step_windows: eta > 0 needs the variance noise")
         x = sample.contiguous()
         coefs = (0.0,) * 6 if coef_dev is not None else self.step_coefficients(timestep, eta, guidance_scale)
         return kernels.cfg_ddim_step_windows(preds.contiguous(), x, noise.to(x.dtype).contiguous() if eta > 0 else None, starts,
                                              weights, self.kernel_mode(use_clipped_model_output), coefs, coef_dev=coef_dev, **_rescale_kw(guidance_rescale),
-                                             **_ring_kw(ring))
+                                             **_ring_kw(ring), **_apg_kw(guidance_apg))
 
 
-    def fused_step(self, pred, timestep, sample, coef_dev=None, *, eta=0.0, noise=None, use_clipped_model_output=False, guidance_rescale=0.0):
+    def fused_step(self, pred, timestep, sample, coef_dev=None, *, eta=0.0, noise=None, use_clipped_model_output=False, guidance_rescale=0.0,
+                   guidance_apg=None):
         """``fused_cfg_step`` for an UNGUIDED step (``guided_steps``): the model ran the text half alone and ``pred`` is its one
         prediction.  The same kernels in their unguided form (``kernels.ddim_update`` / ``kernels.ddim_step``: one prediction stream, no
         guidance read), the same choice between them, the same coefficient vectors -- ``coef_dev`` is the buffer the guided step reads.
         ``guidance_rescale`` is SKIPPED -- no statistics launch, no factor: rescaling a prediction towards its own standard deviation is
         the identity; the keyword only selects the six-coefficient kernel as it does for the guided steps of the run, so that both forms
-        read one coefficient vector."""
+        read one coefficient vector.  ``guidance_apg`` is skipped in the same way: without an unconditional prediction there is no
+        guidance difference to project."""
         p, x = pred.contiguous(), sample.contiguous()
-        if not self.uses_step_kernel(eta, use_clipped_model_output, guidance_rescale):
+        if not self.uses_step_kernel(eta, use_clipped_model_output, guidance_rescale, guidance_apg):
             cx, cv = (0.0, 0.0) if coef_dev is not None else self.coefficients(timestep)
             return kernels.ddim_update(p, x, cx, cv, coef_dev=coef_dev)
         if eta > 0 and noise is None:
@@ -348,9 +401,9 @@ class DDIMScheduler:
                                  coef_dev=coef_dev)
 
     def fused_step_windows(self, preds, starts, weights, timestep, sample, coef_dev=None, *, eta=0.0, noise=None,
-                           use_clipped_model_output=False, guidance_rescale=0.0, ring=False):
+                           use_clipped_model_output=False, guidance_rescale=0.0, ring=False, guidance_apg=None):
         """``fused_cfg_step_windows`` for an unguided step: ``preds`` [nW, 1, ...], the windows' text halves alone
-        (``kernels.ddim_step_windows``); everything else as there, ``guidance_rescale`` skipped as in ``fused_step``."""
+        (``kernels.ddim_step_windows``); everything else as there, ``guidance_rescale`` and ``guidance_apg`` skipped as in ``fused_step``."""
         if eta > 0 and noise is None:
             raise ValueError("fused_step_windows: eta > 0 needs the variance noise")
         x = sample.contiguous()
@@ -409,7 +462,7 @@ class DPMSolverMultistepScheduler(DDIMScheduler):
         """The x0 history of one latent: zeros, float32, ``latent``'s shape and device.  One per latent that is stepped."""
         return torch.zeros(latent.shape, dtype=torch.float32, device=latent.device)
 
-    def uses_step_kernel(self, eta=0.0, use_clipped_model_output=False, guidance_rescale=0.0):
+    def uses_step_kernel(self, eta=0.0, use_clipped_model_output=False, guidance_rescale=0.0, guidance_apg=None):
         """Always the six-coefficient kernel."""
         return True
 
@@ -497,29 +550,31 @@ class DPMSolverMultistepScheduler(DDIMScheduler):
         return (0.0,) * 6 if coef_dev is not None else self.step_coefficients(timestep, 0.0, guidance_scale)
 
     def fused_cfg_step(self, pred_uncond, pred_text, guidance_scale, timestep, sample, coef_dev=None, *, history=None, eta=0.0, noise=None,
-                       guidance_rescale=0.0, **kwargs):
+                       guidance_rescale=0.0, guidance_apg=None, **kwargs):
         """CFG combine + the multistep update in one HIP kernel (``kernels.cfg_multistep_step``); ``history``: this latent's
-        ``new_history``, updated in place.  ``coef_dev``: device float32[6] = ``step_coefficients`` read by the kernel (graph replay)."""
+        ``new_history``, updated in place.  ``coef_dev``: device float32[6] = ``step_coefficients`` read by the kernel (graph replay).
+        ``guidance_apg``: as in ``DDIMScheduler.fused_cfg_step``; the history then receives the x0 of the projected guidance."""
         coefs = self._kernel_args("fused_cfg_step", timestep, guidance_scale, coef_dev, history, eta, noise, kwargs)
         return kernels.cfg_multistep_step(pred_uncond.contiguous(), pred_text.contiguous(), sample.contiguous(), history, self.kernel_mode(),
-                                          coefs, coef_dev=coef_dev, **_rescale_kw(guidance_rescale))
+                                          coefs, coef_dev=coef_dev, **_rescale_kw(guidance_rescale), **_apg_kw(guidance_apg))
 
     def fused_cfg_step_windows(self, preds, starts, weights, guidance_scale, timestep, sample, coef_dev=None, *, history=None, eta=0.0,
-                               noise=None, guidance_rescale=0.0, ring=False, **kwargs):
+                               noise=None, guidance_rescale=0.0, ring=False, guidance_apg=None, **kwargs):
         """``fused_cfg_step`` on the blend of sliding temporal context windows (``kernels.cfg_multistep_step_windows``; arguments of
         ``DDIMScheduler.fused_cfg_step_windows``)."""
         coefs = self._kernel_args("fused_cfg_step_windows", timestep, guidance_scale, coef_dev, history, eta, noise, kwargs)
         return kernels.cfg_multistep_step_windows(preds.contiguous(), sample.contiguous(), history, starts, weights, self.kernel_mode(), coefs,
-                                                  coef_dev=coef_dev, **_rescale_kw(guidance_rescale), **_ring_kw(ring))
+                                                  coef_dev=coef_dev, **_rescale_kw(guidance_rescale), **_ring_kw(ring), **_apg_kw(guidance_apg))
 
-    def fused_step(self, pred, timestep, sample, coef_dev=None, *, history=None, eta=0.0, noise=None, guidance_rescale=0.0, **kwargs):
+    def fused_step(self, pred, timestep, sample, coef_dev=None, *, history=None, eta=0.0, noise=None, guidance_rescale=0.0, guidance_apg=None,
+                   **kwargs):
         """``fused_cfg_step`` for an unguided step (``DDIMScheduler.fused_step``): the multistep update on the one prediction
         (``kernels.multistep_step``); ``history`` is written and read as on a guided step -- the six coefficients do not depend on guidance."""
         coefs = self._kernel_args("fused_step", timestep, 1.0, coef_dev, history, eta, noise, kwargs)
         return kernels.multistep_step(pred.contiguous(), sample.contiguous(), history, self.kernel_mode(), coefs, coef_dev=coef_dev)
 
     def fused_step_windows(self, preds, starts, weights, timestep, sample, coef_dev=None, *, history=None, eta=0.0, noise=None,
-                           guidance_rescale=0.0, ring=False, **kwargs):
+                           guidance_rescale=0.0, ring=False, guidance_apg=None, **kwargs):
         """``fused_cfg_step_windows`` for an unguided step: ``preds`` [nW, 1, ...] (``kernels.multistep_step_windows``)."""
         coefs = self._kernel_args("fused_step_windows", timestep, 1.0, coef_dev, history, eta, noise, kwargs)
         return kernels.multistep_step_windows(preds.contiguous(), sample.contiguous(), history, starts, weights, self.kernel_mode(), coefs,

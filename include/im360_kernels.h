@@ -435,6 +435,71 @@ int im360_multistep_step_windows(const void* pred, const void* x, void* hist, vo
                                  float sqrt_b, float cx, float c0, float c1, int mode, int dtype, void* stream,
                                  const void* coef_dev);
 
+/* ---- adaptive projected guidance (APG, arXiv 2410.02416, algorithm 1 without its momentum) inside the guided step entry points.
+ * The step sees, in place of m = uncond + guidance * (cond - uncond),
+ *   d = cond - uncond,   q = cond + rho * x,   rho = -1 / sqrt_b (epsilon), -sqrt_a / sqrt_b (v_prediction), 0 (sample)
+ *   alpha = sum d q / sum q^2
+ *   s = min(1, threshold / (kp * sqrt(sum d^2 / n))),   kp = sqrt_b / sqrt_a (epsilon), sqrt_b (v_prediction), 1 (sample)
+ *   m = cond + (guidance - 1) * s * d - lambda * q,   lambda = (guidance - 1) * s * (1 - eta) * alpha
+ * i.e. the paper's update of the denoised prediction D(p) = kx x + kp p mapped back to the model's output: the guidance difference
+ * D(cond) - D(uncond) split along D(cond) = kp q, its parallel part scaled by eta, its RMS clamped to `threshold` (x0 units;
+ * INFINITY: no clamp).  The sums run over all n elements in fp32.  eta = 1 without a clamp is m up to rounding; uncond == cond gives
+ * m = cond; sum q^2 = 0 gives NaN.  Two launches like the guidance rescale, with its workspace (8 * im360_cfg_rescale_records(n)
+ * floats) and its grid: a statistics pass writes one record (count, sum d q, sum q^2, sum d^2) per workgroup, and every workgroup of
+ * the step merges all of them in one fixed order -- no atomics, nothing read back, the same bits on every launch.  sqrt_a, sqrt_b and
+ * the guidance are read from coef_dev[1], [2], [0] where coef_dev is given (the steps' six-float vectors: hipGraph replay).
+ * Argument errors beyond the siblings': eta not finite, threshold not > 0, a short or misaligned workspace.
+ * Replaces: nothing in the reference (its pipeline has plain CFG only); the guider of arXiv 2410.02416 between the model and
+ *   DDIMScheduler.step / algorithm 2 of arXiv 2211.01095. */
+
+/* the statistics pass over uncond / cond / x: n elements (n % 8 == 0) of one 16-bit dtype, 16-byte aligned; mode: bits 0-1 select rho */
+int im360_cfg_apg_stats(const void* uncond, const void* cond, const void* x, int64_t n, float sqrt_a, float sqrt_b, int mode, void* ws,
+                        int64_t ws_floats, int dtype, void* stream, const void* coef_dev);
+
+/* the same over the per-frame blends of nW sliding-window predictions: uncond / cond are the blends of the two halves of pred
+ * (layout, tables and preconditions of im360_cfg_ddim_step_windows), x is [outer, F, inner].  One uniform window with L = F writes
+ * the records of im360_cfg_apg_stats bit for bit (for any inner). */
+int im360_cfg_apg_stats_windows(const void* pred, const void* x, const void* start, const void* weight, int nW, int64_t outer,
+                                int64_t F, int64_t L, int64_t inner, float sqrt_a, float sqrt_b, int mode, void* ws,
+                                int64_t ws_floats, int dtype, void* stream, const void* coef_dev);
+
+/* the same with the windows on a ring of F frames.  Precondition: 0 <= start[k] < F, every frame covered, L <= F. */
+int im360_cfg_apg_stats_windows_ring(const void* pred, const void* x, const void* start, const void* weight, int nW, int64_t outer,
+                                     int64_t F, int64_t L, int64_t inner, float sqrt_a, float sqrt_b, int mode, void* ws,
+                                     int64_t ws_floats, int dtype, void* stream, const void* coef_dev);
+
+/* out[0 .. 2] = (alpha, s, lambda) on the device from the records a statistics pass over n elements left in ws: one workgroup, the
+ * merge every workgroup of a step makes (for tests and tools). */
+int im360_cfg_apg_scalars(const void* ws, int64_t ws_floats, int64_t n, float guidance, float sqrt_a, float sqrt_b, int mode,
+                          float eta, float threshold, void* out, void* stream, const void* coef_dev);
+
+/* im360_cfg_ddim_step on the projected guidance; ws: the records of im360_cfg_apg_stats for the same uncond / cond / x / n. */
+int im360_cfg_ddim_step_apg(const void* uncond, const void* cond, const void* x, const void* noise, void* out, int64_t n,
+                            float guidance, float sqrt_a, float sqrt_b, float sqrt_a_prev, float dir, float sigma, int mode, float eta,
+                            float threshold, const void* ws, int64_t ws_floats, int dtype, void* stream, const void* coef_dev);
+
+/* im360_cfg_ddim_step_windows (wrap = 0) / im360_cfg_ddim_step_windows_ring (wrap = F; any other wrap is refused) on the projected
+ * guidance of the blends; ws: the records of im360_cfg_apg_stats_windows(_ring) for the same clip.  One uniform window with L = F
+ * gives im360_cfg_ddim_step_apg's result bit for bit. */
+int im360_cfg_ddim_step_windows_apg(const void* pred, const void* x, const void* noise, void* out, const void* start,
+                                    const void* weight, int nW, int64_t outer, int64_t F, int64_t L, int64_t inner, int64_t wrap,
+                                    float guidance, float sqrt_a, float sqrt_b, float sqrt_a_prev, float dir, float sigma, int mode,
+                                    float eta, float threshold, const void* ws, int64_t ws_floats, int dtype, void* stream,
+                                    const void* coef_dev);
+
+/* im360_cfg_multistep_step on the projected guidance (hist <- its x0); ws: the records of im360_cfg_apg_stats. */
+int im360_cfg_multistep_step_apg(const void* uncond, const void* cond, const void* x, void* hist, void* out, int64_t n, float guidance,
+                                 float sqrt_a, float sqrt_b, float cx, float c0, float c1, int mode, float eta, float threshold,
+                                 const void* ws, int64_t ws_floats, int dtype, void* stream, const void* coef_dev);
+
+/* im360_cfg_multistep_step_windows on the projected guidance of the blends; wrap = 0 (line) or F (ring); ws: the records of
+ * im360_cfg_apg_stats_windows(_ring).  One uniform window with L = F gives im360_cfg_multistep_step_apg's out and hist bit for bit. */
+int im360_cfg_multistep_step_windows_apg(const void* pred, const void* x, void* hist, void* out, const void* start,
+                                         const void* weight, int nW, int64_t outer, int64_t F, int64_t L, int64_t inner, int64_t wrap,
+                                         float guidance, float sqrt_a, float sqrt_b, float cx, float c0, float c1, int mode, float eta,
+                                         float threshold, const void* ws, int64_t ws_floats, int dtype, void* stream,
+                                         const void* coef_dev);
+
 /* ---- start latents of a run that begins from a given clip (AnimationPipeline init_latents / init_video, strength < 1), one launch:
  *   out_pano[c, f, p]    = T(sqrt_a * x0[c, f, p] + sqrt_b * noise[f, c, p])        fp32, one rounding, at the store
  *   out_pers[m, c, f, q] = ok[m, q] ? out_pano[c, f, idx[m, q]] : 0                 the gather of the ROUNDED panorama start, bit for bit

@@ -530,6 +530,36 @@ def interval_bench(args, sch, dev, dt, ts_host):
     return res
 
 
+def apg_bench(args, sch, dev, dt, ts_host):
+    """--apg ETA [R] at cfg2 size (16 frames, 512 x 1024, bf16): the captured step with adaptive projected guidance (a statistics launch
+    and a step launch per branch), next to the plain captured step and the one with guidance_rescale = 0.7 (the same two-launch scheme),
+    replays alternated round by round.  The six-coefficient step kernel serves all three (eta = 0 without either option runs
+    ``cfg_ddim_update``: the shipped default, timed as `plain_step`)."""
+    from imagine360_amd.graph_step import GraphedDenoiseStep
+    frames = 16
+    apg = (float(args.apg[0]), float(args.apg[1]) if len(args.apg) > 1 else None)
+    assert len(args.apg) <= 2, "--apg ETA [R]"
+    res = dict(tool="bench_context --apg", apg_eta=apg[0], apg_threshold=apg[1], frames=frames, pano_hw=PANO_HW, pers_hw=PERS_HW, dtype="bfloat16",
+               device=torch.cuda.get_device_name(0), sampler=args.sampler)
+    mv = configs.build_mv_model(1, device=dev, dtype=dt, xformers=True)
+    mv.dual_stream, mv.warp_streams = True, True
+    inp = synthetic.mv_inputs(frames=frames, pano_hw=PANO_HW, pers_hw=PERS_HW, seed=1, dtype=dt, device=dev)
+    inp.pop("timestep")
+    cams = synthetic.icosahedron_cameras(90, PERS_PX, device=dev)
+    pano_lat, pers_lat = inp["pano_latent"][:1, :4].contiguous(), inp["latents"][:1, :, :4].contiguous()
+    graphs = dict(plain_step=GraphedDenoiseStep(mv, sch, inp, cams, pano_lat, pers_lat, 7.5, warmup=1),
+                  rescale_step=GraphedDenoiseStep(mv, sch, inp, cams, pano_lat, pers_lat, 7.5, warmup=1, guidance_rescale=0.7),
+                  apg_step=GraphedDenoiseStep(mv, sch, inp, cams, pano_lat, pers_lat, 7.5, warmup=1, guidance_apg=apg))
+    torch.cuda.synchronize()
+    res.update(time_steps(graphs, ts_host, args.steps, args.rounds))
+    res["finite"] = all(bool(torch.isfinite(g.pano_lat.float()).all() and torch.isfinite(g.pers_lat.float()).all()) for g in graphs.values())
+    res["apg_over_plain"] = res["apg_step"]["ms_median"] / res["plain_step"]["ms_median"]
+    res["apg_over_rescale"] = res["apg_step"]["ms_median"] / res["rescale_step"]["ms_median"]
+    res["note"] = ("randomly initialised weights: what APG does to a clip's look can only be judged with trained weights; host-clock ms around "
+                   "replays that end in a device synchronise")
+    return res
+
+
 def hires_bench(args, sch, dev, dt):
     """--init-scale N: the two-pass run (1 / N of the size from pure noise, then the full size from its latent at --strength) next to one
     run from pure noise at the full size; whole pipeline calls (encode, loop, decode), host clock around a call that ends in a device
@@ -733,6 +763,9 @@ def main():
                     help="FreeInit: pipeline calls with free_init_iters = N next to the plain call (--frames, --num-steps, --loop), and the filter kernel against its eager definition")
     ap.add_argument("--guidance-interval", type=float, nargs=2, default=None, metavar=("LO", "HI"),
                     help="guided and unguided captured steps of one 25-step run at cfg2 size, interleaved (--steps replays per round, --rounds)")
+    ap.add_argument("--apg", type=float, nargs="+", default=None, metavar="ETA [R]",
+                    help="the captured cfg2 step with adaptive projected guidance (apg_eta ETA, apg_threshold R; no R: no clamp) next to the plain "
+                         "and the guidance-rescale step, interleaved (--steps replays per round, --rounds)")
     ap.add_argument("--pano-hw", type=int, nargs=2, default=[128, 256], metavar=("H", "W"), help="--init-scale: latent size of the full-size run (default: cfg5)")
     ap.add_argument("--sampler", choices=["ddim", "dpmpp2m"], default="ddim", help="the scheduler of every step and call (dpmpp2m: DPM-Solver++ 2M)")
     ap.add_argument("--context-level", choices=["model", "attention", "both"], default=None,
@@ -751,6 +784,8 @@ def main():
     ts_host = [int(t) for t in sch._timesteps_host]
     if args.context_level is not None:
         return emit(level_bench(args, sch, dev, dt, ts_host), args.out)
+    if args.apg is not None:
+        return emit(apg_bench(args, sch, dev, dt, ts_host), args.out)
     if args.guidance_interval is not None:
         return emit(interval_bench(args, sch, dev, dt, ts_host), args.out)
     if args.free_init is not None:

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Per-kernel micro-benchmarks at BASELINE cfg2 shapes (run on the MI355X):
 
-    python tools/bench_kernels.py [attn] [conv] [temporal] [temporal_windows] [ln] [gn] [sampler_step] [unguided_step] [free_init_noise] [keep_release] [sphere_distance2] [--iters N]
+    python tools/bench_kernels.py [attn] [conv] [temporal] [temporal_windows] [ln] [gn] [sampler_step] [apg_step] [unguided_step] [free_init_noise] [keep_release] [sphere_distance2] [--iters N]
 
 Prints achieved TFLOP/s (MFMA kernels, vs 2500 dense bf16) or GB/s (HBM kernels, vs 8000) per shape.
 Usable under `rocprofv3 --pmc ...` for counters of one kernel class.
@@ -516,6 +516,44 @@ def bench_sampler_step(iters):
             base = base or ts[0]
             print(f"sampler_step {name} {n:8d} elements  {label:28s}: {ts[0] * 1e6:7.2f} us min {ts[2] * 1e6:7.2f} us median  "
                   f"{by / 1e6:6.2f} MB  {by / ts[0] / 1e9:6.0f} GB/s  {ts[0] / base:4.2f}x cfg_ddim_step")
+
+
+def bench_apg_step(iters):
+    """Adaptive projected guidance against the guidance rescale on the two latents of cfg2: each is a statistics launch + a step launch
+    (``K.cfg_ddim_step(..., apg=)`` / ``(..., rescale=)``), and so for the DPM-Solver++ 2M step; the plain single launch next to them.
+    Device events, workspace and result allocation included, 5 rounds alternated, min / median.  By bytes the APG pair moves 7 16-bit
+    streams (statistics: u, c, x; step: u, c, x, out), the rescaled pair 6, the plain launch 4.  A JSON line per row, for profiles/."""
+    import json
+    from imagine360_amd import configs
+    from imagine360_amd.scheduler import DDIMScheduler, DPMSolverMultistepScheduler
+    ddim, dpm = DDIMScheduler(**configs.NOISE_SCHEDULER_KWARGS), DPMSolverMultistepScheduler(**configs.NOISE_SCHEDULER_KWARGS)
+    ddim.set_timesteps(25), dpm.set_timesteps(25)
+    t = ddim._timesteps_host[8]
+    apg = (0.0, 0.5)
+    for name, shape in (("pano", (1, 4, 16, 64, 128)), ("pers", (1, 20, 4, 16, 32, 32))):
+        u, c, x = rn(*shape) * 0.25, rn(*shape) * 0.25, rn(*shape)
+        h = torch.zeros(shape, dtype=torch.float32, device=DEV)
+        n = x.numel()
+        mode = ddim.kernel_mode()
+        cd, c2 = ddim.step_coefficients(t, 0.0, 7.5), dpm.multistep_coefficients(dpm._timesteps_host, 8, 7.5)
+        rows = [("cfg_ddim_step", lambda: K.cfg_ddim_step(u, c, x, None, mode, cd), lambda: K.cfg_ddim_step(u, c, x, None, mode, cd, rescale=0.7),
+                 lambda: K.cfg_ddim_step(u, c, x, None, mode, cd, apg=apg), 0),
+                ("cfg_multistep_step order 2", lambda: K.cfg_multistep_step(u, c, x, h, mode, c2),
+                 lambda: K.cfg_multistep_step(u, c, x, h, mode, c2, rescale=0.7), lambda: K.cfg_multistep_step(u, c, x, h, mode, c2, apg=apg), 8 * n)]
+        for label, plain, rescaled, projected, extra in rows:
+            tp, tr, ta = [], [], []
+            for _ in range(5):                      # alternated
+                tp.append(timeit(plain, iters))
+                tr.append(timeit(rescaled, iters))
+                ta.append(timeit(projected, iters))
+            tp, tr, ta = sorted(tp), sorted(tr), sorted(ta)
+            row = dict(bench="apg_step", latent=name, elements=n, kernel=label, iters=iters, plain_us=[v * 1e6 for v in (tp[0], tp[2])],
+                       rescale_us=[v * 1e6 for v in (tr[0], tr[2])], apg_us=[v * 1e6 for v in (ta[0], ta[2])],
+                       plain_mb=(8 * n + extra) / 1e6, rescale_mb=(12 * n + extra) / 1e6, apg_mb=(14 * n + extra) / 1e6,
+                       apg_over_rescale_min=ta[0] / tr[0], apg_over_rescale_median=ta[2] / tr[2], apg_over_plain_min=ta[0] / tp[0])
+            print(f"apg_step {name} {n:8d} elements  {label:28s}: plain {tp[0] * 1e6:7.2f} us  rescale {tr[0] * 1e6:7.2f} us min {tr[2] * 1e6:7.2f} us median  "
+                  f"apg {ta[0] * 1e6:7.2f} us min {ta[2] * 1e6:7.2f} us median  | apg / rescale {ta[0] / tr[0]:4.2f}x min {ta[2] / tr[2]:4.2f}x median")
+            print("JSON", json.dumps(row))
 
 
 def bench_unguided_step(iters):
