@@ -28,7 +28,8 @@ extern "C" __attribute__((visibility("default"))) const char* im360_last_error(v
 // 4 (round 6): im360_groupnorm_partial_pad / im360_groupnorm_apply_partials; 5: the K-split entry points of the 3 x 3 convolutions
 // (still 5: im360_ff_fused -- the GEGLU feed-forward of the 320-channel blocks in one launch --, im360_tuning_get and knob ff_fused are
 //  ADDITIONS: no existing entry point changed its arguments or its meaning, so a caller written for version 5 runs unchanged; so are
-//  the eight im360_cfg_apg_* / im360_cfg_*_step*_apg entry points of adaptive projected guidance)
+//  the eight im360_cfg_apg_* / im360_cfg_*_step*_apg entry points of adaptive projected guidance and the seven *_apg_momentum /
+//  im360_cfg_apg_momentum_* entry points of its momentum)
 extern "C" __attribute__((visibility("default"))) int im360_abi_version(void) { return 5; }
 
 // bit 0: built with -DIM360_ABLATE (`make ablate`): the rejected A/B variants and the ablation kernels are in the library

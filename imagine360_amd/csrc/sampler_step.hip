@@ -541,7 +541,7 @@ __global__ __launch_bounds__(RS ? 256 : 1024) void cfg_multistep_step_windows_ke
     }
 }
 
-// ---- adaptive projected guidance (APG, arXiv 2410.02416, algorithm 1 without its momentum): the guidance difference is split into the
+// ---- adaptive projected guidance (APG, arXiv 2410.02416, algorithm 1; its momentum: the block behind these kernels): the guidance difference is split into the
 //      part parallel to the text branch's denoised prediction and the rest, the parallel part is scaled by eta, and the difference may
 //      be clamped to a radius.  The paper works on x0; mapped back to the model's output the x0 conversion's factor on the prediction
 //      cancels and what the step takes in place of u + g (c - u) is
@@ -841,6 +841,291 @@ __global__ __launch_bounds__(256) void cfg_multistep_step_windows_apg_kernel(con
             ((uint4*)out)[i] = pack8<T>(s);
         } else {
             hist[i] = h[0];
+            out[i] = from_f32<T>(s[0]);
+        }
+    }
+}
+
+// ---- APG with the paper's momentum (algorithm 1 in full): the guidance difference the projection and the clamp see is the running
+//      average of the run's guided steps, Dbar_t = Delta_t + beta Dbar_prev in x0 units.  The state is kept in the model-output units of
+//      the step that wrote it, e_t = Dbar_t / kp_t, so that the update is one fma and everything above holds with d replaced by e:
+//          e = d + carry e_prev,   carry = beta kp_prev / kp_t                         (0 on the first guided step of a run)
+//          alpha = sum e q / sum q^2,   s = min(1, r / (kp sqrt(sum e^2 / N))),   m = c + (g - 1) s e - lambda q
+//      `state`: float[n] indexed like the multistep history (the flat element index of the latent; windows: of the clip of blends),
+//      each element read and written by the thread that owns it, 16-byte lanes of 8 as hist_load8 / hist_store8.  The statistics pass
+//      reads it, the step reads it again, recomputes e with the same bits and stores the UNclamped e in place.  carry == 0 (uniform
+//      over the launch, like k.hist): the state is NOT read, only written, and e = d to the bit -- the records, the scalars and the
+//      step are those of the kernels above, and whatever the buffer held (NaN included) cannot leak.  carry is read from carry_dev[0]
+//      where that is given (hipGraph replay: it changes per step).  Kernels of their own beside the ones above, sharing their device
+//      functions: the shipped instantiations keep their names and their code.
+__device__ __forceinline__ float apg_carry(float carry, const float* __restrict__ carry_dev) {
+    return carry_dev != nullptr ? carry_dev[0] : carry;
+}
+
+// e and q of one element, the same bits in the statistics pass and in the step: apg_dq's d, then one fma of exactly these values
+__device__ __forceinline__ void apg_eq(float u, float c, float x, float rho, bool mom, float carry, float ep, float& e, float& q) {
+    apg_dq(u, c, x, rho, e, q);
+    if (mom) {
+        asm volatile("" : "+v"(ep));
+        e = __fmaf_rn(carry, ep, e);
+        asm volatile("" : "+v"(e));
+    }
+}
+
+// apg_add on e: a <- a + the cnt (1 .. 8) leading elements, in ascending order; ep[] is read with `mom` only
+__device__ __forceinline__ void apg_add_e(ApgSums& a, const float* u, const float* c, const float* x, const float* ep, int cnt, float rho,
+                                          bool mom, float carry) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        if (i < cnt) {
+            float e, q;
+            apg_eq(u[i], c[i], x[i], rho, mom, carry, mom ? ep[i] : 0.0f, e, q);
+            a.dq = __fmaf_rn(e, q, a.dq);
+            a.qq = __fmaf_rn(q, q, a.qq);
+            a.dd = __fmaf_rn(e, e, a.dd);
+        }
+    }
+    a.n += (float)cnt;
+}
+
+// apg_combine on e; `e` is what the state receives
+__device__ __forceinline__ float apg_combine_e(float u, float c, float x, float rho, const ApgScalars& a, bool mom, float carry, float ep,
+                                               float& e) {
+    float q;
+    apg_eq(u, c, x, rho, mom, carry, ep, e, q);
+    float p = a.gs * e;
+    asm volatile("" : "+v"(p));
+    float t = a.lam * q;
+    asm volatile("" : "+v"(t));
+    return add_kept(add_kept(c, p), -t);
+}
+
+// cfg_apg_stats_kernel with the state: reads state when carry != 0, never writes it
+template <typename T>
+__global__ __launch_bounds__(256) void cfg_apg_momentum_stats_kernel(const T* __restrict__ uncond, const T* __restrict__ cond,
+                                                                      const T* __restrict__ x, const float* __restrict__ state, long n8,
+                                                                      float sa, float sb, int mode, float carry,
+                                                                      const float* __restrict__ carry_dev, const float* __restrict__ coef,
+                                                                      float* __restrict__ ws) {
+    __shared__ ApgSums lds[4];
+    if (coef != nullptr) sa = coef[1], sb = coef[2];
+    carry = apg_carry(carry, carry_dev);
+    const bool mom = carry != 0.0f;
+    const float rho = apg_rho(mode & 3, sa, sb);
+    ApgSums a;
+    a.n = a.dq = a.qq = a.dd = 0.0f;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
+        float u[8], c[8], s[8], ep[8];
+        unpack8<T>(((const uint4*)uncond)[i], u);
+        unpack8<T>(((const uint4*)cond)[i], c);
+        unpack8<T>(((const uint4*)x)[i], s);
+        if (mom) hist_load8(state, i, ep);
+        apg_add_e(a, u, c, s, ep, 8, rho, mom, carry);
+    }
+    a = apg_block_reduce(a, lds);
+    if (threadIdx.x == 0) apg_store(ws, a);
+}
+
+// cfg_apg_stats_windows_kernel with the state [outer, F, inner] (groups of 8 for either V; V = 1 reads the state by element)
+template <typename T, int V>
+__global__ __launch_bounds__(256) void cfg_apg_momentum_stats_windows_kernel(const T* __restrict__ pred, const T* __restrict__ x,
+                                                                              const float* __restrict__ state, const int* __restrict__ start,
+                                                                              const float* __restrict__ weight, int nW, long outer, int F,
+                                                                              int L, int wrap, long inner, float sa, float sb, int mode,
+                                                                              float carry, const float* __restrict__ carry_dev,
+                                                                              const float* __restrict__ coef, float* __restrict__ ws) {
+    __shared__ ApgSums lds[4];
+    if (coef != nullptr) sa = coef[1], sb = coef[2];
+    carry = apg_carry(carry, carry_dev);
+    const bool mom = carry != 0.0f;
+    const float rho = apg_rho(mode & 3, sa, sb);
+    const long n = outer * F * inner, n8 = (n + 7) / 8;
+    const long half = outer * L * inner;
+    ApgSums a;
+    a.n = a.dq = a.qq = a.dd = 0.0f;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
+        float u[8], c[8], s[8], ep[8];
+        int cnt = 8;
+        if (V == 8) {
+            windows_blend<T, 8, true>(pred, start, weight, nW, F, L, wrap, inner, half, i * 8, 0.0f, u, c);
+            unpack8<T>(((const uint4*)x)[i], s);
+            if (mom) hist_load8(state, i, ep);
+        } else {
+            cnt = (int)(n - i * 8 < 8 ? n - i * 8 : 8);
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+                if (e < cnt) {
+                    windows_blend<T, 1, true>(pred, start, weight, nW, F, L, wrap, inner, half, i * 8 + e, 0.0f, &u[e], &c[e]);
+                    s[e] = to_f32<T>(x[i * 8 + e]);
+                    if (mom) ep[e] = state[i * 8 + e];
+                }
+        }
+        apg_add_e(a, u, c, s, ep, cnt, rho, mom, carry);
+    }
+    a = apg_block_reduce(a, lds);
+    if (threadIdx.x == 0) apg_store(ws, a);
+}
+
+// cfg_ddim_step_apg_kernel on e, state <- e
+template <typename T>
+__global__ __launch_bounds__(256) void cfg_ddim_step_apg_momentum_kernel(const T* __restrict__ uncond, const T* __restrict__ cond,
+                                     const T* __restrict__ x, const T* __restrict__ noise, float* __restrict__ state, T* __restrict__ out,
+                                     long n8, float g, float sa, float sb, float sap, float dir, float sigma, int mode,
+                                     const float* __restrict__ coef, const float* __restrict__ ws, int nrec, float eta, float r, float carry,
+                                     const float* __restrict__ carry_dev) {
+    const DdimCoefs k = ddim_coefs<true>(g, sa, sb, sap, dir, sigma, mode, coef);
+    const ApgScalars a = apg_scalars(ws, nrec, k.g, k.sa, k.sb, k.pred, eta, r);
+    const float rho = apg_rho(k.pred, k.sa, k.sb);
+    carry = apg_carry(carry, carry_dev);
+    const bool mom = carry != 0.0f;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
+        float u[8], c[8], s[8], z[8], ep[8];
+        unpack8<T>(((const uint4*)uncond)[i], u);
+        unpack8<T>(((const uint4*)cond)[i], c);
+        unpack8<T>(((const uint4*)x)[i], s);
+        if (noise != nullptr) unpack8<T>(((const uint4*)noise)[i], z);
+        else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) z[e] = 0.0f;
+        }
+        if (mom) hist_load8(state, i, ep);
+        else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) ep[e] = 0.0f;
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) s[e] = ddim_step_elem(apg_combine_e(u[e], c[e], s[e], rho, a, mom, carry, ep[e], ep[e]), s[e], z[e], k);
+        hist_store8(state, i, ep);
+        ((uint4*)out)[i] = pack8<T>(s);
+    }
+}
+
+// cfg_multistep_step_apg_kernel on e, state <- e
+template <typename T>
+__global__ __launch_bounds__(256) void cfg_multistep_step_apg_momentum_kernel(const T* __restrict__ uncond, const T* __restrict__ cond,
+                                     const T* __restrict__ x, float* __restrict__ hist, float* __restrict__ state, T* __restrict__ out, long n8,
+                                     float g, float sa, float sb, float cx, float c0, float c1, int mode, const float* __restrict__ coef,
+                                     const float* __restrict__ ws, int nrec, float eta, float r, float carry,
+                                     const float* __restrict__ carry_dev) {
+    const MultistepCoefs k = multistep_coefs<true>(g, sa, sb, cx, c0, c1, mode, coef);
+    const ApgScalars a = apg_scalars(ws, nrec, k.g, k.sa, k.sb, k.pred, eta, r);
+    const float rho = apg_rho(k.pred, k.sa, k.sb);
+    carry = apg_carry(carry, carry_dev);
+    const bool mom = carry != 0.0f;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
+        float u[8], c[8], s[8], h[8], ep[8];
+        unpack8<T>(((const uint4*)uncond)[i], u);
+        unpack8<T>(((const uint4*)cond)[i], c);
+        unpack8<T>(((const uint4*)x)[i], s);
+        if (k.hist) hist_load8(hist, i, h);
+        else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) h[e] = 0.0f;
+        }
+        if (mom) hist_load8(state, i, ep);
+        else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) ep[e] = 0.0f;
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) s[e] = multistep_step_elem(apg_combine_e(u[e], c[e], s[e], rho, a, mom, carry, ep[e], ep[e]), s[e], h[e], k);
+        hist_store8(hist, i, h);
+        hist_store8(state, i, ep);
+        ((uint4*)out)[i] = pack8<T>(s);
+    }
+}
+
+// cfg_ddim_step_windows_apg_kernel on e, state [outer, F, inner] <- e
+template <typename T, int V>
+__global__ __launch_bounds__(256) void cfg_ddim_step_windows_apg_momentum_kernel(const T* __restrict__ pred, const T* __restrict__ x,
+                                             const T* __restrict__ noise, float* __restrict__ state, T* __restrict__ out,
+                                             const int* __restrict__ start, const float* __restrict__ weight, int nW, long outer, int F, int L,
+                                             int wrap, long inner, float g, float sa, float sb, float sap, float dir, float sigma, int mode,
+                                             const float* __restrict__ coef, const float* __restrict__ ws, int nrec, float eta, float r,
+                                             float carry, const float* __restrict__ carry_dev) {
+    const DdimCoefs k = ddim_coefs<true>(g, sa, sb, sap, dir, sigma, mode, coef);
+    const ApgScalars a = apg_scalars(ws, nrec, k.g, k.sa, k.sb, k.pred, eta, r);
+    const float rho = apg_rho(k.pred, k.sa, k.sb);
+    carry = apg_carry(carry, carry_dev);
+    const bool mom = carry != 0.0f;
+    const long nv = outer * F * inner / V;
+    const long half = outer * L * inner;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
+        float u[V], c[V], s[V], z[V], ep[V];
+        windows_blend<T, V, true>(pred, start, weight, nW, F, L, wrap, inner, half, i * V, 0.0f, u, c);
+        if (V == 8) {
+            unpack8<T>(((const uint4*)x)[i], s);
+            if (noise != nullptr) unpack8<T>(((const uint4*)noise)[i], z);
+        } else {
+            s[0] = to_f32<T>(x[i]);
+            if (noise != nullptr) z[0] = to_f32<T>(noise[i]);
+        }
+        if (noise == nullptr) {
+#pragma unroll
+            for (int e = 0; e < V; ++e) z[e] = 0.0f;
+        }
+        if (mom) {
+            if (V == 8) hist_load8(state, i, ep);
+            else ep[0] = state[i];
+        } else {
+#pragma unroll
+            for (int e = 0; e < V; ++e) ep[e] = 0.0f;
+        }
+#pragma unroll
+        for (int e = 0; e < V; ++e) s[e] = ddim_step_elem(apg_combine_e(u[e], c[e], s[e], rho, a, mom, carry, ep[e], ep[e]), s[e], z[e], k);
+        if (V == 8) {
+            hist_store8(state, i, ep);
+            ((uint4*)out)[i] = pack8<T>(s);
+        } else {
+            state[i] = ep[0];
+            out[i] = from_f32<T>(s[0]);
+        }
+    }
+}
+
+// cfg_multistep_step_windows_apg_kernel on e, state [outer, F, inner] <- e
+template <typename T, int V>
+__global__ __launch_bounds__(256) void cfg_multistep_step_windows_apg_momentum_kernel(const T* __restrict__ pred, const T* __restrict__ x,
+                                             float* __restrict__ hist, float* __restrict__ state, T* __restrict__ out,
+                                             const int* __restrict__ start, const float* __restrict__ weight, int nW, long outer, int F, int L,
+                                             int wrap, long inner, float g, float sa, float sb, float cx, float c0, float c1, int mode,
+                                             const float* __restrict__ coef, const float* __restrict__ ws, int nrec, float eta, float r,
+                                             float carry, const float* __restrict__ carry_dev) {
+    const MultistepCoefs k = multistep_coefs<true>(g, sa, sb, cx, c0, c1, mode, coef);
+    const ApgScalars a = apg_scalars(ws, nrec, k.g, k.sa, k.sb, k.pred, eta, r);
+    const float rho = apg_rho(k.pred, k.sa, k.sb);
+    carry = apg_carry(carry, carry_dev);
+    const bool mom = carry != 0.0f;
+    const long nv = outer * F * inner / V;
+    const long half = outer * L * inner;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
+        float u[V], c[V], s[V], h[V], ep[V];
+        windows_blend<T, V, true>(pred, start, weight, nW, F, L, wrap, inner, half, i * V, 0.0f, u, c);
+        if (V == 8) unpack8<T>(((const uint4*)x)[i], s);
+        else s[0] = to_f32<T>(x[i]);
+        if (k.hist) {
+            if (V == 8) hist_load8(hist, i, h);
+            else h[0] = hist[i];
+        } else {
+#pragma unroll
+            for (int e = 0; e < V; ++e) h[e] = 0.0f;
+        }
+        if (mom) {
+            if (V == 8) hist_load8(state, i, ep);
+            else ep[0] = state[i];
+        } else {
+#pragma unroll
+            for (int e = 0; e < V; ++e) ep[e] = 0.0f;
+        }
+#pragma unroll
+        for (int e = 0; e < V; ++e) s[e] = multistep_step_elem(apg_combine_e(u[e], c[e], s[e], rho, a, mom, carry, ep[e], ep[e]), s[e], h[e], k);
+        if (V == 8) {
+            hist_store8(hist, i, h);
+            hist_store8(state, i, ep);
+            ((uint4*)out)[i] = pack8<T>(s);
+        } else {
+            hist[i] = h[0];
+            state[i] = ep[0];
             out[i] = from_f32<T>(s[0]);
         }
     }
@@ -1428,6 +1713,197 @@ extern "C" __attribute__((visibility("default"))) int im360_cfg_multistep_step_w
                                (hipStream_t)stream, (const T*)pred, (const T*)x, (float*)hist, (T*)out, (const int*)start, (const float*)weight, nW,
                                (long)outer, (int)F, (int)L, w.wrap, (long)inner, guidance, sqrt_a, sqrt_b, cx, c0, c1, mode,
                                (const float*)coef_dev, (const float*)ws, nrec, eta, threshold);
+        });
+        return im360_launch_status();
+    });
+}
+
+// ---- adaptive projected guidance with momentum: the statistics pass and the four guided steps on e = d + carry * state
+namespace im360 {
+// What an _apg_momentum entry point is given besides its _apg sibling's arguments: the fp32 state of n elements (read when carry != 0;
+// written by the steps, never by a statistics pass), the host carry and the optional device carry (float[1], read instead)
+struct ApgMomentum {
+    const void* state;
+    float carry;
+    const void* carry_dev;
+};
+// `vec`: the launch moves the state in 16-byte lanes
+static int check_apg_momentum(const char* name, const ApgMomentum& m, bool vec) {
+    IM360_CHECK_ARG(m.state && ((uintptr_t)m.state % (vec ? 16 : 4)) == 0, "%s: null or misaligned momentum state", name);
+    IM360_CHECK_ARG(std::isfinite(m.carry), "%s: apg carry=%g must be finite", name, (double)m.carry);
+    IM360_CHECK_ARG(((uintptr_t)m.carry_dev % 4) == 0, "%s: misaligned device carry", name);
+    return IM360_OK;
+}
+
+// im360_cfg_apg_momentum_stats_windows (w.wrap = 0) and _ring (w.wrap = F): checks, then the launch
+static int cfg_apg_momentum_stats_windows(const char* name, const Windows& w, const void* x, const ApgMomentum& m, float sa, float sb, int mode,
+                                          void* ws, int64_t ws_floats, int dtype, void* stream, const void* coef_dev) {
+    if (const int rc = check_windows(name, w, x != nullptr, nullptr)) return rc;
+    if (const int rc = check_apg_mode(name, mode)) return rc;
+    if (const int rc = check_rescale_ws(name, ws, ws_floats, w.elements())) return rc;
+    const bool vec = (w.inner % 8) == 0 && (((uintptr_t)w.pred | (uintptr_t)x | (uintptr_t)m.state) % 16) == 0;
+    if (const int rc = check_apg_momentum(name, m, vec)) return rc;
+    const unsigned blocks = (unsigned)im360_cfg_rescale_records(w.elements());
+    return with_dtype(dtype, name, [&](auto t) {
+        using T = typename decltype(t)::type;
+        with_const<1, 8>(vec ? 8 : 1, [&](auto v) {
+            hipLaunchKernelGGL((cfg_apg_momentum_stats_windows_kernel<T, decltype(v)::value>), dim3(blocks), dim3(256), 0, (hipStream_t)stream,
+                               (const T*)w.pred, (const T*)x, (const float*)m.state, (const int*)w.start, (const float*)w.weight, w.nW,
+                               (long)w.outer, (int)w.F, (int)w.L, w.wrap, (long)w.inner, sa, sb, mode, m.carry, (const float*)m.carry_dev,
+                               (const float*)coef_dev, (float*)ws);
+        });
+        return im360_launch_status();
+    });
+}
+}  // namespace im360
+
+// im360_cfg_apg_stats over e = (cond - uncond) + carry * state: the partial sums of e q, q^2 and e^2 -> ws
+extern "C" __attribute__((visibility("default"))) int im360_cfg_apg_momentum_stats(const void* uncond, const void* cond, const void* x,
+                                   const void* state, int64_t n, float sqrt_a, float sqrt_b, int mode, float carry, const void* carry_dev,
+                                   void* ws, int64_t ws_floats, int dtype, void* stream, const void* coef_dev) {
+    using namespace im360;
+    const char* name = "cfg_apg_momentum_stats";
+    if (const int rc = check_tensors(name, {uncond, cond, x}, nullptr, n)) return rc;
+    if (const int rc = check_apg_mode(name, mode)) return rc;
+    if (const int rc = check_rescale_ws(name, ws, ws_floats, n)) return rc;
+    if (const int rc = check_apg_momentum(name, ApgMomentum{state, carry, carry_dev}, true)) return rc;
+    const unsigned blocks = (unsigned)im360_cfg_rescale_records(n);
+    return with_dtype(dtype, name, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((cfg_apg_momentum_stats_kernel<T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const T*)uncond,
+                           (const T*)cond, (const T*)x, (const float*)state, (long)(n / 8), sqrt_a, sqrt_b, mode, carry,
+                           (const float*)carry_dev, (const float*)coef_dev, (float*)ws);
+        return im360_launch_status();
+    });
+}
+
+// the same over the per-frame blends of nW sliding-window predictions, state [outer, F, inner]
+extern "C" __attribute__((visibility("default"))) int im360_cfg_apg_momentum_stats_windows(const void* pred, const void* x, const void* state,
+                                   const void* start, const void* weight, int nW, int64_t outer, int64_t F, int64_t L, int64_t inner,
+                                   float sqrt_a, float sqrt_b, int mode, float carry, const void* carry_dev, void* ws, int64_t ws_floats,
+                                   int dtype, void* stream, const void* coef_dev) {
+    const im360::Windows w{pred, start, weight, nW, 0, outer, F, L, inner};
+    return im360::cfg_apg_momentum_stats_windows("cfg_apg_momentum_stats_windows", w, x, im360::ApgMomentum{state, carry, carry_dev}, sqrt_a,
+                                                 sqrt_b, mode, ws, ws_floats, dtype, stream, coef_dev);
+}
+
+// the same with the windows on a ring of F frames (preconditions of im360_cfg_ddim_step_windows_ring)
+extern "C" __attribute__((visibility("default"))) int im360_cfg_apg_momentum_stats_windows_ring(const void* pred, const void* x,
+                                   const void* state, const void* start, const void* weight, int nW, int64_t outer, int64_t F, int64_t L,
+                                   int64_t inner, float sqrt_a, float sqrt_b, int mode, float carry, const void* carry_dev, void* ws,
+                                   int64_t ws_floats, int dtype, void* stream, const void* coef_dev) {
+    const im360::Windows w{pred, start, weight, nW, (int)F, outer, F, L, inner};
+    return im360::cfg_apg_momentum_stats_windows("cfg_apg_momentum_stats_windows_ring", w, x, im360::ApgMomentum{state, carry, carry_dev},
+                                                 sqrt_a, sqrt_b, mode, ws, ws_floats, dtype, stream, coef_dev);
+}
+
+// im360_cfg_ddim_step_apg on e, state <- e; ws: the records of im360_cfg_apg_momentum_stats for the same tensors, state and carry
+extern "C" __attribute__((visibility("default"))) int im360_cfg_ddim_step_apg_momentum(const void* uncond, const void* cond, const void* x,
+                                   const void* noise, void* state, void* out, int64_t n, float guidance, float sqrt_a, float sqrt_b,
+                                   float sqrt_a_prev, float dir, float sigma, int mode, float eta, float threshold, const void* ws,
+                                   int64_t ws_floats, float carry, const void* carry_dev, int dtype, void* stream, const void* coef_dev) {
+    using namespace im360;
+    const char* name = "cfg_ddim_step_apg_momentum";
+    const StepArgs s{guidance, sqrt_a, sqrt_b, sqrt_a_prev, dir, sigma, mode, noise, coef_dev, nullptr, 0, 0.0f};
+    const ApgArgs a{eta, threshold, ws, ws_floats};
+    if (const int rc = check_tensors(name, {uncond, cond, x, out}, noise, n)) return rc;
+    if (const int rc = check_step(name, s)) return rc;
+    if (const int rc = check_apg(name, a, n)) return rc;
+    if (const int rc = check_apg_momentum(name, ApgMomentum{state, carry, carry_dev}, true)) return rc;
+    return with_dtype(dtype, name, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((cfg_ddim_step_apg_momentum_kernel<T>), dim3(step_blocks(n / 8)), dim3(256), 0, (hipStream_t)stream,
+                           (const T*)uncond, (const T*)cond, (const T*)x, (const T*)noise, (float*)state, (T*)out, (long)(n / 8), guidance,
+                           sqrt_a, sqrt_b, sqrt_a_prev, dir, sigma, mode, (const float*)coef_dev, (const float*)ws,
+                           (int)im360_cfg_rescale_records(n), eta, threshold, carry, (const float*)carry_dev);
+        return im360_launch_status();
+    });
+}
+
+// im360_cfg_ddim_step_windows_apg on e, state [outer, F, inner] <- e; wrap = 0 (line) or F (ring)
+extern "C" __attribute__((visibility("default"))) int im360_cfg_ddim_step_windows_apg_momentum(const void* pred, const void* x,
+                                   const void* noise, void* state, void* out, const void* start, const void* weight, int nW, int64_t outer,
+                                   int64_t F, int64_t L, int64_t inner, int64_t wrap, float guidance, float sqrt_a, float sqrt_b,
+                                   float sqrt_a_prev, float dir, float sigma, int mode, float eta, float threshold, const void* ws,
+                                   int64_t ws_floats, float carry, const void* carry_dev, int dtype, void* stream, const void* coef_dev) {
+    using namespace im360;
+    const char* name = "cfg_ddim_step_windows_apg_momentum";
+    const Windows w{pred, start, weight, nW, wrap == 0 ? 0 : (int)F, outer, F, L, inner};
+    const StepArgs s{guidance, sqrt_a, sqrt_b, sqrt_a_prev, dir, sigma, mode, noise, coef_dev, nullptr, 0, 0.0f};
+    const ApgArgs a{eta, threshold, ws, ws_floats};
+    if (const int rc = check_windows(name, w, x && out, &s)) return rc;
+    IM360_CHECK_ARG(wrap == 0 || wrap == F, "%s: wrap=%ld must be 0 (line) or F=%ld (ring)", name, (long)wrap, (long)F);
+    if (const int rc = check_apg(name, a, w.elements())) return rc;
+    const bool vec = (inner % 8) == 0 && (((uintptr_t)pred | (uintptr_t)x | (uintptr_t)noise | (uintptr_t)state | (uintptr_t)out) % 16) == 0;
+    if (const int rc = check_apg_momentum(name, ApgMomentum{state, carry, carry_dev}, vec)) return rc;
+    const long nv = (long)w.elements() / (vec ? 8 : 1);
+    const int nrec = (int)im360_cfg_rescale_records(w.elements());
+    return with_dtype(dtype, name, [&](auto t) {
+        using T = typename decltype(t)::type;
+        with_const<1, 8>(vec ? 8 : 1, [&](auto v) {
+            hipLaunchKernelGGL((cfg_ddim_step_windows_apg_momentum_kernel<T, decltype(v)::value>), dim3(step_blocks(nv)), dim3(256), 0,
+                               (hipStream_t)stream, (const T*)pred, (const T*)x, (const T*)noise, (float*)state, (T*)out, (const int*)start,
+                               (const float*)weight, nW, (long)outer, (int)F, (int)L, w.wrap, (long)inner, guidance, sqrt_a, sqrt_b,
+                               sqrt_a_prev, dir, sigma, mode, (const float*)coef_dev, (const float*)ws, nrec, eta, threshold, carry,
+                               (const float*)carry_dev);
+        });
+        return im360_launch_status();
+    });
+}
+
+// im360_cfg_multistep_step_apg on e (hist <- the x0 of its projected guidance), state <- e
+extern "C" __attribute__((visibility("default"))) int im360_cfg_multistep_step_apg_momentum(const void* uncond, const void* cond, const void* x,
+                                   void* hist, void* state, void* out, int64_t n, float guidance, float sqrt_a, float sqrt_b, float cx,
+                                   float c0, float c1, int mode, float eta, float threshold, const void* ws, int64_t ws_floats, float carry,
+                                   const void* carry_dev, int dtype, void* stream, const void* coef_dev) {
+    using namespace im360;
+    const char* name = "cfg_multistep_step_apg_momentum";
+    const MultistepArgs m{multistep_step_args(guidance, sqrt_a, sqrt_b, mode, 0.0f, nullptr, 0, coef_dev), cx, c0, c1, hist};
+    const ApgArgs a{eta, threshold, ws, ws_floats};
+    if (const int rc = check_tensors(name, {uncond, cond, x, hist, out}, nullptr, n)) return rc;
+    if (const int rc = check_step(name, m.s)) return rc;
+    if (const int rc = check_multistep(name, m, n)) return rc;
+    if (const int rc = check_apg(name, a, n)) return rc;
+    if (const int rc = check_apg_momentum(name, ApgMomentum{state, carry, carry_dev}, true)) return rc;
+    IM360_CHECK_ARG(state != hist, "%s: the momentum state and the history are one buffer", name);
+    return with_dtype(dtype, name, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((cfg_multistep_step_apg_momentum_kernel<T>), dim3(step_blocks(n / 8)), dim3(256), 0, (hipStream_t)stream,
+                           (const T*)uncond, (const T*)cond, (const T*)x, (float*)hist, (float*)state, (T*)out, (long)(n / 8), guidance, sqrt_a,
+                           sqrt_b, cx, c0, c1, mode, (const float*)coef_dev, (const float*)ws, (int)im360_cfg_rescale_records(n), eta,
+                           threshold, carry, (const float*)carry_dev);
+        return im360_launch_status();
+    });
+}
+
+// im360_cfg_multistep_step_windows_apg on e, state [outer, F, inner] <- e; wrap = 0 or F
+extern "C" __attribute__((visibility("default"))) int im360_cfg_multistep_step_windows_apg_momentum(const void* pred, const void* x, void* hist,
+                                   void* state, void* out, const void* start, const void* weight, int nW, int64_t outer, int64_t F, int64_t L,
+                                   int64_t inner, int64_t wrap, float guidance, float sqrt_a, float sqrt_b, float cx, float c0, float c1,
+                                   int mode, float eta, float threshold, const void* ws, int64_t ws_floats, float carry,
+                                   const void* carry_dev, int dtype, void* stream, const void* coef_dev) {
+    using namespace im360;
+    const char* name = "cfg_multistep_step_windows_apg_momentum";
+    const Windows w{pred, start, weight, nW, wrap == 0 ? 0 : (int)F, outer, F, L, inner};
+    const MultistepArgs m{multistep_step_args(guidance, sqrt_a, sqrt_b, mode, 0.0f, nullptr, 0, coef_dev), cx, c0, c1, hist};
+    const ApgArgs a{eta, threshold, ws, ws_floats};
+    if (const int rc = check_windows(name, w, x && hist && out, &m.s)) return rc;
+    IM360_CHECK_ARG(wrap == 0 || wrap == F, "%s: wrap=%ld must be 0 (line) or F=%ld (ring)", name, (long)wrap, (long)F);
+    IM360_CHECK_ARG(((uintptr_t)hist % 4) == 0, "%s: misaligned history", name);
+    if (const int rc = check_multistep(name, m, w.elements())) return rc;
+    if (const int rc = check_apg(name, a, w.elements())) return rc;
+    const bool vec = (inner % 8) == 0 && (((uintptr_t)pred | (uintptr_t)x | (uintptr_t)hist | (uintptr_t)state | (uintptr_t)out) % 16) == 0;
+    if (const int rc = check_apg_momentum(name, ApgMomentum{state, carry, carry_dev}, vec)) return rc;
+    IM360_CHECK_ARG(state != hist, "%s: the momentum state and the history are one buffer", name);
+    const long nv = (long)w.elements() / (vec ? 8 : 1);
+    const int nrec = (int)im360_cfg_rescale_records(w.elements());
+    return with_dtype(dtype, name, [&](auto t) {
+        using T = typename decltype(t)::type;
+        with_const<1, 8>(vec ? 8 : 1, [&](auto v) {
+            hipLaunchKernelGGL((cfg_multistep_step_windows_apg_momentum_kernel<T, decltype(v)::value>), dim3(step_blocks(nv)), dim3(256), 0,
+                               (hipStream_t)stream, (const T*)pred, (const T*)x, (float*)hist, (float*)state, (T*)out, (const int*)start,
+                               (const float*)weight, nW, (long)outer, (int)F, (int)L, w.wrap, (long)inner, guidance, sqrt_a, sqrt_b, cx, c0,
+                               c1, mode, (const float*)coef_dev, (const float*)ws, nrec, eta, threshold, carry, (const float*)carry_dev);
         });
         return im360_launch_status();
     });

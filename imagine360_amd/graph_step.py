@@ -11,6 +11,9 @@ sqrt b_t, sqrt a_prev, dir, sigma) for ``cfg_ddim_step``.  Guidance rescale (``g
 statistics launch in front of each branch's step launch; its workspace is a graph-pool tensor and nothing more is uploaded.
 Adaptive projected guidance (``guidance_apg``) is captured the same way: its statistics launch and its step launch per branch read
 sqrt a_t, sqrt b_t and the guidance from the six uploaded coefficients; only the guided graph of a guidance interval holds them.
+Its momentum (``guidance_apg_momentum`` = beta) adds one fp32 state per branch, updated in place by the captured step launch, and a
+one-float device carry (``scheduler.apg_carry``) that ``step`` computes on the host for every GUIDED step and uploads through a pinned
+ring of its own; a carry of 0 makes the kernels write the state without reading it, so no buffer is ever cleared.
 A partly regenerated clip (``keep``, pipeline ``regenerate_mask``) adds one captured ``keep_latents`` launch after the two step launches;
 its two coefficients are a fifth tiny buffer, refreshed per step through a pinned ring of its own.  A release-mode region
 (``regenerate_mode="release"``) captures ``keep_latents_release`` in its place and uploads three: the step's threshold rides along.
@@ -51,7 +54,7 @@ class GraphedDenoiseStep:
 
     def __init__(self, mv, scheduler, inputs, cameras, pano_latent, pers_latent, guidance, use_fps=True, warmup=2, cfg_pair=None,
                  eta=0.0, generator=None, use_clipped_model_output=False, frame_shard=None, guidance_rescale=0.0, keep=None,
-                 guidance_interval=None, steps=None, guidance_apg=None):
+                 guidance_interval=None, steps=None, guidance_apg=None, guidance_apg_momentum=None):
         """``inputs``: the keyword tensors of MultiViewBaseModel.forward (CFG-batched, resident on the GPU);
         ``pano_latent`` [1,4,F,H,W] / ``pers_latent`` [1,m,4,F,h,w]: initial noisy latents.
         Frame-sharded models (``mv.set_frame_shard``) capture their all-to-alls with the step: the exchange buffers are
@@ -61,6 +64,10 @@ class GraphedDenoiseStep:
         ``eta`` / ``generator`` / ``use_clipped_model_output``: DDIMScheduler.step's keywords (defaults: the eta = 0 update).
         ``frame_shard`` (dist.FrameShard): with eta > 0 the variance noise is drawn for the whole clip and cut to the local
         frames, like the initial noise.  ``guidance_rescale`` / ``guidance_apg``: ``DDIMScheduler.fused_cfg_step``'s keywords.
+        ``guidance_apg_momentum`` (None or beta, with ``guidance_apg`` only): the momentum of the projected guidance.  The step owns one
+        state per branch and the device carry; ``step(t)`` uploads ``apg_carry(previous guided timestep, t, beta)`` before a guided step
+        -- 0 on the first guided step after construction and after ``restart`` -- and an unguided step leaves carry, states and
+        predecessor alone.
         ``keep`` (pipeline.KeepRegion): the kept region of a given clip, blended into both latents after the two updates.
         ``guidance_interval`` (None: every step guided, one graph, nothing else runs) with ``steps``, the run's timestep list: the kinds
         of step the run holds (``scheduler.guided_steps``) are each warmed up and captured once.  The caller keeps
@@ -72,6 +79,10 @@ class GraphedDenoiseStep:
         self.apg = guidance_apg
         if guidance_apg is not None and frame_shard is not None:
             raise ValueError("guidance_apg cannot be combined with frame_shard (its sums span all frames)")
+        self.apg_beta = None if guidance_apg_momentum is None else float(guidance_apg_momentum)
+        if self.apg_beta is not None and guidance_apg is None:
+            raise ValueError("guidance_apg_momentum needs guidance_apg (the momentum is that of the projected guidance)")
+        self._apg_prev_t = None                  # the previous guided timestep of the run; None: the next guided step has carry 0
         self.interval = guidance_interval
         kinds = [True]                           # True: the CFG-batch body, False: the text-half body
         if guidance_interval is not None:
@@ -92,6 +103,12 @@ class GraphedDenoiseStep:
         # a multistep scheduler's x0 histories, one per branch (None: DDIM).  The warm-up below runs a first-order step, which only
         # writes them, and so does the first step of every run: no reset after warm-up or capture
         self.hist = (scheduler.new_history(self.pano_lat), scheduler.new_history(self.pers_lat)) if hasattr(scheduler, "new_history") else None
+        # the momentum states of the projected guidance, one per branch, and the device carry.  Never cleared: the carry buffer is 0
+        # through warm-up and capture (``step`` alone uploads it), and a carry of 0 writes the states without reading them
+        if self.apg_beta is not None:
+            self.apg_state = (scheduler.new_apg_state(self.pano_lat), scheduler.new_apg_state(self.pers_lat))
+            self.apg_carry = torch.zeros(1, dtype=torch.float32, device=dev)
+            self._up_apg = _PinnedUploads(self.apg_carry)
         self.timestep = torch.zeros(1, dtype=torch.int64, device=dev)
         self.coef = torch.zeros(6 if self.step_kernel else 3, dtype=torch.float32, device=dev)
         self.use_fps = use_fps
@@ -172,9 +189,9 @@ class GraphedDenoiseStep:
         pred_pano, pred_pers = pred_pano.to(ldt), pred_pers.to(ldt)
         kw = dict(eta=self.eta, use_clipped_model_output=self.clipped, guidance_rescale=self.rescale, **self._apg_kw())
         new_pano = self.sch.fused_cfg_step(pred_pano[0:1], pred_pano[1:2], self.g, None, self.pano_lat, coef_dev=self.coef,
-                                           noise=self._noise(self.pano_lat, mdt, 2), **kw, **self._history(0))
+                                           noise=self._noise(self.pano_lat, mdt, 2), **kw, **self._history(0), **self._apg_momentum(0))
         new_pers = self.sch.fused_cfg_step(pred_pers[0:1], pred_pers[1:2], self.g, None, self.pers_lat, coef_dev=self.coef,
-                                           noise=self._noise(self.pers_lat, mdt, 3), **kw, **self._history(1))
+                                           noise=self._noise(self.pers_lat, mdt, 3), **kw, **self._history(1), **self._apg_momentum(1))
         self._keep(new_pano, new_pers)
         self.pano_lat.copy_(new_pano)
         self.pers_lat.copy_(new_pers)
@@ -220,6 +237,19 @@ class GraphedDenoiseStep:
         """``guidance_apg=`` of the scheduler calls, left out when it is off: they are then made with exactly the keywords of before."""
         return {} if self.apg is None else dict(guidance_apg=self.apg)
 
+    def _apg_momentum(self, branch):
+        """``guidance_apg_momentum=`` / ``carry_dev=`` of one branch's GUIDED step call; nothing without momentum.  The host carry is
+        not read: the kernels take the uploaded one."""
+        return {} if self.apg_beta is None else dict(guidance_apg_momentum=(self.apg_state[branch], 0.0), carry_dev=self.apg_carry)
+
+    def _upload_apg_carry(self, t_host):
+        """The carry of the guided step at ``t_host``, from the previous guided timestep of the run, which ``t_host`` then becomes.  An
+        unguided step uploads nothing and is no predecessor."""
+        if self.apg_beta is None or (self.interval is not None and not self.sch.guided_steps([t_host], self.interval)[0]):
+            return
+        self._up_apg.upload(self.apg_carry, [self.sch.apg_carry(self._apg_prev_t, t_host, self.apg_beta)])
+        self._apg_prev_t = t_host
+
     def _history(self, branch):
         """``history=`` of one branch's step call (0 panorama, 1 perspective); nothing with a scheduler that keeps none."""
         return {} if self.hist is None else dict(history=self.hist[branch])
@@ -254,13 +284,16 @@ class GraphedDenoiseStep:
     def step(self, t_host):
         """Advance the latents by one DDIM step at (host int) timestep ``t_host``."""
         self._upload(t_host)
+        self._upload_apg_carry(t_host)
         self._graph_for(t_host).replay()
         return self.pano_lat, self.pers_lat
 
     def restart(self, pano_latent, pers_latent):
         """Another run of the schedule on the captured step (pipeline ``free_init_iters``): the given start latents are copied into the
         static ones -- no new capture, no warm-up (both graphs of a guidance interval read them).  ``step`` returns the static buffers, so a caller that keeps a result clones it
-        first.  A multistep scheduler's histories need no reset: the first step of a run is first order and only writes them."""
+        first.  A multistep scheduler's histories need no reset: the first step of a run is first order and only writes them.  Nor do
+        the momentum states of the projected guidance: the run's first guided step gets carry 0 and only writes them."""
+        self._apg_prev_t = None
         self.pano_lat.copy_(pano_latent)
         self.pers_lat.copy_(pers_latent)
 
@@ -279,7 +312,7 @@ class GraphedWindowedStep(GraphedDenoiseStep):
 
     def __init__(self, mv, scheduler, inputs, cameras, pano_latent, pers_latent, guidance, plan, use_fps=True, warmup=1, eta=0.0,
                  generator=None, use_clipped_model_output=False, guidance_rescale=0.0, keep=None, guidance_interval=None, steps=None,
-                 guidance_apg=None):
+                 guidance_apg=None, guidance_apg_momentum=None):
         dev = pano_latent.device
         self.plan = plan
         self.static = plan.static_inputs(inputs)
@@ -294,7 +327,8 @@ class GraphedWindowedStep(GraphedDenoiseStep):
         self._up_k = _PinnedUploads(self.coins)
         super().__init__(mv, scheduler, inputs, cameras, pano_latent, pers_latent, guidance, use_fps=use_fps, warmup=warmup, eta=eta,
                          generator=generator, use_clipped_model_output=use_clipped_model_output, guidance_rescale=guidance_rescale, keep=keep,
-                         guidance_interval=guidance_interval, steps=steps, guidance_apg=guidance_apg)
+                         guidance_interval=guidance_interval, steps=steps, guidance_apg=guidance_apg,
+                         guidance_apg_momentum=guidance_apg_momentum)
 
     def _body_text(self):
         inp = self.inp_text
@@ -328,9 +362,11 @@ class GraphedWindowedStep(GraphedDenoiseStep):
         kw = dict(coef_dev=self.coef, eta=self.eta, use_clipped_model_output=self.clipped, guidance_rescale=self.rescale,
                   ring=self.plan.loop, **self._apg_kw())
         new_pano = self.sch.fused_cfg_step_windows(self.preds_pano, self.plan.starts_dev, self.plan.weights, self.g, None,
-                                                   self.pano_lat, noise=self._noise(self.pano_lat, mdt, 2), **kw, **self._history(0))
+                                                   self.pano_lat, noise=self._noise(self.pano_lat, mdt, 2), **kw, **self._history(0),
+                                                   **self._apg_momentum(0))
         new_pers = self.sch.fused_cfg_step_windows(self.preds_pers, self.plan.starts_dev, self.plan.weights, self.g, None,
-                                                   self.pers_lat, noise=self._noise(self.pers_lat, mdt, 3), **kw, **self._history(1))
+                                                   self.pers_lat, noise=self._noise(self.pers_lat, mdt, 3), **kw, **self._history(1),
+                                                   **self._apg_momentum(1))
         self._keep(new_pano, new_pers)
         self.pano_lat.copy_(new_pano)
         self.pers_lat.copy_(new_pers)

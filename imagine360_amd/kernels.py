@@ -83,6 +83,19 @@ _SIGNATURES = {
     "im360_cfg_multistep_step_apg": (_INT, [_PTR] * 5 + [_I64] + [_F32] * 6 + [_INT, _F32, _F32, _PTR, _I64, _INT, _PTR, _PTR]),
     "im360_cfg_multistep_step_windows_apg": (_INT, [_PTR] * 6 + [_INT] + [_I64] * 5 + [_F32] * 6 + [_INT, _F32, _F32, _PTR, _I64, _INT,
                                                                                                    _PTR, _PTR]),
+    "im360_cfg_apg_momentum_stats": (_INT, [_PTR] * 4 + [_I64, _F32, _F32, _INT, _F32, _PTR, _PTR, _I64, _INT, _PTR, _PTR]),
+    "im360_cfg_apg_momentum_stats_windows": (_INT, [_PTR] * 5 + [_INT] + [_I64] * 4 + [_F32, _F32, _INT, _F32, _PTR, _PTR, _I64, _INT, _PTR,
+                                                                                        _PTR]),
+    "im360_cfg_apg_momentum_stats_windows_ring": (_INT, [_PTR] * 5 + [_INT] + [_I64] * 4 + [_F32, _F32, _INT, _F32, _PTR, _PTR, _I64, _INT,
+                                                                                             _PTR, _PTR]),
+    "im360_cfg_ddim_step_apg_momentum": (_INT, [_PTR] * 6 + [_I64] + [_F32] * 6 + [_INT, _F32, _F32, _PTR, _I64, _F32, _PTR, _INT, _PTR,
+                                                                                   _PTR]),
+    "im360_cfg_ddim_step_windows_apg_momentum": (_INT, [_PTR] * 7 + [_INT] + [_I64] * 5 + [_F32] * 6 + [_INT, _F32, _F32, _PTR, _I64, _F32,
+                                                                                                        _PTR, _INT, _PTR, _PTR]),
+    "im360_cfg_multistep_step_apg_momentum": (_INT, [_PTR] * 6 + [_I64] + [_F32] * 6 + [_INT, _F32, _F32, _PTR, _I64, _F32, _PTR, _INT,
+                                                                                        _PTR, _PTR]),
+    "im360_cfg_multistep_step_windows_apg_momentum": (_INT, [_PTR] * 7 + [_INT] + [_I64] * 5 + [_F32] * 6 + [_INT, _F32, _F32, _PTR, _I64,
+                                                                                                             _F32, _PTR, _INT, _PTR, _PTR]),
     "im360_noise_latents": (_INT, [_PTR] * 6 + [_I64] * 5 + [_F32, _F32, _INT, _PTR]),
     "im360_keep_latents": (_INT, [_PTR] * 7 + [_I64] * 5 + [_F32, _F32, _INT, _PTR, _PTR]),
     "im360_keep_latents_release": (_INT, [_PTR] * 7 + [_I64] * 5 + [_F32, _F32, _F32, _INT, _PTR, _PTR]),
@@ -1035,6 +1048,40 @@ def _apg_stats_windows(preds, sample, starts, weights, geometry, mode, coefs, co
     return ws
 
 
+def _apg_momentum_args(who, apg, apg_momentum, carry_dev, sample):
+    """``apg_momentum = (state, carry)`` / ``carry_dev`` of the guided step wrappers after their checks: ``state`` float32, contiguous,
+    on ``sample``'s device and of its element count (the momentum state, ``scheduler.new_apg_state``), ``carry`` a finite float,
+    ``carry_dev`` None or a device float32[1] read instead.  Refused without ``apg``: the momentum is that of the projected guidance."""
+    if apg is None:
+        raise ValueError(f"{who}: apg_momentum needs apg (the momentum is that of the projected guidance)")
+    state, carry = apg_momentum
+    carry = float(carry)
+    if not math.isfinite(carry):
+        raise ValueError(f"{who}: apg carry={carry} must be finite")
+    _dev(state, carry_dev)
+    assert state.dtype == torch.float32 and state.is_contiguous() and state.device == sample.device and state.numel() == sample.numel()
+    if carry_dev is not None:
+        assert carry_dev.dtype == torch.float32 and carry_dev.numel() == 1 and carry_dev.is_cuda
+    return state, carry
+
+
+def _apg_momentum_stats(uncond, cond, sample, state, carry, carry_dev, mode, coefs, coef_dev):
+    ws = _rescale_workspace(sample)
+    rc = lib().im360_cfg_apg_momentum_stats(_p(uncond), _p(cond), _p(sample), _p(state), sample.numel(), float(coefs[1]), float(coefs[2]),
+                                            int(mode), carry, _p(carry_dev), _p(ws), ws.numel(), _dt(sample), _stream(), _p(coef_dev))
+    _check(rc, "im360_cfg_apg_momentum_stats")
+    return ws
+
+
+def _apg_momentum_stats_windows(preds, sample, state, carry, carry_dev, starts, weights, geometry, mode, coefs, coef_dev, ring):
+    ws = _rescale_workspace(sample)
+    name = "im360_cfg_apg_momentum_stats_windows_ring" if ring else "im360_cfg_apg_momentum_stats_windows"
+    rc = getattr(lib(), name)(_p(preds), _p(sample), _p(state), _p(starts), _p(weights), *geometry, float(coefs[1]), float(coefs[2]),
+                              int(mode), carry, _p(carry_dev), _p(ws), ws.numel(), _dt(sample), _stream(), _p(coef_dev))
+    _check(rc, name)
+    return ws
+
+
 def _apg_scalars(ws, like, mode, coefs, apg, coef_dev):
     """(alpha, s, lambda) from the records ``ws`` of a statistics pass over ``like``: a device float32[3]."""
     eta, threshold = _apg_args("cfg_apg_scalars", apg)
@@ -1045,16 +1092,21 @@ def _apg_scalars(ws, like, mode, coefs, apg, coef_dev):
     return out
 
 
-def cfg_apg_scalars(uncond, cond, sample, mode, coefs, apg, coef_dev=None):
+def cfg_apg_scalars(uncond, cond, sample, mode, coefs, apg, coef_dev=None, apg_momentum=None, carry_dev=None):
     """The three scalars of adaptive projected guidance (arXiv 2410.02416; ``cfg_ddim_step(..., apg=)``) as a device float32[3], no
     synchronisation: ``alpha = <d, q> / <q, q>``, the clamp factor ``s`` and ``lambda = (g - 1) s (1 - eta) alpha`` with d = cond -
     uncond and q = cond + rho * sample, the sums over the whole tensor in fp32.  Two launches: the statistics pass the step wrappers
     run, then the merge of its records that every workgroup of the step kernel makes -- the bits the step uses.  ``mode`` / ``coefs``:
     those of the step (only the prediction type and the first three coefficients are read); ``apg = (eta, threshold)``;
-    ``coef_dev``: device float32[6] whose first three elements are read instead."""
+    ``coef_dev``: device float32[6] whose first three elements are read instead.  ``apg_momentum = (state, carry)`` / ``carry_dev``: the
+    scalars of the step with momentum (``cfg_ddim_step``), d replaced by e = d + carry * state; the state is read, never written."""
     _dev(uncond, cond, sample, coef_dev)
     assert uncond.is_contiguous() and cond.is_contiguous() and sample.is_contiguous()
     assert uncond.shape == cond.shape == sample.shape and uncond.dtype == cond.dtype == sample.dtype
+    if apg_momentum is not None:
+        state, carry = _apg_momentum_args("cfg_apg_scalars", apg, apg_momentum, carry_dev, sample)
+        return _apg_scalars(_apg_momentum_stats(uncond, cond, sample, state, carry, carry_dev, mode, coefs, coef_dev), sample, mode, coefs,
+                            apg, coef_dev)
     return _apg_scalars(_apg_stats(uncond, cond, sample, mode, coefs, coef_dev), sample, mode, coefs, apg, coef_dev)
 
 
@@ -1068,7 +1120,7 @@ def _check_step_noise(who, sample, noise, coefs, coef_dev):
         assert coef_dev.dtype == torch.float32 and coef_dev.numel() == 6 and coef_dev.is_cuda
 
 
-def cfg_ddim_step(uncond, cond, sample, noise, mode, coefs, coef_dev=None, rescale=0.0, apg=None):
+def cfg_ddim_step(uncond, cond, sample, noise, mode, coefs, coef_dev=None, rescale=0.0, apg=None, apg_momentum=None, carry_dev=None):
     """DDIMScheduler.step(uncond + g (cond - uncond), t, sample) for any prediction type / clip / eta in one pass.
     ``mode``: DDIM_PRED_MODE | DDIM_CLIP_SAMPLE | DDIM_CLIPPED_OUTPUT; ``coefs`` = (guidance, sqrt_a, sqrt_b, sqrt_a_prev,
     dir, sigma) (DDIMScheduler.step_coefficients); ``noise``: variance noise like ``sample`` or None (zero noise, refused
@@ -1076,16 +1128,30 @@ def cfg_ddim_step(uncond, cond, sample, noise, mode, coefs, coef_dev=None, resca
     ``rescale`` != 0: guidance rescale (arXiv 2305.08891, 3.4) -- the step sees r (uncond + g (cond - uncond)) with
     r = rescale * std(cond) / std(uncond + g (cond - uncond)) + (1 - rescale) over the whole tensor; a statistics launch in front of
     the step launch, no host read.  0 is the single launch without it.
-    ``apg = (eta, threshold)``: adaptive projected guidance (arXiv 2410.02416, algorithm 1 without momentum) -- the step sees
+    ``apg = (eta, threshold)``: adaptive projected guidance (arXiv 2410.02416, algorithm 1) -- the step sees
     ``cond + (g - 1) s d - lambda q`` (``cfg_apg_scalars``) in place of the combination: the guidance difference split along the text
     branch's denoised prediction, its parallel part scaled by ``eta``, its RMS in x0 units clamped to ``threshold`` (None: no clamp);
     a statistics launch over (uncond, cond, sample) in front of the step launch.  None is the call without it; refused together with
-    ``rescale`` != 0."""
+    ``rescale`` != 0.
+    ``apg_momentum = (state, carry)`` (with ``apg`` only; None: the calls without it): the paper's momentum -- d is replaced by
+    ``e = d + carry * state`` in the sums and in the combination, and ``state`` (float32, contiguous, ``sample``'s element count;
+    ``scheduler.new_apg_state``) receives the unclamped e in place.  ``carry`` = ``scheduler.apg_carry(t_prev, t, beta)``; 0 (the
+    first guided step of a run): the state is not read, only written, and the result is that of ``apg`` alone bit for bit.
+    ``carry_dev``: device float32[1] read instead of ``carry`` (graph replay)."""
     _dev(uncond, cond, sample, noise)
     assert uncond.is_contiguous() and cond.is_contiguous() and sample.is_contiguous()
     assert uncond.shape == cond.shape == sample.shape and uncond.dtype == cond.dtype == sample.dtype
     _check_step_noise("cfg_ddim_step", sample, noise, coefs, coef_dev)
     out = torch.empty(sample.shape, dtype=sample.dtype, device=sample.device)
+    if apg_momentum is not None:
+        state, carry = _apg_momentum_args("cfg_ddim_step", apg, apg_momentum, carry_dev, sample)
+        eta, threshold = _apg_args("cfg_ddim_step", apg, rescale)
+        ws = _apg_momentum_stats(uncond, cond, sample, state, carry, carry_dev, mode, coefs, coef_dev)
+        rc = lib().im360_cfg_ddim_step_apg_momentum(_p(uncond), _p(cond), _p(sample), _p(noise), _p(state), _p(out), sample.numel(),
+                                                    *(float(v) for v in coefs), int(mode), eta, threshold, _p(ws), ws.numel(), carry,
+                                                    _p(carry_dev), _dt(sample), _stream(), _p(coef_dev))
+        _check(rc, "im360_cfg_ddim_step_apg_momentum")
+        return out
     if apg is not None:
         eta, threshold = _apg_args("cfg_ddim_step", apg, rescale)
         ws = _apg_stats(uncond, cond, sample, mode, coefs, coef_dev)
@@ -1138,17 +1204,23 @@ def cfg_rescale_factor_windows(preds, sample, starts, weights, guidance, rescale
     return _rescale_factor(_rescale_stats_windows(preds, sample, starts, weights, geometry, guidance, coef_dev, ring), sample, rescale)
 
 
-def cfg_apg_scalars_windows(preds, sample, starts, weights, mode, coefs, apg, coef_dev=None, ring=False):
+def cfg_apg_scalars_windows(preds, sample, starts, weights, mode, coefs, apg, coef_dev=None, ring=False, apg_momentum=None, carry_dev=None):
     """``cfg_apg_scalars`` over the per-frame blends of sliding-window predictions (arguments of ``cfg_ddim_step_windows``): the
     statistics pass ``cfg_ddim_step_windows(..., apg=)`` runs over the blends of both halves and ``sample``, then the merge every
-    workgroup of its step kernel makes.  A device float32[3], no synchronisation.  ``ring``: the windows lie on a ring."""
+    workgroup of its step kernel makes.  A device float32[3], no synchronisation.  ``ring``: the windows lie on a ring.
+    ``apg_momentum`` / ``carry_dev``: as in ``cfg_apg_scalars``, the state in ``sample``'s layout."""
     _dev(preds, sample, starts, weights, coef_dev)
     geometry = _windows_geometry(preds, sample, starts, weights)
+    if apg_momentum is not None:
+        state, carry = _apg_momentum_args("cfg_apg_scalars_windows", apg, apg_momentum, carry_dev, sample)
+        return _apg_scalars(_apg_momentum_stats_windows(preds, sample, state, carry, carry_dev, starts, weights, geometry, mode, coefs,
+                                                        coef_dev, ring), sample, mode, coefs, apg, coef_dev)
     return _apg_scalars(_apg_stats_windows(preds, sample, starts, weights, geometry, mode, coefs, coef_dev, ring), sample, mode, coefs, apg,
                         coef_dev)
 
 
-def cfg_ddim_step_windows(preds, sample, noise, starts, weights, mode, coefs, coef_dev=None, rescale=0.0, ring=False, apg=None):
+def cfg_ddim_step_windows(preds, sample, noise, starts, weights, mode, coefs, coef_dev=None, rescale=0.0, ring=False, apg=None,
+                          apg_momentum=None, carry_dev=None):
     """``cfg_ddim_step`` on the per-frame weighted blend of sliding-window predictions, one pass.  ``sample`` (and ``noise`` /
     the result): a panorama latent [1, 4, F, H, W] or a perspective latent [1, m, 4, F, h, w];  ``preds`` [nW, 2, *sample.shape
     with F -> L]: window k's CFG-batched prediction in slot k;  ``starts`` device int32 [nW] ascending window start frames
@@ -1157,11 +1229,22 @@ def cfg_ddim_step_windows(preds, sample, noise, starts, weights, mode, coefs, co
     halves blended with the same weights), a statistics launch in front of the step launch.  ``ring``: the windows lie on a ring
     of F frames (context.context_windows(loop=True)) -- window k covers the frames (starts[k] + j) mod F, 0 <= starts[k] < F; the
     ``_ring`` entry points, the same blend and step.  ``apg = (eta, threshold)``: adaptive projected guidance as in ``cfg_ddim_step``
-    on the blends of the two halves, the sums over the whole clip."""
+    on the blends of the two halves, the sums over the whole clip.  ``apg_momentum = (state, carry)`` / ``carry_dev``: its momentum as
+    in ``cfg_ddim_step``, the state on the clip of blends (``sample``'s layout)."""
     _dev(preds, sample, noise, starts, weights)
     nW, outer, F, L, inner = geometry = _windows_geometry(preds, sample, starts, weights)
     _check_step_noise("cfg_ddim_step_windows", sample, noise, coefs, coef_dev)
     out = torch.empty(sample.shape, dtype=sample.dtype, device=sample.device)
+    if apg_momentum is not None:
+        state, carry = _apg_momentum_args("cfg_ddim_step_windows", apg, apg_momentum, carry_dev, sample)
+        eta, threshold = _apg_args("cfg_ddim_step_windows", apg, rescale)
+        ws = _apg_momentum_stats_windows(preds, sample, state, carry, carry_dev, starts, weights, geometry, mode, coefs, coef_dev, ring)
+        rc = lib().im360_cfg_ddim_step_windows_apg_momentum(_p(preds), _p(sample), _p(noise), _p(state), _p(out), _p(starts), _p(weights), nW,
+                                                            outer, F, L, inner, F if ring else 0, *(float(v) for v in coefs), int(mode), eta,
+                                                            threshold, _p(ws), ws.numel(), carry, _p(carry_dev), _dt(sample), _stream(),
+                                                            _p(coef_dev))
+        _check(rc, "im360_cfg_ddim_step_windows_apg_momentum")
+        return out
     if apg is not None:
         eta, threshold = _apg_args("cfg_ddim_step_windows", apg, rescale)
         ws = _apg_stats_windows(preds, sample, starts, weights, geometry, mode, coefs, coef_dev, ring)
@@ -1197,19 +1280,29 @@ def _check_multistep(who, sample, hist, mode, coefs, coef_dev):
         assert coef_dev.dtype == torch.float32 and coef_dev.numel() == 6 and coef_dev.is_cuda
 
 
-def cfg_multistep_step(uncond, cond, sample, hist, mode, coefs, coef_dev=None, rescale=0.0, apg=None):
+def cfg_multistep_step(uncond, cond, sample, hist, mode, coefs, coef_dev=None, rescale=0.0, apg=None, apg_momentum=None, carry_dev=None):
     """The DPM-Solver++ 2M update (arXiv 2211.01095, algorithm 2) of ``sample`` on uncond + g (cond - uncond), one pass:
     ``cx * sample + c0 * x0 + c1 * hist`` with x0 the prediction-type conversion (and clamp) of ``cfg_ddim_step``; ``hist`` (float32,
     like ``sample``) then holds x0, written in place, and is not read when c1 == 0.  ``mode``: DDIM_PRED_MODE | DDIM_CLIP_SAMPLE;
     ``coefs`` = (guidance, sqrt_a, sqrt_b, cx, c0, c1) (DPMSolverMultistepScheduler.multistep_coefficients); ``coef_dev`` = device
     float32[6] holding them, read by the kernel instead (graph replay).  ``rescale`` != 0: guidance rescale, the statistics launch of
     ``cfg_ddim_step`` in front of the step launch.  ``apg = (eta, threshold)``: adaptive projected guidance as in ``cfg_ddim_step``;
-    ``hist`` then holds the x0 of the projected guidance."""
+    ``hist`` then holds the x0 of the projected guidance.  ``apg_momentum = (state, carry)`` / ``carry_dev``: its momentum as in
+    ``cfg_ddim_step``; ``state`` is a buffer of its own beside ``hist``."""
     _dev(uncond, cond, sample, hist)
     assert uncond.is_contiguous() and cond.is_contiguous() and sample.is_contiguous()
     assert uncond.shape == cond.shape == sample.shape and uncond.dtype == cond.dtype == sample.dtype
     _check_multistep("cfg_multistep_step", sample, hist, mode, coefs, coef_dev)
     out = torch.empty(sample.shape, dtype=sample.dtype, device=sample.device)
+    if apg_momentum is not None:
+        state, carry = _apg_momentum_args("cfg_multistep_step", apg, apg_momentum, carry_dev, sample)
+        eta, threshold = _apg_args("cfg_multistep_step", apg, rescale)
+        ws = _apg_momentum_stats(uncond, cond, sample, state, carry, carry_dev, mode, coefs, coef_dev)
+        rc = lib().im360_cfg_multistep_step_apg_momentum(_p(uncond), _p(cond), _p(sample), _p(hist), _p(state), _p(out), sample.numel(),
+                                                         *(float(v) for v in coefs), int(mode), eta, threshold, _p(ws), ws.numel(), carry,
+                                                         _p(carry_dev), _dt(sample), _stream(), _p(coef_dev))
+        _check(rc, "im360_cfg_multistep_step_apg_momentum")
+        return out
     if apg is not None:
         eta, threshold = _apg_args("cfg_multistep_step", apg, rescale)
         ws = _apg_stats(uncond, cond, sample, mode, coefs, coef_dev)
@@ -1225,14 +1318,26 @@ def cfg_multistep_step(uncond, cond, sample, hist, mode, coefs, coef_dev=None, r
     return out
 
 
-def cfg_multistep_step_windows(preds, sample, hist, starts, weights, mode, coefs, coef_dev=None, rescale=0.0, ring=False, apg=None):
+def cfg_multistep_step_windows(preds, sample, hist, starts, weights, mode, coefs, coef_dev=None, rescale=0.0, ring=False, apg=None,
+                               apg_momentum=None, carry_dev=None):
     """``cfg_multistep_step`` on the per-frame weighted blend of sliding-window predictions, one pass: ``preds`` / ``starts`` /
     ``weights`` / ``ring`` as in ``cfg_ddim_step_windows``, ``hist`` float32 in ``sample``'s layout.  ``rescale`` != 0: the
-    statistics launch over the blends in front of the step launch.  ``apg``: as in ``cfg_ddim_step_windows``."""
+    statistics launch over the blends in front of the step launch.  ``apg`` / ``apg_momentum`` / ``carry_dev``: as in
+    ``cfg_ddim_step_windows``."""
     _dev(preds, sample, hist, starts, weights)
     nW, outer, F, L, inner = geometry = _windows_geometry(preds, sample, starts, weights)
     _check_multistep("cfg_multistep_step_windows", sample, hist, mode, coefs, coef_dev)
     out = torch.empty(sample.shape, dtype=sample.dtype, device=sample.device)
+    if apg_momentum is not None:
+        state, carry = _apg_momentum_args("cfg_multistep_step_windows", apg, apg_momentum, carry_dev, sample)
+        eta, threshold = _apg_args("cfg_multistep_step_windows", apg, rescale)
+        ws = _apg_momentum_stats_windows(preds, sample, state, carry, carry_dev, starts, weights, geometry, mode, coefs, coef_dev, ring)
+        rc = lib().im360_cfg_multistep_step_windows_apg_momentum(_p(preds), _p(sample), _p(hist), _p(state), _p(out), _p(starts), _p(weights),
+                                                                 nW, outer, F, L, inner, F if ring else 0, *(float(v) for v in coefs),
+                                                                 int(mode), eta, threshold, _p(ws), ws.numel(), carry, _p(carry_dev),
+                                                                 _dt(sample), _stream(), _p(coef_dev))
+        _check(rc, "im360_cfg_multistep_step_windows_apg_momentum")
+        return out
     if apg is not None:
         eta, threshold = _apg_args("cfg_multistep_step_windows", apg, rescale)
         ws = _apg_stats_windows(preds, sample, starts, weights, geometry, mode, coefs, coef_dev, ring)

@@ -15,7 +15,9 @@ surface, rebuilt for the MI355X:
     the text prediction's standard deviation inside the CFG + DDIM kernels (a statistics launch in front of the step launch);
   * adaptive projected guidance (``apg_eta=eta``, ``apg_threshold=r``, arXiv 2410.02416): the guidance difference of each branch split
     along the text branch's denoised prediction, its parallel part scaled by eta, its RMS clamped to r, in place of the CFG
-    combination inside the fused step kernels (a statistics launch in front of the step launch);
+    combination inside the fused step kernels (a statistics launch in front of the step launch); ``apg_momentum=beta`` adds the
+    paper's momentum, a running average of the guidance difference over the guided steps held in an fp32 state per branch that the
+    same kernels read and update in place;
   * long clips (``context_frames=L``): sliding temporal context windows -- one forward of the unmodified model per window
     of L frames, the windows' predictions blended per frame inside the CFG + DDIM kernel (imagine360_amd/context.py).
   * a start from a clip that exists (``init_latents`` / ``init_video`` with ``strength``): the clean latent noised to the timestep at
@@ -371,7 +373,7 @@ class AnimationPipeline:
                  context_frames=None, context_overlap=4, context_weights="pyramid", guidance_rescale=0.0, context_loop=False,
                  init_latents=None, init_video=None, strength=1.0, regenerate_mask=None, init_resize="bicubic", init_retime=None,
                  free_init_iters=1, free_init_d_s=0.25, free_init_d_t=0.25, regenerate_mode="blend", regenerate_feather=0.0,
-                 guidance_interval=None, context_level="model", apg_eta=None, apg_threshold=None, **kwargs):
+                 guidance_interval=None, context_level="model", apg_eta=None, apg_threshold=None, apg_momentum=None, **kwargs):
         """``frame_shard`` (imagine360_amd.dist.FrameShard): this rank denoises a contiguous chunk of the frames (BASELINE
         configs 4 / 5); all ranks must be called with the same seeds and inputs.  Noise is drawn for the whole clip and
         cut, the VAE encodes / the loop runs / the VAE decodes only the local frames, the motion modules exchange tokens
@@ -496,7 +498,7 @@ class AnimationPipeline:
         exit.  Malformed intervals and ``frame_shard`` raise ``ValueError``.  What the interval does to a clip's quality can only be
         judged with trained weights.
         ``apg_eta`` (None: off; the paper's value is 0.0) / ``apg_threshold`` (None: no clamp): adaptive projected guidance (APG, arXiv
-        2410.02416, algorithm 1 without its momentum; ``scheduler.projected_guidance`` is the definition) in place of the plain CFG
+        2410.02416, algorithm 1; ``scheduler.projected_guidance`` is the definition) in place of the plain CFG
         combination on every guided step.  In x0 space the guidance difference is split into the part parallel to the text branch's
         denoised prediction -- the part that saturates under the shipped zero-terminal-SNR, guidance-7.5 configuration -- and the part
         orthogonal to it; the parallel part is scaled by ``apg_eta`` (0 removes it, 1 keeps it) and the difference is first clamped to
@@ -512,8 +514,23 @@ class AnimationPipeline:
         DPM-Solver++ 2M, ``free_init_iters``, ``guidance_interval``: an unguided step has no guidance difference and makes no APG
         launch).  ``ValueError``: ``apg_threshold`` without ``apg_eta``, non-finite values, ``apg_threshold <= 0``, ``apg_eta`` with
         ``guidance_rescale != 0`` (the two address the same defect; the product of the kernel variants is not built) and with
-        ``frame_shard`` (the sums span the frames of all ranks).  The paper's momentum is not implemented.  What APG does to a clip's
-        look can only be judged with trained weights."""
+        ``frame_shard`` (the sums span the frames of all ranks).  What APG does to a clip's look can only be judged with trained
+        weights.
+        ``apg_momentum`` (None: off, the call without the keyword bit for bit -- no state is allocated and the entry points of before
+        run; the paper's values are -0.5 ... -0.75): the paper's momentum beta.  The difference that is projected and clamped becomes
+        the running average ``Dbar_t = Delta_t + beta * Dbar_prev`` (x0 units) over the GUIDED steps of a run; a negative beta keeps the
+        differences of consecutive steps from piling up in one direction.  Each branch owns an fp32 state like its latent, next to the
+        multistep history, read by the statistics launch and read and rewritten in place by the step launch
+        (``kernels.cfg_ddim_step(..., apg_momentum=)``); the factor on it, ``scheduler.apg_carry(t_prev, t, beta)``, is computed on
+        the host per step (under graph replay: one float uploaded beside the coefficients).  Update order: the first step that is run
+        has carry 0 -- it writes the state without reading it -- in a full run, in a ``strength`` < 1 run that enters the schedule
+        later, and in every FreeInit pass (the state of the previous pass is dropped); the unguided steps of ``guidance_interval``
+        leave the state and the predecessor alone, so the next guided step continues from the last guided one; ``regenerate_mask``
+        does not touch the state (it blends latents, not guidance); ``context_level="attention"`` is the plain loop; with whole-model
+        context windows (line or ring) the state lives on the clip of blends; both schedulers.  ``apg_momentum=0.0`` equals None bit
+        for bit (on the kernels with the state).  ``ValueError``: ``apg_momentum`` without ``apg_eta``, a non-finite value, ``|beta|
+        >= 1`` (the running sum diverges); ``frame_shard`` and ``guidance_rescale`` stay refused through ``apg_eta``.  What the
+        momentum does to a clip's look can only be judged with trained weights."""
         device = self.device
         vb = video_batch
         plan = None
@@ -551,6 +568,14 @@ class AnimationPipeline:
                 raise ValueError("apg_eta cannot be combined with frame_shard (its sums span the frames of all ranks and would need an "
                                  "all-reduce inside the step, which is not implemented)")
             apg_kw = dict(guidance_apg=(apg_eta, apg_threshold))
+        apg_beta = None
+        if apg_momentum is not None:
+            if apg_eta is None:
+                raise ValueError("apg_momentum needs apg_eta (adaptive projected guidance is off without it)")
+            apg_beta = float(apg_momentum)
+            if not (math.isfinite(apg_beta) and abs(apg_beta) < 1.0):
+                raise ValueError(f"apg_momentum must be finite with |beta| < 1 (the running sum diverges otherwise; the paper's values "
+                                 f"are -0.5 ... -0.75), got {apg_beta}")
         if context_loop and frame_shard is not None:
             raise ValueError("context_loop cannot be combined with frame_shard (windows under frame sharding are not implemented)")
         if init_latents is not None and init_video is not None:
@@ -672,6 +697,7 @@ class AnimationPipeline:
             # a multistep scheduler: the run's timestep list fixes its coefficients, and each branch's latent owns its x0 history
             self.scheduler.begin_run(steps_host)
             hist = (self.scheduler.new_history(pano_latent), self.scheduler.new_history(pers_latent))
+        apg_mom_kw = {} if apg_beta is None else dict(guidance_apg_momentum=apg_beta)
         # (guidance_interval) the flags of the run's steps; None: every step is guided, the call without the keyword
         guided = None if guidance_interval is None else self.scheduler.guided_steps(steps_host, guidance_interval)
         if guided is not None and all(guided):
@@ -723,7 +749,8 @@ class AnimationPipeline:
                 pano_latent, pers_latent = self._windowed_loop(plan, inputs, cameras, pano_latent, pers_latent, steps_host, ts_dev,
                                                                guidance_scale_text, use_fps_condition, eta, generator, trace,
                                                                callback, callback_steps, guidance_rescale, region, hist, next_pass,
-                                                               **({} if guided is None else dict(guidance_interval=guidance_interval)), **apg_kw)
+                                                               **({} if guided is None else dict(guidance_interval=guidance_interval)), **apg_kw,
+                                                               **apg_mom_kw)
             graphed = None
             if guided is not None and plan is None:
                 # the text-half views of the model inputs, made once and kept (the IP-token cache keys on the feature tensors' identity),
@@ -750,9 +777,16 @@ class AnimationPipeline:
                 if guided is not None:
                     stoch.update(guidance_interval=guidance_interval, steps=steps_host)
                 stoch.update(apg_kw)
+                stoch.update(apg_mom_kw)
                 graphed = GraphedDenoiseStep(self.mv_base_model, self.scheduler, inputs, cameras, pano_latent, pers_latent,
                                              guidance_scale_text, use_fps=use_fps_condition, warmup=1, guidance_rescale=guidance_rescale, **stoch)       # one eager step fills every cache
+            # (apg_momentum, eager loop) one momentum state per branch next to `hist`, never initialised: the first guided step of
+            # every pass has carry 0 and only writes it
+            apg_state = None
+            if apg_beta is not None and plan is None and graphed is None:
+                apg_state = (self.scheduler.new_apg_state(pano_latent), self.scheduler.new_apg_state(pers_latent))
             while plan is None:                 # one round per pass: once without free_init_iters
+                apg_prev_t = None               # the previous guided timestep of this pass
                 for i, t in enumerate(self.progress_bar(steps_host)):
                     if graphed is not None:
                         pano_latent, pers_latent = graphed.step(t)
@@ -769,10 +803,15 @@ class AnimationPipeline:
                             use_ip_plus_cross_attention=use_ip_plus_cross_attention, fps_tensor_pano=fps_pano, fps_tensor_pers=fps_pers,
                             reference_images_clip_feat_pano=feat_pano, reference_images_clip_feat_pers=feat_pers,
                             relative_position_tensor=rel, pitchs_tensor=pitch)
+                        mom = ({}, {})
+                        if apg_state is not None:
+                            carry = self.scheduler.apg_carry(apg_prev_t, t, apg_beta)
+                            mom = tuple(dict(guidance_apg_momentum=(state, carry)) for state in apg_state)
+                            apg_prev_t = t
                         pano_latent = self._cfg_step(pred_pano, guidance_scale_text, t, pano_latent, eta, generator, sh, 2, guidance_rescale,
-                                                     **({} if hist is None else dict(history=hist[0])), **apg_kw)
+                                                     **({} if hist is None else dict(history=hist[0])), **apg_kw, **mom[0])
                         pers_latent = self._cfg_step(pred_pers, guidance_scale_text, t, pers_latent, eta, generator, sh, 3, guidance_rescale,
-                                                     **({} if hist is None else dict(history=hist[1])), **apg_kw)
+                                                     **({} if hist is None else dict(history=hist[1])), **apg_kw, **mom[1])
                     if region is not None:
                         region.apply(pano_latent, pers_latent, i)
                     if trace is not None:
@@ -808,11 +847,14 @@ class AnimationPipeline:
             if ip_slots is not None:
                 ip_slots.__exit__(None, None, None)           # (guidance_interval) back to the single-entry IP-token cache
 
-    def _cfg_step(self, pred, g, t, latent, eta=0.0, generator=None, shard=None, frame_dim=2, guidance_rescale=0.0, guidance_apg=None, **history):
+    def _cfg_step(self, pred, g, t, latent, eta=0.0, generator=None, shard=None, frame_dim=2, guidance_rescale=0.0, guidance_apg=None,
+                  guidance_apg_momentum=None, **history):
         """``history`` (``history=``, a multistep scheduler only): the x0 history of this latent, handed on to the scheduler.
-        ``guidance_apg``: handed on when it is set (``apg_eta``)."""
+        ``guidance_apg`` / ``guidance_apg_momentum`` = (state, carry): handed on when set (``apg_eta`` / ``apg_momentum``)."""
         u, c = pred.to(latent.dtype).chunk(2)          # latents_dtype may differ from the model dtype (the reference promotes)
         apg = {} if guidance_apg is None else dict(guidance_apg=guidance_apg)
+        if guidance_apg_momentum is not None:
+            apg["guidance_apg_momentum"] = guidance_apg_momentum
         if eta > 0:
             z = variance_noise(self.scheduler, latent, pred.dtype, generator, self.rng, shard, frame_dim)
             return self.scheduler.fused_cfg_step(u, c, g, t, latent, eta=eta, noise=z, guidance_rescale=guidance_rescale, **apg)
@@ -870,7 +912,7 @@ class AnimationPipeline:
 
     def _windowed_loop(self, plan, inputs, cameras, pano_latent, pers_latent, steps_host, ts_dev, g, use_fps, eta, generator,
                        trace, callback, callback_steps, guidance_rescale=0.0, keep=None, hist=None, next_pass=None, guidance_interval=None,
-                       guidance_apg=None):
+                       guidance_apg=None, guidance_apg_momentum=None):
         """The denoising loop over sliding temporal context windows: per step one forward per window (slot order), then ONE
         blend + CFG + DDIM kernel per branch, panorama first.  RNG: as len(plan) successive calls of the model, then (eta > 0)
         the whole clip's panorama and perspective variance noise.  Captured in one hipGraph under the conditions of the
@@ -880,10 +922,13 @@ class AnimationPipeline:
         loop, else it returns the start latents of another run of the whole schedule (the captured step is restarted, not captured again).
         ``guidance_interval`` (None: every step guided): the unguided steps run every window on its text half (views made once, [nW, 1, ...]
         prediction buffers, ``scheduler.fused_step_windows``), and the IP-token cache holds both forms of every window's features.
-        ``guidance_apg`` (``apg_eta``): handed on to the scheduler's step functions and the graphed step when it is set."""
+        ``guidance_apg`` (``apg_eta``): handed on to the scheduler's step functions and the graphed step when it is set.
+        ``guidance_apg_momentum`` (``apg_momentum``, beta): the graphed step owns the momentum states; the eager loop makes one per branch
+        on the clip of blends and tracks the previous guided timestep of each pass itself."""
         from .context import ip_cache_slots
         mv, sch = self.mv_base_model, self.scheduler
         apg_kw = {} if guidance_apg is None else dict(guidance_apg=guidance_apg)
+        apg_beta = guidance_apg_momentum
         guided = None if guidance_interval is None else sch.guided_steps(steps_host, guidance_interval)
         with ip_cache_slots(mv, len(plan) * (1 if guided is None else 2)):
             if self.use_graph and self.rng == "device" and pano_latent.is_cuda and trace is None and callback is None:
@@ -891,7 +936,8 @@ class AnimationPipeline:
                 graphed = GraphedWindowedStep(mv, sch, inputs, cameras, pano_latent, pers_latent, g, plan, use_fps=use_fps, warmup=1,
                                               eta=eta, generator=generator, guidance_rescale=guidance_rescale,
                                               **({} if keep is None else dict(keep=keep)),
-                                              **({} if guided is None else dict(guidance_interval=guidance_interval, steps=steps_host)), **apg_kw)
+                                              **({} if guided is None else dict(guidance_interval=guidance_interval, steps=steps_host)), **apg_kw,
+                                              **({} if apg_beta is None else dict(guidance_apg_momentum=apg_beta)))
                 while True:
                     for t in self.progress_bar(steps_host):
                         pano_latent, pers_latent = graphed.step(t)
@@ -905,7 +951,9 @@ class AnimationPipeline:
                 from .dist import cfg_half_inputs
                 text_half, text_static = cfg_half_inputs(inputs, 1), plan.text_half(static)
                 text_preds = plan.pred_buffers(pano_latent, pers_latent, halves=1)           # (perspective, panorama)
+            apg_state = None if apg_beta is None else (sch.new_apg_state(pano_latent), sch.new_apg_state(pers_latent))
             while True:
+                apg_prev_t = None               # the previous guided timestep of this pass: its first guided step has carry 0
                 for i, t in enumerate(self.progress_bar(steps_host)):
                     if guided is not None and not guided[i]:
                         pano_latent, pers_latent = self._unguided_windows_step(plan, text_half, text_static, text_preds, pano_latent,
@@ -917,12 +965,17 @@ class AnimationPipeline:
                         plan.forward(mv, inputs, static, cameras, ts_dev[i], use_fps, preds_pers, preds_pano)
                         mdt = mv.unet.dtype
                         kw = dict(eta=eta, guidance_rescale=guidance_rescale, ring=plan.loop, **apg_kw)
+                        mom = ({}, {})
+                        if apg_state is not None:
+                            carry = sch.apg_carry(apg_prev_t, t, apg_beta)
+                            mom = tuple(dict(guidance_apg_momentum=(state, carry)) for state in apg_state)
+                            apg_prev_t = t
                         z = variance_noise(sch, pano_latent, mdt, generator, self.rng) if eta > 0 else None
                         pano_latent = sch.fused_cfg_step_windows(preds_pano, plan.starts_dev, plan.weights, g, t, pano_latent, noise=z, **kw,
-                                                                 **({} if hist is None else dict(history=hist[0])))
+                                                                 **({} if hist is None else dict(history=hist[0])), **mom[0])
                         z = variance_noise(sch, pers_latent, mdt, generator, self.rng, frame_dim=3) if eta > 0 else None
                         pers_latent = sch.fused_cfg_step_windows(preds_pers, plan.starts_dev, plan.weights, g, t, pers_latent, noise=z, **kw,
-                                                                 **({} if hist is None else dict(history=hist[1])))
+                                                                 **({} if hist is None else dict(history=hist[1])), **mom[1])
                     if keep is not None:
                         keep.apply(pano_latent, pers_latent, i)
                     if trace is not None:

@@ -74,8 +74,8 @@ def rescale_noise_cfg(noise_cfg, noise_pred_text, guidance_rescale=0.0):
 _APG_KAPPA = {"epsilon": lambda sa, sb: (1.0 / sa, -sb / sa), "v_prediction": lambda sa, sb: (sa, -sb), "sample": lambda sa, sb: (0.0, 1.0)}
 
 
-def projected_guidance(pred_uncond, pred_text, sample, guidance, sqrt_a, sqrt_b, prediction_type, eta, threshold=None):
-    """Adaptive projected guidance (APG, arXiv 2410.02416, algorithm 1 without its momentum; diffusers carries it as a guider) in
+def projected_guidance(pred_uncond, pred_text, sample, guidance, sqrt_a, sqrt_b, prediction_type, eta, threshold=None, momentum=None):
+    """Adaptive projected guidance (APG, arXiv 2410.02416, algorithm 1; diffusers carries it as a guider) in
     model-output space: what the step functions take in place of ``pred_uncond + guidance * (pred_text - pred_uncond)``.  The eager
     definition, in torch ops on any device and in the inputs' dtype (fp64 in, fp64 out); the pipeline's kernels compute the same
     inside the fused CFG + step kernels.
@@ -97,25 +97,50 @@ def projected_guidance(pred_uncond, pred_text, sample, guidance, sqrt_a, sqrt_b,
     norm: a norm over a 4 x F x h x w clip would tie the setting to clip length and resolution; the paper's radius equals
     ``threshold * sqrt(C * H * W)``.  None: no clamp.
 
+    ``momentum = (e_prev, carry)``: the paper's momentum, and the return value is ``(m, e)``.  The paper replaces Delta by the running
+    average Dbar_t = Delta_t + beta * Dbar_prev over the guided steps of a run (0 before the first) in the projection and in the
+    clamp.  The state is kept in the model-output units of the step that wrote it, e_t = Dbar_t / kp_t, so that
+
+        e = d + carry * e_prev,   carry = beta * kp_prev / kp_t   (``DDIMScheduler.apg_carry``; 0 on the first guided step of a run)
+
+    and the formulas above hold with d replaced by e.  The returned e is the UNclamped one, the ``e_prev`` of the next guided step.
+    ``carry == 0`` does not read ``e_prev`` (it may be None or hold anything) and gives ``e = d``: m is then the value without
+    momentum, bit for bit.  None: m alone, as before.
+
     Edge cases, as the formula gives them: ``eta = 1`` without a threshold is plain CFG up to rounding (not bit for bit);
-    ``pred_uncond == pred_text`` gives m = pred_text; ``sum q^2 = 0`` gives NaN."""
+    ``pred_uncond == pred_text`` gives m = pred_text; ``sum q^2 = 0`` gives NaN; epsilon prediction at a timestep with sqrt_a = 0 has
+    kp infinite, as x0 itself is (not guarded)."""
     if prediction_type not in _APG_KAPPA:
         raise ValueError(f"prediction_type given as {prediction_type} must be one of `epsilon`, `sample`, or `v_prediction`")
     kx, kp = _APG_KAPPA[prediction_type](sqrt_a, sqrt_b)
     u, c = pred_uncond, pred_text
     d, q = c - u, c + (kx / kp) * sample
+    if momentum is not None and momentum[1] != 0.0:
+        d = d + momentum[1] * momentum[0]
     alpha = (d * q).sum() / (q * q).sum()
     s = 1.0
     if threshold is not None:
         s = torch.clamp(threshold / (abs(kp) * (d * d).mean().sqrt()), max=1.0)
     gs = (guidance - 1.0) * s
-    return c + gs * d - gs * (1.0 - eta) * alpha * q
+    m = c + gs * d - gs * (1.0 - eta) * alpha * q
+    return m if momentum is None else (m, d)
 
 
 def _apg_kw(guidance_apg):
     """``apg=`` for the guided step wrappers of ``kernels``, left out when it is off: they are then called with exactly the arguments of
     before.  ``guidance_apg``: None or (eta, threshold)."""
     return dict(apg=(guidance_apg[0], guidance_apg[1])) if guidance_apg is not None else {}
+
+
+def _apg_momentum_kw(guidance_apg_momentum, carry_dev):
+    """``apg_momentum=`` / ``carry_dev=`` for the guided step wrappers of ``kernels``, left out when the momentum is off.
+    ``guidance_apg_momentum``: None or (state, carry)."""
+    if guidance_apg_momentum is None:
+        return {}
+    kw = dict(apg_momentum=(guidance_apg_momentum[0], guidance_apg_momentum[1]))
+    if carry_dev is not None:
+        kw["carry_dev"] = carry_dev
+    return kw
 
 
 def _rescale_kw(guidance_rescale):
@@ -189,6 +214,23 @@ class DDIMScheduler:
         else:
             raise ValueError(f"prediction_type {self.config.prediction_type} unsupported")
         return cx, cv
+
+    def apg_carry(self, t_prev, t, beta):
+        """The factor on the momentum state of adaptive projected guidance at the guided step ``t`` whose previous guided step of the
+        run was ``t_prev``: ``beta * kp(t_prev) / kp(t)`` with kp the x0 conversion's factor on the prediction (``_APG_KAPPA``) -- the
+        state is held in the model-output units of the step that wrote it (``projected_guidance``).  ``t_prev`` None (the first
+        guided step of a run): 0.0, which makes the step write the state without reading it.  ``sample`` prediction: ``beta``."""
+        if t_prev is None:
+            return 0.0
+        kappa = _APG_KAPPA[self.config.prediction_type]
+        a_prev, a_t = self._alphas(t_prev)[0], self._alphas(t)[0]
+        kp_prev, kp_t = kappa(a_prev ** 0.5, (1.0 - a_prev) ** 0.5)[1], kappa(a_t ** 0.5, (1.0 - a_t) ** 0.5)[1]
+        return float(beta) * kp_prev / kp_t
+
+    def new_apg_state(self, latent):
+        """The momentum state of adaptive projected guidance for one latent: float32, ``latent``'s shape and device, NOT initialised --
+        the first guided step of a run (carry 0) writes it without reading it.  One per latent that is stepped."""
+        return torch.empty_like(latent, dtype=torch.float32)
 
     def uses_step_kernel(self, eta=0.0, use_clipped_model_output=False, guidance_rescale=0.0, guidance_apg=None):
         """True when an update needs ``cfg_ddim_step``: anything but the eta = 0, unclipped v / epsilon update without guidance
@@ -344,14 +386,16 @@ class DDIMScheduler:
         return DDIMSchedulerOutput(prev_sample=prev, pred_original_sample=x0) if return_dict else (prev,)
 
     def fused_cfg_step(self, pred_uncond, pred_text, guidance_scale, timestep, sample, coef_dev=None, *, eta=0.0, noise=None,
-                       use_clipped_model_output=False, guidance_rescale=0.0, guidance_apg=None):
+                       use_clipped_model_output=False, guidance_rescale=0.0, guidance_apg=None, guidance_apg_momentum=None, carry_dev=None):
         """CFG combine + update in one HIP kernel (pipeline_animation_inference_dual.py:791-800).  ``coef_dev``: device
         float32 coefficients read by the kernel instead of host scalars (graph replay): [3] = (guidance, cx, cv) for the
         eta = 0 v / epsilon update, [6] = ``step_coefficients`` otherwise.  ``noise``: the variance noise (like ``sample``),
         used when eta > 0.  ``guidance_rescale`` != 0: ``rescale_noise_cfg`` on the combination before the update, inside the step
         kernel (always the six-coefficient one).  ``guidance_apg = (eta, threshold)``: ``projected_guidance`` in place of the
         combination, inside the step kernel (the six-coefficient one, a statistics launch in front); not together with
-        ``guidance_rescale``."""
+        ``guidance_rescale``.  ``guidance_apg_momentum = (state, carry)`` with ``guidance_apg``: its momentum -- ``state`` from
+        ``new_apg_state`` is updated in place, ``carry`` = ``apg_carry(t_prev, t, beta)``; ``carry_dev``: device float32[1] read
+        instead (graph replay).  Handed on only when set."""
         u, c, x = pred_uncond.contiguous(), pred_text.contiguous(), sample.contiguous()
         if not self.uses_step_kernel(eta, use_clipped_model_output, guidance_rescale, guidance_apg):
             cx, cv = (0.0, 0.0) if coef_dev is not None else self.coefficients(timestep)
@@ -361,35 +405,37 @@ class DDIMScheduler:
         coefs = (0.0,) * 6 if coef_dev is not None else self.step_coefficients(timestep, eta, guidance_scale)
         return kernels.cfg_ddim_step(u, c, x, noise.to(x.dtype).contiguous() if eta > 0 else None,
                                      self.kernel_mode(use_clipped_model_output), coefs, coef_dev=coef_dev, **_rescale_kw(guidance_rescale),
-                                     **_apg_kw(guidance_apg))
+                                     **_apg_kw(guidance_apg), **_apg_momentum_kw(guidance_apg_momentum, carry_dev))
 
     def fused_cfg_step_windows(self, preds, starts, weights, guidance_scale, timestep, sample, coef_dev=None, *, eta=0.0,
-                               noise=None, use_clipped_model_output=False, guidance_rescale=0.0, ring=False, guidance_apg=None):
+                               noise=None, use_clipped_model_output=False, guidance_rescale=0.0, ring=False, guidance_apg=None,
+                               guidance_apg_momentum=None, carry_dev=None):
         """``fused_cfg_step`` over sliding temporal context windows: the per-frame weighted blend of the windows' CFG-combined
         predictions + the update, one HIP kernel (``kernels.cfg_ddim_step_windows``).  ``preds`` [nW, 2, ...]: window k's
         CFG-batched prediction in slot k, in ``sample``'s layout with L frames;  ``starts`` device int32 [nW], ``weights`` device
         float32 [L] (imagine360_amd.context).  The step kernel serves eta = 0 as well, so ``coef_dev`` is always float32[6] =
         ``step_coefficients``.  ``guidance_rescale`` != 0: ``rescale_noise_cfg`` on the blends (guided and text), the standard
         deviations over the whole clip.  ``ring``: the windows of a looping clip (context.WindowPlan(loop=True)), ``starts`` on a
-        ring of F frames.  ``guidance_apg``: ``projected_guidance`` on the blends of the two halves, the sums over the whole clip."""
+        ring of F frames.  ``guidance_apg``: ``projected_guidance`` on the blends of the two halves, the sums over the whole clip;
+        ``guidance_apg_momentum`` / ``carry_dev``: as in ``fused_cfg_step``, the state on the clip of blends."""
         if eta > 0 and noise is None:
             raise ValueError("fused_cfg_step_windows: eta > 0 needs the variance noise")
         x = sample.contiguous()
         coefs = (0.0,) * 6 if coef_dev is not None else self.step_coefficients(timestep, eta, guidance_scale)
         return kernels.cfg_ddim_step_windows(preds.contiguous(), x, noise.to(x.dtype).contiguous() if eta > 0 else None, starts,
                                              weights, self.kernel_mode(use_clipped_model_output), coefs, coef_dev=coef_dev, **_rescale_kw(guidance_rescale),
-                                             **_ring_kw(ring), **_apg_kw(guidance_apg))
+                                             **_ring_kw(ring), **_apg_kw(guidance_apg), **_apg_momentum_kw(guidance_apg_momentum, carry_dev))
 
 
     def fused_step(self, pred, timestep, sample, coef_dev=None, *, eta=0.0, noise=None, use_clipped_model_output=False, guidance_rescale=0.0,
-                   guidance_apg=None):
+                   guidance_apg=None, guidance_apg_momentum=None, carry_dev=None):
         """``fused_cfg_step`` for an UNGUIDED step (``guided_steps``): the model ran the text half alone and ``pred`` is its one
         prediction.  The same kernels in their unguided form (``kernels.ddim_update`` / ``kernels.ddim_step``: one prediction stream, no
         guidance read), the same choice between them, the same coefficient vectors -- ``coef_dev`` is the buffer the guided step reads.
         ``guidance_rescale`` is SKIPPED -- no statistics launch, no factor: rescaling a prediction towards its own standard deviation is
         the identity; the keyword only selects the six-coefficient kernel as it does for the guided steps of the run, so that both forms
         read one coefficient vector.  ``guidance_apg`` is skipped in the same way: without an unconditional prediction there is no
-        guidance difference to project."""
+        guidance difference to project, and the momentum state (``guidance_apg_momentum``) is neither read nor written."""
         p, x = pred.contiguous(), sample.contiguous()
         if not self.uses_step_kernel(eta, use_clipped_model_output, guidance_rescale, guidance_apg):
             cx, cv = (0.0, 0.0) if coef_dev is not None else self.coefficients(timestep)
@@ -401,7 +447,8 @@ class DDIMScheduler:
                                  coef_dev=coef_dev)
 
     def fused_step_windows(self, preds, starts, weights, timestep, sample, coef_dev=None, *, eta=0.0, noise=None,
-                           use_clipped_model_output=False, guidance_rescale=0.0, ring=False, guidance_apg=None):
+                           use_clipped_model_output=False, guidance_rescale=0.0, ring=False, guidance_apg=None, guidance_apg_momentum=None,
+                           carry_dev=None):
         """``fused_cfg_step_windows`` for an unguided step: ``preds`` [nW, 1, ...], the windows' text halves alone
         (``kernels.ddim_step_windows``); everything else as there, ``guidance_rescale`` and ``guidance_apg`` skipped as in ``fused_step``."""
         if eta > 0 and noise is None:
@@ -550,31 +597,35 @@ class DPMSolverMultistepScheduler(DDIMScheduler):
         return (0.0,) * 6 if coef_dev is not None else self.step_coefficients(timestep, 0.0, guidance_scale)
 
     def fused_cfg_step(self, pred_uncond, pred_text, guidance_scale, timestep, sample, coef_dev=None, *, history=None, eta=0.0, noise=None,
-                       guidance_rescale=0.0, guidance_apg=None, **kwargs):
+                       guidance_rescale=0.0, guidance_apg=None, guidance_apg_momentum=None, carry_dev=None, **kwargs):
         """CFG combine + the multistep update in one HIP kernel (``kernels.cfg_multistep_step``); ``history``: this latent's
         ``new_history``, updated in place.  ``coef_dev``: device float32[6] = ``step_coefficients`` read by the kernel (graph replay).
-        ``guidance_apg``: as in ``DDIMScheduler.fused_cfg_step``; the history then receives the x0 of the projected guidance."""
+        ``guidance_apg`` / ``guidance_apg_momentum`` / ``carry_dev``: as in ``DDIMScheduler.fused_cfg_step``; the history then receives
+        the x0 of the projected guidance."""
         coefs = self._kernel_args("fused_cfg_step", timestep, guidance_scale, coef_dev, history, eta, noise, kwargs)
         return kernels.cfg_multistep_step(pred_uncond.contiguous(), pred_text.contiguous(), sample.contiguous(), history, self.kernel_mode(),
-                                          coefs, coef_dev=coef_dev, **_rescale_kw(guidance_rescale), **_apg_kw(guidance_apg))
+                                          coefs, coef_dev=coef_dev, **_rescale_kw(guidance_rescale), **_apg_kw(guidance_apg),
+                                          **_apg_momentum_kw(guidance_apg_momentum, carry_dev))
 
     def fused_cfg_step_windows(self, preds, starts, weights, guidance_scale, timestep, sample, coef_dev=None, *, history=None, eta=0.0,
-                               noise=None, guidance_rescale=0.0, ring=False, guidance_apg=None, **kwargs):
+                               noise=None, guidance_rescale=0.0, ring=False, guidance_apg=None, guidance_apg_momentum=None, carry_dev=None,
+                               **kwargs):
         """``fused_cfg_step`` on the blend of sliding temporal context windows (``kernels.cfg_multistep_step_windows``; arguments of
         ``DDIMScheduler.fused_cfg_step_windows``)."""
         coefs = self._kernel_args("fused_cfg_step_windows", timestep, guidance_scale, coef_dev, history, eta, noise, kwargs)
         return kernels.cfg_multistep_step_windows(preds.contiguous(), sample.contiguous(), history, starts, weights, self.kernel_mode(), coefs,
-                                                  coef_dev=coef_dev, **_rescale_kw(guidance_rescale), **_ring_kw(ring), **_apg_kw(guidance_apg))
+                                                  coef_dev=coef_dev, **_rescale_kw(guidance_rescale), **_ring_kw(ring), **_apg_kw(guidance_apg),
+                                                  **_apg_momentum_kw(guidance_apg_momentum, carry_dev))
 
     def fused_step(self, pred, timestep, sample, coef_dev=None, *, history=None, eta=0.0, noise=None, guidance_rescale=0.0, guidance_apg=None,
-                   **kwargs):
+                   guidance_apg_momentum=None, carry_dev=None, **kwargs):
         """``fused_cfg_step`` for an unguided step (``DDIMScheduler.fused_step``): the multistep update on the one prediction
         (``kernels.multistep_step``); ``history`` is written and read as on a guided step -- the six coefficients do not depend on guidance."""
         coefs = self._kernel_args("fused_step", timestep, 1.0, coef_dev, history, eta, noise, kwargs)
         return kernels.multistep_step(pred.contiguous(), sample.contiguous(), history, self.kernel_mode(), coefs, coef_dev=coef_dev)
 
     def fused_step_windows(self, preds, starts, weights, timestep, sample, coef_dev=None, *, history=None, eta=0.0, noise=None,
-                           guidance_rescale=0.0, ring=False, guidance_apg=None, **kwargs):
+                           guidance_rescale=0.0, ring=False, guidance_apg=None, guidance_apg_momentum=None, carry_dev=None, **kwargs):
         """``fused_cfg_step_windows`` for an unguided step: ``preds`` [nW, 1, ...] (``kernels.multistep_step_windows``)."""
         coefs = self._kernel_args("fused_step_windows", timestep, 1.0, coef_dev, history, eta, noise, kwargs)
         return kernels.multistep_step_windows(preds.contiguous(), sample.contiguous(), history, starts, weights, self.kernel_mode(), coefs,

@@ -435,7 +435,7 @@ int im360_multistep_step_windows(const void* pred, const void* x, void* hist, vo
                                  float sqrt_b, float cx, float c0, float c1, int mode, int dtype, void* stream,
                                  const void* coef_dev);
 
-/* ---- adaptive projected guidance (APG, arXiv 2410.02416, algorithm 1 without its momentum) inside the guided step entry points.
+/* ---- adaptive projected guidance (APG, arXiv 2410.02416, algorithm 1; its momentum: the block behind this one) inside the guided step entry points.
  * The step sees, in place of m = uncond + guidance * (cond - uncond),
  *   d = cond - uncond,   q = cond + rho * x,   rho = -1 / sqrt_b (epsilon), -sqrt_a / sqrt_b (v_prediction), 0 (sample)
  *   alpha = sum d q / sum q^2
@@ -499,6 +499,68 @@ int im360_cfg_multistep_step_windows_apg(const void* pred, const void* x, void* 
                                          float guidance, float sqrt_a, float sqrt_b, float cx, float c0, float c1, int mode, float eta,
                                          float threshold, const void* ws, int64_t ws_floats, int dtype, void* stream,
                                          const void* coef_dev);
+
+/* ---- APG with the paper's momentum (algorithm 1 in full): the difference that is projected and clamped is the running average of the
+ * run's guided steps, Dbar_t = Delta_t + beta * Dbar_prev in x0 units.  The state holds it in the model-output units of the step that
+ * wrote it, e_t = Dbar_t / kp_t (kp = -sqrt_b / sqrt_a (epsilon), -sqrt_b (v_prediction), 1 (sample)), so that
+ *   e = d + carry * state,   carry = beta * kp_prev / kp_t      (0 on the first guided step of a run; beta for `sample`)
+ * is one fma and the block above holds with d replaced by e: alpha = sum e q / sum q^2, s from sum e^2, m = cond + (guidance - 1) s e
+ * - lambda q.  `state`: float32[n], indexed like the multistep history (the flat element index of x; windows: of the clip [outer, F,
+ * inner] of blends), 16-byte aligned where the launch moves 16-byte lanes (always for the plain entry points), each element read and
+ * written by one thread.  A statistics pass reads it; the step reads it again, forms the same bits and stores the UNclamped e in
+ * place.  carry == 0: the state is not read at all, only written by the step, and e = d to the bit -- records, scalars and step are
+ * those of the _apg entry points, and whatever the buffer held (NaN included) has no effect; so a state never needs clearing.  carry
+ * is read from carry_dev[0] (device float32[1]) where carry_dev is given (hipGraph replay; coef_dev keeps its six floats).
+ * Argument errors beyond the _apg siblings': a null or misaligned state, a non-finite host carry, a misaligned carry_dev, state ==
+ * hist.  im360_cfg_apg_scalars serves the records of either statistics pass.
+ * Replaces: nothing in the reference; the momentum buffer of the guider of arXiv 2410.02416. */
+
+/* im360_cfg_apg_stats on e: the records (count, sum e q, sum q^2, sum e^2); the state is not written */
+int im360_cfg_apg_momentum_stats(const void* uncond, const void* cond, const void* x, const void* state, int64_t n, float sqrt_a,
+                                 float sqrt_b, int mode, float carry, const void* carry_dev, void* ws, int64_t ws_floats, int dtype,
+                                 void* stream, const void* coef_dev);
+
+/* im360_cfg_apg_stats_windows on e; state [outer, F, inner].  One uniform window with L = F writes the records of
+ * im360_cfg_apg_momentum_stats bit for bit. */
+int im360_cfg_apg_momentum_stats_windows(const void* pred, const void* x, const void* state, const void* start, const void* weight,
+                                         int nW, int64_t outer, int64_t F, int64_t L, int64_t inner, float sqrt_a, float sqrt_b,
+                                         int mode, float carry, const void* carry_dev, void* ws, int64_t ws_floats, int dtype,
+                                         void* stream, const void* coef_dev);
+
+/* the same with the windows on a ring of F frames.  Precondition: 0 <= start[k] < F, every frame covered, L <= F. */
+int im360_cfg_apg_momentum_stats_windows_ring(const void* pred, const void* x, const void* state, const void* start,
+                                              const void* weight, int nW, int64_t outer, int64_t F, int64_t L, int64_t inner,
+                                              float sqrt_a, float sqrt_b, int mode, float carry, const void* carry_dev, void* ws,
+                                              int64_t ws_floats, int dtype, void* stream, const void* coef_dev);
+
+/* im360_cfg_ddim_step_apg on e, state <- e; ws: the records of im360_cfg_apg_momentum_stats for the same tensors, state and carry. */
+int im360_cfg_ddim_step_apg_momentum(const void* uncond, const void* cond, const void* x, const void* noise, void* state, void* out,
+                                     int64_t n, float guidance, float sqrt_a, float sqrt_b, float sqrt_a_prev, float dir, float sigma,
+                                     int mode, float eta, float threshold, const void* ws, int64_t ws_floats, float carry,
+                                     const void* carry_dev, int dtype, void* stream, const void* coef_dev);
+
+/* im360_cfg_ddim_step_windows_apg on e, state [outer, F, inner] <- e; wrap = 0 (line) or F (ring).  One uniform window with L = F
+ * gives im360_cfg_ddim_step_apg_momentum's out and state bit for bit. */
+int im360_cfg_ddim_step_windows_apg_momentum(const void* pred, const void* x, const void* noise, void* state, void* out,
+                                             const void* start, const void* weight, int nW, int64_t outer, int64_t F, int64_t L,
+                                             int64_t inner, int64_t wrap, float guidance, float sqrt_a, float sqrt_b,
+                                             float sqrt_a_prev, float dir, float sigma, int mode, float eta, float threshold,
+                                             const void* ws, int64_t ws_floats, float carry, const void* carry_dev, int dtype,
+                                             void* stream, const void* coef_dev);
+
+/* im360_cfg_multistep_step_apg on e (hist <- the x0 of its projected guidance), state <- e. */
+int im360_cfg_multistep_step_apg_momentum(const void* uncond, const void* cond, const void* x, void* hist, void* state, void* out,
+                                          int64_t n, float guidance, float sqrt_a, float sqrt_b, float cx, float c0, float c1, int mode,
+                                          float eta, float threshold, const void* ws, int64_t ws_floats, float carry,
+                                          const void* carry_dev, int dtype, void* stream, const void* coef_dev);
+
+/* im360_cfg_multistep_step_windows_apg on e, state [outer, F, inner] <- e; wrap = 0 or F. */
+int im360_cfg_multistep_step_windows_apg_momentum(const void* pred, const void* x, void* hist, void* state, void* out,
+                                                  const void* start, const void* weight, int nW, int64_t outer, int64_t F, int64_t L,
+                                                  int64_t inner, int64_t wrap, float guidance, float sqrt_a, float sqrt_b, float cx,
+                                                  float c0, float c1, int mode, float eta, float threshold, const void* ws,
+                                                  int64_t ws_floats, float carry, const void* carry_dev, int dtype, void* stream,
+                                                  const void* coef_dev);
 
 /* ---- start latents of a run that begins from a given clip (AnimationPipeline init_latents / init_video, strength < 1), one launch:
  *   out_pano[c, f, p]    = T(sqrt_a * x0[c, f, p] + sqrt_b * noise[f, c, p])        fp32, one rounding, at the store

@@ -534,7 +534,8 @@ def apg_bench(args, sch, dev, dt, ts_host):
     """--apg ETA [R] at cfg2 size (16 frames, 512 x 1024, bf16): the captured step with adaptive projected guidance (a statistics launch
     and a step launch per branch), next to the plain captured step and the one with guidance_rescale = 0.7 (the same two-launch scheme),
     replays alternated round by round.  The six-coefficient step kernel serves all three (eta = 0 without either option runs
-    ``cfg_ddim_update``: the shipped default, timed as `plain_step`)."""
+    ``cfg_ddim_update``: the shipped default, timed as `plain_step`).  ``--apg-momentum BETA`` adds the captured step with the momentum
+    of the projected guidance (an fp32 state per branch and an uploaded carry) to the same alternated rounds."""
     from imagine360_amd.graph_step import GraphedDenoiseStep
     frames = 16
     apg = (float(args.apg[0]), float(args.apg[1]) if len(args.apg) > 1 else None)
@@ -550,11 +551,18 @@ def apg_bench(args, sch, dev, dt, ts_host):
     graphs = dict(plain_step=GraphedDenoiseStep(mv, sch, inp, cams, pano_lat, pers_lat, 7.5, warmup=1),
                   rescale_step=GraphedDenoiseStep(mv, sch, inp, cams, pano_lat, pers_lat, 7.5, warmup=1, guidance_rescale=0.7),
                   apg_step=GraphedDenoiseStep(mv, sch, inp, cams, pano_lat, pers_lat, 7.5, warmup=1, guidance_apg=apg))
+    if args.apg_momentum is not None:
+        graphs["apg_momentum_step"] = GraphedDenoiseStep(mv, sch, inp, cams, pano_lat, pers_lat, 7.5, warmup=1, guidance_apg=apg,
+                                                         guidance_apg_momentum=args.apg_momentum)
+        res["apg_momentum"] = args.apg_momentum
     torch.cuda.synchronize()
     res.update(time_steps(graphs, ts_host, args.steps, args.rounds))
     res["finite"] = all(bool(torch.isfinite(g.pano_lat.float()).all() and torch.isfinite(g.pers_lat.float()).all()) for g in graphs.values())
     res["apg_over_plain"] = res["apg_step"]["ms_median"] / res["plain_step"]["ms_median"]
     res["apg_over_rescale"] = res["apg_step"]["ms_median"] / res["rescale_step"]["ms_median"]
+    if args.apg_momentum is not None:
+        res["apg_momentum_over_apg"] = res["apg_momentum_step"]["ms_median"] / res["apg_step"]["ms_median"]
+        res["apg_momentum_over_apg_min"] = res["apg_momentum_step"]["ms_min"] / res["apg_step"]["ms_min"]
     res["note"] = ("randomly initialised weights: what APG does to a clip's look can only be judged with trained weights; host-clock ms around "
                    "replays that end in a device synchronise")
     return res
@@ -766,6 +774,8 @@ def main():
     ap.add_argument("--apg", type=float, nargs="+", default=None, metavar="ETA [R]",
                     help="the captured cfg2 step with adaptive projected guidance (apg_eta ETA, apg_threshold R; no R: no clamp) next to the plain "
                          "and the guidance-rescale step, interleaved (--steps replays per round, --rounds)")
+    ap.add_argument("--apg-momentum", type=float, default=None, metavar="BETA",
+                    help="with --apg: the captured step with the momentum of the projected guidance (apg_momentum BETA) in the same rounds")
     ap.add_argument("--pano-hw", type=int, nargs=2, default=[128, 256], metavar=("H", "W"), help="--init-scale: latent size of the full-size run (default: cfg5)")
     ap.add_argument("--sampler", choices=["ddim", "dpmpp2m"], default="ddim", help="the scheduler of every step and call (dpmpp2m: DPM-Solver++ 2M)")
     ap.add_argument("--context-level", choices=["model", "attention", "both"], default=None,

@@ -522,7 +522,9 @@ def bench_apg_step(iters):
     """Adaptive projected guidance against the guidance rescale on the two latents of cfg2: each is a statistics launch + a step launch
     (``K.cfg_ddim_step(..., apg=)`` / ``(..., rescale=)``), and so for the DPM-Solver++ 2M step; the plain single launch next to them.
     Device events, workspace and result allocation included, 5 rounds alternated, min / median.  By bytes the APG pair moves 7 16-bit
-    streams (statistics: u, c, x; step: u, c, x, out), the rescaled pair 6, the plain launch 4.  A JSON line per row, for profiles/."""
+    streams (statistics: u, c, x; step: u, c, x, out), the rescaled pair 6, the plain launch 4.  The momentum pair
+    (``apg_momentum=(state, carry)``) is timed in the same rounds, once with carry -0.5 (the fp32 state read by both launches and written
+    by the step: 12 bytes per element more) and once with carry 0 (written only: 4 more).  A JSON line per row, for profiles/."""
     import json
     from imagine360_amd import configs
     from imagine360_amd.scheduler import DDIMScheduler, DPMSolverMultistepScheduler
@@ -533,26 +535,39 @@ def bench_apg_step(iters):
     for name, shape in (("pano", (1, 4, 16, 64, 128)), ("pers", (1, 20, 4, 16, 32, 32))):
         u, c, x = rn(*shape) * 0.25, rn(*shape) * 0.25, rn(*shape)
         h = torch.zeros(shape, dtype=torch.float32, device=DEV)
+        st = torch.zeros(shape, dtype=torch.float32, device=DEV)          # the momentum state (finite under the chained replays: |carry| < 1)
         n = x.numel()
         mode = ddim.kernel_mode()
         cd, c2 = ddim.step_coefficients(t, 0.0, 7.5), dpm.multistep_coefficients(dpm._timesteps_host, 8, 7.5)
         rows = [("cfg_ddim_step", lambda: K.cfg_ddim_step(u, c, x, None, mode, cd), lambda: K.cfg_ddim_step(u, c, x, None, mode, cd, rescale=0.7),
-                 lambda: K.cfg_ddim_step(u, c, x, None, mode, cd, apg=apg), 0),
+                 lambda: K.cfg_ddim_step(u, c, x, None, mode, cd, apg=apg), 0,
+                 lambda carry: K.cfg_ddim_step(u, c, x, None, mode, cd, apg=apg, apg_momentum=(st, carry))),
                 ("cfg_multistep_step order 2", lambda: K.cfg_multistep_step(u, c, x, h, mode, c2),
-                 lambda: K.cfg_multistep_step(u, c, x, h, mode, c2, rescale=0.7), lambda: K.cfg_multistep_step(u, c, x, h, mode, c2, apg=apg), 8 * n)]
-        for label, plain, rescaled, projected, extra in rows:
-            tp, tr, ta = [], [], []
+                 lambda: K.cfg_multistep_step(u, c, x, h, mode, c2, rescale=0.7), lambda: K.cfg_multistep_step(u, c, x, h, mode, c2, apg=apg), 8 * n,
+                 lambda carry: K.cfg_multistep_step(u, c, x, h, mode, c2, apg=apg, apg_momentum=(st, carry)))]
+        for label, plain, rescaled, projected, extra, momentum in rows:
+            tp, tr, ta, tm, t0 = [], [], [], [], []
             for _ in range(5):                      # alternated
                 tp.append(timeit(plain, iters))
                 tr.append(timeit(rescaled, iters))
                 ta.append(timeit(projected, iters))
-            tp, tr, ta = sorted(tp), sorted(tr), sorted(ta)
+                tm.append(timeit(lambda: momentum(-0.5), iters))
+                t0.append(timeit(lambda: momentum(0.0), iters))
+            tp, tr, ta, tm, t0 = sorted(tp), sorted(tr), sorted(ta), sorted(tm), sorted(t0)
             row = dict(bench="apg_step", latent=name, elements=n, kernel=label, iters=iters, plain_us=[v * 1e6 for v in (tp[0], tp[2])],
                        rescale_us=[v * 1e6 for v in (tr[0], tr[2])], apg_us=[v * 1e6 for v in (ta[0], ta[2])],
                        plain_mb=(8 * n + extra) / 1e6, rescale_mb=(12 * n + extra) / 1e6, apg_mb=(14 * n + extra) / 1e6,
-                       apg_over_rescale_min=ta[0] / tr[0], apg_over_rescale_median=ta[2] / tr[2], apg_over_plain_min=ta[0] / tp[0])
+                       apg_over_rescale_min=ta[0] / tr[0], apg_over_rescale_median=ta[2] / tr[2], apg_over_plain_min=ta[0] / tp[0],
+                       momentum_us=[v * 1e6 for v in (tm[0], tm[2])], momentum_carry0_us=[v * 1e6 for v in (t0[0], t0[2])],
+                       momentum_mb=(26 * n + extra) / 1e6, momentum_carry0_mb=(18 * n + extra) / 1e6,
+                       momentum_over_apg_min=tm[0] / ta[0], momentum_over_apg_median=tm[2] / ta[2],
+                       momentum_carry0_over_apg_min=t0[0] / ta[0], momentum_carry0_over_apg_median=t0[2] / ta[2],
+                       bytes_ratio=(26 * n + extra) / (14 * n + extra), bytes_ratio_carry0=(18 * n + extra) / (14 * n + extra))
             print(f"apg_step {name} {n:8d} elements  {label:28s}: plain {tp[0] * 1e6:7.2f} us  rescale {tr[0] * 1e6:7.2f} us min {tr[2] * 1e6:7.2f} us median  "
                   f"apg {ta[0] * 1e6:7.2f} us min {ta[2] * 1e6:7.2f} us median  | apg / rescale {ta[0] / tr[0]:4.2f}x min {ta[2] / tr[2]:4.2f}x median")
+            print(f"apg_step {name} {n:8d} elements  {label:28s}: momentum {tm[0] * 1e6:7.2f} us min {tm[2] * 1e6:7.2f} us median, carry 0 "
+                  f"{t0[0] * 1e6:7.2f} us min  | momentum / apg {tm[0] / ta[0]:4.2f}x min {tm[2] / ta[2]:4.2f}x median (bytes "
+                  f"{(26 * n + extra) / (14 * n + extra):4.2f}x), carry 0 / apg {t0[0] / ta[0]:4.2f}x min (bytes {(18 * n + extra) / (14 * n + extra):4.2f}x)")
             print("JSON", json.dumps(row))
 
 

@@ -27,13 +27,14 @@ tolerance does not count as checked; multi-process tests are not traced):
     python -m pytest -q -m gpu tests/test_temporal_windows_gpu.py::test_windows_kernel_vs_fp64
     python -m pytest -q -m gpu tests/test_ff_fused_gpu.py
     python -m pytest -q -m gpu tests/test_projected_guidance_gpu.py::test_cfg_apg_scalars_vs_fp64 tests/test_projected_guidance_gpu.py::test_apg_ddim_step_kernel_all_modes tests/test_projected_guidance_gpu.py::test_apg_multistep_step_kernel_all_modes tests/test_projected_guidance_gpu.py::test_apg_windows_kernels_vs_fp64
+    python -m pytest -q -m gpu tests/test_apg_momentum_gpu.py::test_momentum_scalars_vs_fp64 tests/test_apg_momentum_gpu.py::test_momentum_ddim_step_kernel_all_modes tests/test_apg_momentum_gpu.py::test_momentum_multistep_step_kernel_all_modes tests/test_apg_momentum_gpu.py::test_momentum_windows_kernels_vs_fp64
 
 each as   rocprofv3 --kernel-trace --stats -M --output-format csv -d <dir>/<label> -o trace -- <command>   (mangled names; kernel trace only,
 no counters), one rocprofv3 invocation per command, each under its own `timeout -k 10`; the job stops at the first step that fails.
 
     python tools/kernel_launch_coverage.py --emit-script <dir> > job.sh      # the MI355X job: per command an untraced run (its wall time x 3 is
                                                                             # the traced run's time limit), then the traced run; writes <dir>/<label>/
-    python tools/kernel_launch_coverage.py --collect <dir> --commit <hash>   # <dir>/<label>/*kernel_stats.csv + meta.json -> tests/golden/kernel_launch_ledger_apg.json
+    python tools/kernel_launch_coverage.py --collect <dir> --commit <hash>   # <dir>/<label>/*kernel_stats.csv + meta.json -> tests/golden/kernel_launch_ledger_apg_momentum.json
     python tools/kernel_launch_coverage.py --collect <dir> --label <label>   # only these runs were traced again: the other runs' launches are taken
                                                                             # over from --base (default: the previous ledger) for the kernels the library still has
     python tools/kernel_launch_coverage.py --report                          # library kernels against the ledger: unlaunched, stale, unpaired dtypes
@@ -59,10 +60,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # free_init kernels, kernel_launch_ledger_freeinit.json the one before keep_latents_kernel took its RELEASE argument and
 # sphere_distance2_kernel, kernel_launch_ledger_release.json the one before the step kernels took their GUIDED argument and ddim_kernel,
 # kernel_launch_ledger_interval.json the one before temporal_attn_windows_kernel, kernel_launch_ledger_tattn_windows.json the one before
-# ff_fused_kernel, kernel_launch_ledger_ff_fused.json the one before the adaptive-projected-guidance kernels: all thirteen kept as they
-# were; the last one is read only as the default --base of a partial --collect)
-LEDGER = os.path.join(ROOT, "tests", "golden", "kernel_launch_ledger_apg.json")
-PREVIOUS_LEDGER = os.path.join(ROOT, "tests", "golden", "kernel_launch_ledger_ff_fused.json")
+# ff_fused_kernel, kernel_launch_ledger_ff_fused.json the one before the adaptive-projected-guidance kernels,
+# kernel_launch_ledger_apg.json the one before their momentum forms: all fourteen kept as they were; the last one is read only as the
+# default --base of a partial --collect)
+LEDGER = os.path.join(ROOT, "tests", "golden", "kernel_launch_ledger_apg_momentum.json")
+PREVIOUS_LEDGER = os.path.join(ROOT, "tests", "golden", "kernel_launch_ledger_apg.json")
 LIB = os.path.join(ROOT, "imagine360_amd", "libim360_kernels.so")
 LLVM = "/opt/rocm/lib/llvm/bin"
 PREFIX = "_ZN5im360"
@@ -96,7 +98,11 @@ RUNS = [("test_kernels_gpu", ["tests/test_kernels_gpu.py"]),
         ("test_projected_guidance_gpu", ["tests/test_projected_guidance_gpu.py::test_cfg_apg_scalars_vs_fp64",
                                          "tests/test_projected_guidance_gpu.py::test_apg_ddim_step_kernel_all_modes",
                                          "tests/test_projected_guidance_gpu.py::test_apg_multistep_step_kernel_all_modes",
-                                         "tests/test_projected_guidance_gpu.py::test_apg_windows_kernels_vs_fp64"])]
+                                         "tests/test_projected_guidance_gpu.py::test_apg_windows_kernels_vs_fp64"]),
+        ("test_apg_momentum_gpu", ["tests/test_apg_momentum_gpu.py::test_momentum_scalars_vs_fp64",
+                                   "tests/test_apg_momentum_gpu.py::test_momentum_ddim_step_kernel_all_modes",
+                                   "tests/test_apg_momentum_gpu.py::test_momentum_multistep_step_kernel_all_modes",
+                                   "tests/test_apg_momentum_gpu.py::test_momentum_windows_kernels_vs_fp64"])]
 
 
 def command(args):
